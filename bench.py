@@ -10,8 +10,14 @@ Workload (BASELINE.json configs[1] + planted SVs so that the getsv passes have j
 150 bp paired end, ~617 M records per GPU, 1 % random soft clips, 10 k planted DEL/INV/TRA at VAF 0.5.  With N GPUs the
 depth is 30x * N over the same genome (weak scaling: per-GPU records fixed), range-partitioned by reference interval.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome-frac F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome-frac F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything measured beside the headline:
+the per-kernel breakdown steps and the roofline, the host link probes, BASELINE config 3's shape, the BAM file leg and the `seeksv`
+binary on it, BASELINE config 5 through the product, host batches, the CPU baselines and (N > 1) the product's own ranks.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, float32 for sampled string bytes; a fixed, seeded
+sample of the cluster table).
 """
 import argparse
 import json
@@ -75,7 +81,13 @@ def main():
                     "strong = BASELINE config 4: ONE sample of --strong-depth (300x tumor WGS, 6.18 G records) range-partitioned N ways; refused where a rank's share does not fit its GPU")
     ap.add_argument("--strong-depth", type=float, default=300.0, help="coverage of the one sample that --scaling strong splits over the GPUs")
     ap.add_argument("--no-overlap", action="store_true", help="collect every cluster table in its own step (no copy in flight while other kernels run); use under rocprofv3, which serialises dispatches of different streams")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline too (breakdown steps + roofline, host link probes, config3 / file / cli / config5 / "
+                    "host batch / CPU baseline legs, ranks_path for N > 1); off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (cluster table sample, getsv counts and depths, "
+                    "the folded per-junction values) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` by itself: this process starts the N ranks - one fresh process per GPU through torch.distributed.run, the launch the
@@ -121,7 +133,7 @@ def main():
     from seeksv_amd import host, shard, synth
     from seeksv_amd.device import Context
 
-    def resident(args, ctx=None):
+    def resident(args, ctx=None, dump_dir=None):
         """the resident-input leg on one workload (args.depth / args.genome_frac / args.n_sv): generation, K timed steps, the breakdown steps"""
 
         strong = args.scaling == "strong"
@@ -188,6 +200,7 @@ def main():
                 state["table_bytes"] = n * (4 + 2 * t.len_bytes + t.support_bytes + t.ncig_bytes + 1) + t.str_bytes + t.cigar_bytes * t.cigar_ops + 16 * t.n_runs + 8 * t.n_base_exc
             else:
                 state["table_bytes"] = n * 42 + t.str_bytes + 4 * t.cigar_ops
+            state["last_table"] = t   # (the table of the step collected last: --dump-outputs reads it after the timed steps)
             state["table_info"] = dict(format=int(t.format), qual_bits=int(t.qual_bits), qual_group=int(t.qual_group), cigar_bytes=int(t.cigar_bytes), base_bits=int(t.base_bits), base_exceptions=int(t.n_base_exc))
             ssum = int(t.support_sum) if t.format == 3 else (int(np.ctypeslib.as_array(t.support, shape=(n,)).sum()) if n else 0)
             assert ssum == t.n_events, "clip events were lost or duplicated"
@@ -262,6 +275,7 @@ def main():
             folded = plan.fold(merged[0], merged[1], merged[2])
             plan.close()
             lap("host_fold")
+            state["last_step"] = (merged, folded, mean, sd, max_depth)
             return dict(n_clusters=merged[3], n_events=merged[4], support_sum=merged[5], mean=mean, sd=sd, abnormal_sum=int(folded["abnormal"].sum()),
                         depth_sum=int(folded["up_depth"].sum() + folded["down_depth"].sum()), flank_sum=int(folded["flank"].sum()), max_depth=max_depth)
 
@@ -312,31 +326,38 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=coll_dev if coll_dev is not None else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        # three extra, untimed steps with every kernel group bracketed by events, nothing else in flight: the per-kernel breakdown (per-step means:
-        # one launch of a sub-millisecond kernel varies by a few percent)
-        BREAKDOWN_STEPS = 3
-        ctx.prof_reset()
-        ctx.prof_enable(1)
-        for _ in range(BREAKDOWN_STEPS):
-            step(wall)
-            drain()
-        allprof = ctx.prof_all()
-        for v in allprof.values():   # per step
-            v["total_ms"] /= BREAKDOWN_STEPS
-            v["launches"] = v["launches"] // BREAKDOWN_STEPS if v["launches"] >= BREAKDOWN_STEPS else v["launches"]
-            v["units"] = v["units"] // BREAKDOWN_STEPS
-        for k in list(wall):
-            wall[k] /= BREAKDOWN_STEPS
-        breakdown = {k: round(v["total_ms"], 4) for k, v in allprof.items() if v["launches"]}
-        ctx.prof_enable(0)
+        if dump_dir is not None and rank == 0:
+            # before anything else runs on the context: the last step's table stays valid until the second-next clustering
+            dump_outputs(dump_dir, state["last_table"], *state["last_step"], support_sum=state["support_sum"])
+        breakdown, allprof, BREAKDOWN_STEPS = {}, {}, 0
+        if args.full:
+            # three extra, untimed steps with every kernel group bracketed by events, nothing else in flight: the per-kernel breakdown (per-step means:
+            # one launch of a sub-millisecond kernel varies by a few percent)
+            BREAKDOWN_STEPS = 3
+            ctx.prof_reset()
+            ctx.prof_enable(1)
+            for _ in range(BREAKDOWN_STEPS):
+                step(wall)
+                drain()
+            allprof = ctx.prof_all()
+            for v in allprof.values():   # per step
+                v["total_ms"] /= BREAKDOWN_STEPS
+                v["launches"] = v["launches"] // BREAKDOWN_STEPS if v["launches"] >= BREAKDOWN_STEPS else v["launches"]
+                v["units"] = v["units"] // BREAKDOWN_STEPS
+            for k in list(wall):
+                wall[k] /= BREAKDOWN_STEPS
+            breakdown = {k: round(v["total_ms"], 4) for k, v in allprof.items() if v["launches"]}
+            ctx.prof_enable(0)
         del scan_batch, scan_t, own_batch, prefix_batch, prefix_t   # (the sample leaves HBM with the leg)
         return dict(locals())
 
     link = {"what": "device <-> pinned host through hipMemcpyAsync (the runtime's choice of SDMA engine), 256 MB, [median, slowest] GB/s of four copies, taken between the legs (host_link_probe)"}
     gpu_dev = dev
-    link["before"] = host_link_probe(torch, gpu_dev)
-    R = resident(args)
-    link["after the resident leg"] = host_link_probe(torch, gpu_dev)
+    if args.full:
+        link["before"] = host_link_probe(torch, gpu_dev)
+    R = resident(args, dump_dir=args.dump_outputs)
+    if args.full:
+        link["after the resident leg"] = host_link_probe(torch, gpu_dev)
     import gc
     gc.collect()
     torch.cuda.empty_cache()
@@ -353,47 +374,48 @@ def main():
         assert state["tables"] >= args.steps, "every step's cluster table must have reached the host"
         total_records = w.n_total
         ms_per_step = dt / args.steps * 1e3
-        # Roofline: the whole path.  achieved = SURVEY 8(d)'s 40 B/record x this rank's records / the sum of ALL device kernels of one step
-        # (HIP events on the context's stream around every kernel group, nothing else in flight: the extra breakdown steps above); every
-        # group is listed with its own time, its byte model where it has one and - from the committed PMC passes (profiles/traffic.json) - the
-        # HBM bytes it really moved; the longest group is named.  The two streaming kernels (the only ones that touch every record) are also
-        # timed inside the K timed steps, the table copy of the previous step in flight beside them.
-        dev = {k: v for k, v in allprof.items() if k in DEVICE_GROUPS and v["launches"]}
-        dev_ms = sum(v["total_ms"] for v in dev.values())
-        longest = max(dev, key=lambda k: dev[k]["total_ms"])
-        traffic = {}
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                traffic = json.load(open(tpath))
-            except Exception:
-                traffic = {}
-        scale = n_own / traffic["records"] if traffic.get("records") else None   # the PMC passes ran the default workload
-
-        def group_entry(k, v):
-            per = v["total_ms"]
-            units = v["units"] / max(v["launches"], 1) if k in ("clip_scan", "getsv_scan", "clip_place", "event_sort", "cluster_pack") else None
-            e = {"ms": round(per, 4)}
-            if k in ALGO_BYTES and units:
-                e["units"] = int(units)
-                e["algorithmic_bytes_per_unit"] = ALGO_BYTES[k]
-                e["achieved_GBs"] = round(ALGO_BYTES[k] * units / (per * 1e-3) / 1e9, 1)
-                e["frac"] = round(e["achieved_GBs"] / HBM_PEAK_GBS, 3)
-            t = traffic.get("groups", {}).get(k)
-            if t is not None and scale is not None and abs(scale - 1.0) < 0.02:
-                e["traffic_bytes"] = t
-                e["hbm_frac_measured"] = round(t / (per * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)   # the group's counter bytes over its time: the share of the memory system it really uses
-            return e
-
-        groups = {k: group_entry(k, v) for k, v in dev.items()}
-        path_bytes = PATH_BYTES_PER_RECORD * n_own
-        achieved = path_bytes / (dev_ms * 1e-3) / 1e9
-        total_traffic = traffic.get("path_bytes_per_step") if (scale is not None and abs(scale - 1.0) < 0.02) else None
         timed = {}
         for k in ("clip_scan", "getsv_scan"):
             if prof.get(k, {}).get("launches"):
                 timed[k] = {"avg_launch_ms": round(prof[k]["total_ms"] / prof[k]["launches"], 4), "launches_timed": int(prof[k]["launches"]),
                             "achieved_GBs": round(ALGO_BYTES[k] * (prof[k]["units"] / prof[k]["launches"]) / (prof[k]["total_ms"] / prof[k]["launches"] * 1e-3) / 1e9, 1)}
+        if args.full:
+            # Roofline: the whole path.  achieved = SURVEY 8(d)'s 40 B/record x this rank's records / the sum of ALL device kernels of one step
+            # (HIP events on the context's stream around every kernel group, nothing else in flight: the extra breakdown steps above); every
+            # group is listed with its own time, its byte model where it has one and - from the committed PMC passes (profiles/traffic.json) - the
+            # HBM bytes it really moved; the longest group is named.  The two streaming kernels (the only ones that touch every record) are also
+            # timed inside the K timed steps, the table copy of the previous step in flight beside them.
+            dev = {k: v for k, v in allprof.items() if k in DEVICE_GROUPS and v["launches"]}
+            dev_ms = sum(v["total_ms"] for v in dev.values())
+            longest = max(dev, key=lambda k: dev[k]["total_ms"])
+            traffic = {}
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    traffic = json.load(open(tpath))
+                except Exception:
+                    traffic = {}
+            scale = n_own / traffic["records"] if traffic.get("records") else None   # the PMC passes ran the default workload
+
+            def group_entry(k, v):
+                per = v["total_ms"]
+                units = v["units"] / max(v["launches"], 1) if k in ("clip_scan", "getsv_scan", "clip_place", "event_sort", "cluster_pack") else None
+                e = {"ms": round(per, 4)}
+                if k in ALGO_BYTES and units:
+                    e["units"] = int(units)
+                    e["algorithmic_bytes_per_unit"] = ALGO_BYTES[k]
+                    e["achieved_GBs"] = round(ALGO_BYTES[k] * units / (per * 1e-3) / 1e9, 1)
+                    e["frac"] = round(e["achieved_GBs"] / HBM_PEAK_GBS, 3)
+                t = traffic.get("groups", {}).get(k)
+                if t is not None and scale is not None and abs(scale - 1.0) < 0.02:
+                    e["traffic_bytes"] = t
+                    e["hbm_frac_measured"] = round(t / (per * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)   # the group's counter bytes over its time: the share of the memory system it really uses
+                return e
+
+            groups = {k: group_entry(k, v) for k, v in dev.items()}
+            path_bytes = PATH_BYTES_PER_RECORD * n_own
+            achieved = path_bytes / (dev_ms * 1e-3) / 1e9
+            total_traffic = traffic.get("path_bytes_per_step") if (scale is not None and abs(scale - 1.0) < 0.02) else None
         line = {
             "metric": "BAM records/sec through getclip+getsv",
             "value": total_records * args.steps / dt,
@@ -408,31 +430,34 @@ def main():
                                     ("; this leg's exchange: ONE torch.distributed.all_gather per step (RCCL, one process per GPU); the product's own exchange (ssv_group_allgather = ncclAllGather from the host library, ranks as threads of `seeksv -N`) is timed in ranks_path" if world > 1 else ""),
                        "batch_layout": "hot columns tid/pos/n_cigar + cigar_ends (a one-byte copy of the first and last CIGAR operation codes: the getclip stream reads it and applies the soft-clip test to every record) + the tid column also as runs (one per contig: the getsv stream reads pos only) + one 64-byte line per record (ssv_record) + CIGARs + packed bases/qualities of soft-clipped records; SSV_MEM_PERSISTENT",
                        "host_cpus_bound_near_gpu": near_cpus, "generation_s": round(gen_s, 2)},
-            "roofline": {"kernel": "path: all device kernels of one step (getclip + insert size + getsv passes; PCIe copy excluded)", "bound": "hbm",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": total_traffic,
-                         # `traffic` is NOT measured in this run: PMC passes cannot run inside a bench line.  It is the committed counter file of the builder's
-                         # PMC passes over this same command; used only when this run's records per GPU equal that file's (within 2 %: the rank split), null otherwise
-                         "traffic_source": (f"profiles/traffic.json ({traffic.get('_round', 'builder-run')} rocprofv3 PMC passes over `bench.py --steps 1 --warmup 1 --no-overlap`, "
-                                            f"{traffic.get('records')} records; this run: {n_own} records per GPU)" if total_traffic else
-                                            f"none: profiles/traffic.json holds {traffic.get('records')} records per GPU, this run {n_own}"),
-                         # the other way to read the same launches: the bytes the kernels really moved (PMC counters) over their time.  The path reads 18 of the 40
-                         # "read every field once" bytes (the cold 64-byte lines are touched for 1-2 % of the records only), so `frac` (work done per second against
-                         # the peak) is higher than the share of the memory system that is in use.
-                         "hbm_frac_measured": (round(total_traffic / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if total_traffic else None),
-                         "note": "frac is the contract's budget figure: SURVEY 8(d)'s 40 B/record x records / the step's device time / 8 TB/s - the path reads ~14 of those 40 bytes (the cold "
-                                 "64-byte lines are touched for 1-2 % of the records), so kernels-only it can exceed 1 and says how fast the WORK is done, not how busy the memory is; "
-                                 "hbm_frac_measured (counter bytes over the same time, here and per group) is the utilisation figure",
-                         "algorithmic_bytes_per_record": PATH_BYTES_PER_RECORD, "records_per_launch": float(n_own), "avg_launch_ms": round(dev_ms, 4),
-                         "launches_timed": BREAKDOWN_STEPS, "dominant_group": {"name": longest, **groups[longest]},
-                         "groups": groups, "streaming_kernels_in_timed_region": timed},
-            "kernel_ms_one_step": breakdown,
-            "wall_ms_one_step": {k: round(v, 3) for k, v in wall.items()},
             "wall_ms_timed_steps": step_walls,
+            "streaming_kernels_in_timed_region": timed,
             "result": res,
             "table": dict(state.get("table_info", {}), host_expand_ms=[round(x, 2) for x in state.get("expand_ms", [])[-6:]], wait_ms=[round(x, 2) for x in state.get("wait_ms", [])[-6:]], bytes=int(state.get("table_bytes", 0)), bytes_per_cluster=round(state.get("table_bytes", 0) / max(1, res["n_clusters"]), 1),
                           note="what crosses PCIe per step; format 3: contig / side / offsets are rebuilt on the host inside the step (ssv_clip_table_expand)"),
         }
-        if world == 1 and not args.no_config3 and not strong:
+        if args.full:
+            line.update({
+                "roofline": {"kernel": "path: all device kernels of one step (getclip + insert size + getsv passes; PCIe copy excluded)", "bound": "hbm",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": total_traffic,
+                             # `traffic` is NOT measured in this run: PMC passes cannot run inside a bench line.  It is the committed counter file of the builder's
+                             # PMC passes over this same command; used only when this run's records per GPU equal that file's (within 2 %: the rank split), null otherwise
+                             "traffic_source": (f"profiles/traffic.json ({traffic.get('_round', 'builder-run')} rocprofv3 PMC passes over `bench.py --full --steps 1 --warmup 1 --no-overlap`, "
+                                                f"{traffic.get('records')} records; this run: {n_own} records per GPU)" if total_traffic else
+                                                f"none: profiles/traffic.json holds {traffic.get('records')} records per GPU, this run {n_own}"),
+                             # the other way to read the same launches: the bytes the kernels really moved (PMC counters) over their time.  The path reads 18 of the 40
+                             # "read every field once" bytes (the cold 64-byte lines are touched for 1-2 % of the records only), so `frac` (work done per second against
+                             # the peak) is higher than the share of the memory system that is in use.
+                             "hbm_frac_measured": (round(total_traffic / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if total_traffic else None),
+                             "note": "frac is the contract's budget figure: SURVEY 8(d)'s 40 B/record x records / the step's device time / 8 TB/s - the path reads ~14 of those 40 bytes (the cold "
+                                     "64-byte lines are touched for 1-2 % of the records), so kernels-only it can exceed 1 and says how fast the WORK is done, not how busy the memory is; "
+                                     "hbm_frac_measured (counter bytes over the same time, here and per group) is the utilisation figure",
+                             "algorithmic_bytes_per_record": PATH_BYTES_PER_RECORD, "records_per_launch": float(n_own), "avg_launch_ms": round(dev_ms, 4),
+                             "launches_timed": BREAKDOWN_STEPS, "dominant_group": {"name": longest, **groups[longest]},
+                             "groups": groups, "streaming_kernels_in_timed_region": timed},
+                "kernel_ms_one_step": breakdown,
+                "wall_ms_one_step": {k: round(v, 3) for k, v in wall.items()}})
+        if args.full and world == 1 and not args.no_config3 and not strong:
             # BASELINE config 3's shape on one GPU: ten times the depth over a tenth of the genome - the same number of records resident in HBM, the
             # same 10,000 planted SVs, but every planted breakpoint's bin holds 50-150 clipped reads and every junction window ten times the records
             # (the full 6.18 G-record sample does not fit one GPU at once: tests/test_full_size_gpu.py streams it).  Same step, same timing rules.
@@ -462,7 +487,7 @@ def main():
                 torch.cuda.empty_cache()   # (the 49 GB sample goes back to the device: the file leg below keeps its own 49 GB of decoded records)
             except BaseException as e:  # (SystemExit too: a report beside the headline)
                 line["config3_path"] = {"error": f"{type(e).__name__}: {e}"}
-        if args.file_frac < 0:
+        if args.full and args.file_frac < 0:
             cores_here = os.cpu_count() or 1
             try:
                 avail_gb = next(int(l.split()[1]) for l in open("/proc/meminfo") if l.startswith("MemAvailable:")) / (1 << 20)
@@ -485,7 +510,7 @@ def main():
         if args.file_level == "auto":
             args.file_level = "6"
         args.file_level = -2 if args.file_level == "fast" else int(args.file_level)
-        if world == 1 and args.file_frac > 0:
+        if args.full and world == 1 and args.file_frac > 0:
             try:
                 line["file_path"] = file_path_leg(ctx, args, local_rank)
                 if args.file_frac == args.genome_frac and isinstance(line.get("result"), dict):
@@ -494,9 +519,9 @@ def main():
                     line["file_path"]["same_result_as_resident_path"] = all(fr[k] == line["result"][k] for k in fr if k in line["result"])
             except Exception as e:  # the leg is a report beside the headline, never a reason to lose the line
                 line["file_path"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.file_frac > 0:
+        if args.full and world == 1 and args.file_frac > 0:
             link["after file_path + cli_path"] = host_link_probe(torch, gpu_dev)
-        if world == 1 and args.config5_frac != 0 and not strong:
+        if args.full and world == 1 and args.config5_frac != 0 and not strong:
             try:
                 if args.config5_frac < 0:
                     args.config5_frac = args.genome_frac / 16
@@ -504,12 +529,12 @@ def main():
                 line["config5_path"] = config5_path_leg(args)
             except Exception as e:
                 line["config5_path"] = {"error": f"{type(e).__name__}: {e}"}
-        if world > 1 and args.ranks_frac > 0:
+        if args.full and world > 1 and args.ranks_frac > 0:
             try:
                 line["ranks_path"] = ranks_path_leg(args, world, os.environ.get("SSV_FORCE_DEVICE"))
             except Exception as e:
                 line["ranks_path"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_host_batch and not strong:
+        if args.full and world == 1 and not args.no_host_batch and not strong:
             # the boundary handing over HOST buffers (what libseeksv_host's reader produces): SoA batches, 49.5 B/record, through the staging path - never `value`
             try:
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -520,7 +545,7 @@ def main():
                 line["host_batch_path"] = hbp
             except Exception as e:
                 line["host_batch_path"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
             # the three host legs are reports beside the headline; the two single-threaded ones (the oracle in this process, the real reference
             # binary as a child process) run side by side, then every core gets an oracle worker for a few seconds: ~20 s in all
             box = {}
@@ -533,11 +558,65 @@ def main():
             allc = cpu_baseline_all_cores(args, w, seconds=4.0)
             if allc:
                 line["cpu_baseline_all_cores"] = allc
-        line["host_link_GBs"] = link
+        if args.full:
+            line["host_link_GBs"] = link
         print(json.dumps(line))
     if world > 1:
         dist.barrier(group=wait_group)
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20261016
+DUMP_TABLE_ROWS = 1 << 18      # sampled clusters: their index and 10 columns in float64 = 23 MB
+DUMP_STR_BYTES = 1 << 22       # sampled bytes of the table's string blocks (seeded positions, the same for the same str bytes count): 17 MB as float32
+DUMP_CIGAR_OPS = 1 << 20       # sampled CIGAR operations, likewise: 8 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, t, merged, folded, mean, sd, max_depth, support_sum):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files (float32 for byte streams): the
+    cluster table (getclip's output; every column at a fixed, seeded sample of its rows, the string and CIGAR streams at seeded positions),
+    the getsv counts and depths as merged over the ranks, the per-junction values folded from them, and the scalars"""
+    import ctypes as C
+    os.makedirs(d, exist_ok=True)
+    n = int(t.n_clusters)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+
+    def sample(total, k):
+        return np.arange(total, dtype=np.int64) if total <= k else np.sort(rng.choice(total, k, replace=False))
+
+    def column(ptr, count, dt, idx):
+        if count == 0:
+            return np.zeros(0, np.float64)
+        assert ptr, "a column of the table is missing"
+        return np.frombuffer((C.c_uint8 * (count * np.dtype(dt).itemsize)).from_address(C.cast(ptr, C.c_void_p).value), dtype=dt)[idx].astype(np.float64)
+
+    rows = sample(n, DUMP_TABLE_ROWS)
+    out["clip_table_row_index"] = rows.astype(np.float64)
+    for name, dt in (("tid", np.int32), ("pos", np.int32), ("side", np.uint8), ("support", np.int32), ("left_len", np.int32), ("right_len", np.int32),
+                     ("qual_missing", np.uint8), ("n_cigar", np.int32), ("str_off", np.uint64), ("cigar_off", np.uint64)):
+        out["clip_table_" + name] = column(getattr(t, name), n, dt, rows)
+    sb, ops = int(t.str_bytes), int(t.cigar_ops)
+    si = sample(sb, DUMP_STR_BYTES)
+    out["clip_table_str_sample"] = column(t.str, sb, np.uint8, si).astype(np.float32)
+    ci = sample(ops, DUMP_CIGAR_OPS)
+    if int(t.format) == 3 and int(t.cigar_bytes) == 2:   # (16-bit operations: `cigar` is NULL, c_cigar holds them)
+        out["clip_table_cigar_sample"] = column(t.c_cigar, ops, np.uint16, ci)
+    else:
+        out["clip_table_cigar_sample"] = column(t.cigar, ops, np.uint32, ci)
+    out["getsv_discordant_counts"] = np.asarray(merged[0], np.float64)
+    out["getsv_range_sums"] = np.asarray(merged[1], np.float64)
+    out["getsv_point_depths"] = np.asarray(merged[2], np.float64)
+    for k, v in folded.items():
+        out["junction_" + k] = np.asarray(v, np.float64)
+    out["scalars"] = np.array([n, int(t.n_events), support_sum, sb, ops, mean, sd, max_depth], np.float64)   # n_clusters, n_events, support_sum, str bytes, CIGAR ops, mean, sd, max depth
+    out = {k: a for k, a in out.items() if a.size}   # (an output that holds nothing - extra_point_depth without extra points - is not written)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(out)} arrays, {total / 1e6:.1f} MB in {d}", file=sys.stderr)
 
 
 def host_link_probe(torch, dev):

@@ -1,6 +1,7 @@
 """-m gpu: bench.py at a small size prints ONE JSON line that keeps the driver's contract (metric / value / unit / n_gpus / steps / warmup /
-ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, roofline, cpu_baseline), and the two-rank code path
-gives the same result as the one-rank path on the same total workload (two ranks on one GPU over gloo: the test hook of bench.py)."""
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload; with --full also roofline, cpu_baseline and the legs beside
+the headline), a plain run does only the headline and --dump-outputs writes the same outputs twice, and the two-rank code path gives the same
+result as the one-rank path on the same total workload (two ranks on one GPU over gloo: the test hook of bench.py)."""
 import json
 import os
 import socket
@@ -20,7 +21,7 @@ def _line(out):
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "3", "--warmup", "1", "--cpu-sample", "300000", "--ref-sample", "0", "--config5-frac", "0.0009765625"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "3", "--warmup", "1", "--cpu-sample", "300000", "--ref-sample", "0", "--config5-frac", "0.0009765625"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-600:]
     d = _line(r.stdout)
@@ -58,11 +59,43 @@ def test_bench_line_contract():
     assert (rf["traffic"] is None) == rf["traffic_source"].startswith("none")
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """without --full: the headline only (no leg beside it), --steps timed steps; --dump-outputs: float arrays within 64 MB, the same from run to run
+    (two runs with different step counts over the same inputs)"""
+    import numpy as np
+    dumps = []
+    for steps in (3, 2):
+        d = tmp_path / f"out{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-600:]
+        a = _line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "result"):
+            assert k in a, k
+        assert a["steps"] == steps and a["warmup"] == 1 and a["unit"] == "records/s" and a["higher_is_better"] is True
+        assert len([w for w in a["wall_ms_timed_steps"] if not isinstance(w, list)]) == steps
+        assert abs(a["value"] - a["config"]["records_total"] / (a["ms_per_step"] * 1e-3)) < 1e-6 * a["value"]
+        for k in ("roofline", "kernel_ms_one_step", "cpu_baseline", "file_path", "config3_path", "config5_path", "host_batch_path", "host_link_GBs"):
+            assert k not in a, k
+        files = sorted(p.name for p in d.iterdir())
+        assert "scalars.npy" in files and "clip_table_pos.npy" in files and "getsv_discordant_counts.npy" in files
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(x.dtype in (np.float32, np.float64) and x.size > 0 for x in arrays.values())
+        assert sum(x.nbytes for x in arrays.values()) <= 64 << 20
+        s = arrays["scalars.npy"]
+        assert s[0] == a["result"]["n_clusters"] and s[1] == a["result"]["n_events"] and s[2] == a["result"]["support_sum"]
+        assert len(arrays["clip_table_pos.npy"]) == min(int(s[0]), 1 << 18) and arrays["junction_abnormal.npy"].sum() == a["result"]["abnormal_sum"]
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_under_torchrun_with_one_rank_is_the_plain_line():
     """the driver's scaling run starts N = 1 through torch.distributed.run too: same footing as the plain `python bench.py` line (same workload, same legs
     beside the headline, same counts) - SCALE's N = 1 must agree with BENCH"""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    common = ["--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1", "--cpu-sample", "200000", "--ref-sample", "0"]
+    common = ["--full", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1", "--cpu-sample", "200000", "--ref-sample", "0"]
     r1 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
                          os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-800:]
@@ -83,7 +116,7 @@ def test_bench_two_ranks_equal_one():
     env = dict(os.environ, SSV_FORCE_DEVICE="0", SSV_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, env=env)
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, env=env)
     assert r2.returncode == 0, r2.stderr[-800:]
     a = _line(r2.stdout)
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome-frac", "0.00390625", "--n-sv", "200", "--depth", "60", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--config5-frac", "0"],
@@ -105,7 +138,7 @@ def test_bench_eight_forced_ranks_strong_scaling_dry_run():
     env = dict(os.environ, SSV_FORCE_DEVICE="0", SSV_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--scaling", "strong", "--strong-depth", "60", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--scaling", "strong", "--strong-depth", "60", "--genome-frac", "0.00390625", "--n-sv", "200", "--steps", "2", "--warmup", "1",
                         "--ranks-frac", "0.5"], capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-800:]
     a = _line(r.stdout)

@@ -1,10 +1,13 @@
-"""-m gpu (and only where the REAL reference binary travelled along: oracle/_ref/seeksv_ref): the host junction stage (clip.gz x clip.bam join,
+"""-m gpu: the host junction stage (clip.gz x clip.bam join,
 GetAlignInfo, GetJunction, MergeJunction, OutputBreakpoint: SURVEY 8f #1) on randomized inputs, `seeksv getsv` of this repository against
 the reference's, byte for byte.  The inputs are made directly (no aligner): clip rows of planted junctions in all orientations whose clipped
 sequences re-align to the partner breakpoint (forward / reverse, with microhomology shifts, soft- and hard-clipped ends, MAPQ 0, secondary
 records, both-sided and one-sided support), duplicated and near-duplicate junctions that MergeJunction folds, and noise rows that re-align
-nowhere or anywhere; the BAM passes run on a committed background BAM."""
+nowhere or anywhere; the BAM passes run on a committed background BAM.  What the REAL reference wrote for these inputs is committed as the
+sha256 of every output in tests/golden/random/cli_vs_reference.json, made by tests/golden/make_random_reference.py with the reference binary."""
 import gzip
+import hashlib
+import json
 import os
 import subprocess
 
@@ -15,10 +18,28 @@ import bamio
 import golden_util as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "seeksv_ref")
 SEEKSV = os.environ.get("SSV_CLI") or os.path.join(ROOT, "seeksv_amd", "bin", "seeksv")
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(REF), reason="the real reference binary is not here")]
+pytestmark = pytest.mark.gpu
 COMP = str.maketrans("ACGT", "TGCA")
+GETSV_RUNS = (("default", []), ("loose", ["-f", "0", "-b", "0", "-d", "0"]), ("l90", ["-l", "90", "-e", "1"]))
+SOMATIC_RUNS = (("s", []), ("s_l60", ["-l", "60", "-m", "30"]), ("s_t", ["-t", "0.5", "-q", "0"]))
+GETCLIP_RUNS = (("a", []), ("b", ["-t", "0.8", "-q", "0", "-s"]))
+GZ_OUTPUTS = ("clip.gz", "clip.fq.gz", "unmapped_1.fq.gz", "unmapped_2.fq.gz")
+
+
+def sha(data):
+    return hashlib.sha256(data.encode() if isinstance(data, str) else data).hexdigest()
+
+
+def gz_sha(path):
+    with gzip.open(path) as f:
+        return sha(f.read())
+
+
+def reference_outputs():
+    """what the real reference wrote (tests/golden/random/cli_vs_reference.json)"""
+    with open(os.path.join(G.GOLDEN, "random", "cli_vs_reference.json")) as f:
+        return json.load(f)
 
 
 def rnd(rng, n):
@@ -121,27 +142,24 @@ def make_inputs(seed, d):
 
 @pytest.mark.parametrize("seed", range(8))
 def test_getsv_full_equals_reference_on_random_junction_inputs(tmp_path, seed):
+    ref = reference_outputs()["getsv"][str(seed)]
     d = str(tmp_path)
     bg, clip_bam, clip_gz = make_inputs(seed, d)
-    for tag, flags in (("default", []), ("loose", ["-f", "0", "-b", "0", "-d", "0"]), ("l90", ["-l", "90", "-e", "1"])):
-        ref = subprocess.run([REF, "getsv"] + flags + [clip_bam, bg, clip_gz, os.path.join(d, f"ref.{tag}.sv"), os.path.join(d, "r.fq")], capture_output=True, text=True)
-        assert ref.returncode == 0, ref.stderr[-400:]
+    for tag, flags in GETSV_RUNS:
         ours = subprocess.run([SEEKSV, "getsv"] + flags + [clip_bam, bg, clip_gz, os.path.join(d, f"ours.{tag}.sv"), os.path.join(d, "o.fq")], capture_output=True, text=True)
         assert ours.returncode == 0, ours.stderr[-400:]
-        want, got = open(os.path.join(d, f"ref.{tag}.sv")).read(), open(os.path.join(d, f"ours.{tag}.sv")).read()
-        assert got == want, (seed, tag)
-        assert ours.stdout == ref.stdout, (seed, tag)
+        got = open(os.path.join(d, f"ours.{tag}.sv")).read()
+        assert sha(got) == ref[tag]["sv"], (seed, tag)
+        assert sha(ours.stdout) == ref[tag]["stdout"], (seed, tag)
         if tag == "loose":
-            assert want.count("\n") > 30 and ref.stdout.count("\n") >= 0, want.count("\n")
-    # seeksv somatic with the loose table as the tumor's and the same clip clusters / BAM as the control: every look-up kind
-    # finds something, and a shifted copy of the clusters makes the range probes walk
-    table = os.path.join(d, "ref.loose.sv")
-    for tag, flags in (("s", []), ("s_l60", ["-l", "60", "-m", "30"]), ("s_t", ["-t", "0.5", "-q", "0"])):
-        ref = subprocess.run([REF, "somatic"] + flags + [bg, clip_gz, table, os.path.join(d, f"ref.{tag}.sv")], capture_output=True, text=True)
-        assert ref.returncode == 0, ref.stderr[-400:]
+            assert ref[tag]["sv_lines"] > 30, ref[tag]["sv_lines"]
+    # seeksv somatic with the loose table as the tumor's (ours: the same bytes as the reference's, checked above) and the same clip
+    # clusters / BAM as the control: every look-up kind finds something, and a shifted copy of the clusters makes the range probes walk
+    table = os.path.join(d, "ours.loose.sv")
+    for tag, flags in SOMATIC_RUNS:
         ours = subprocess.run([SEEKSV, "somatic"] + flags + [bg, clip_gz, table, os.path.join(d, f"ours.{tag}.sv")], capture_output=True, text=True)
         assert ours.returncode == 0, ours.stderr[-400:]
-        assert open(os.path.join(d, f"ours.{tag}.sv")).read() == open(os.path.join(d, f"ref.{tag}.sv")).read(), (seed, tag)
+        assert sha(open(os.path.join(d, f"ours.{tag}.sv")).read()) == ref[tag]["sv"], (seed, tag)
 
 
 @pytest.mark.parametrize("seed", range(200, 206))
@@ -149,57 +167,66 @@ def test_getsv_full_equals_reference_on_random_junction_inputs(tmp_path, seed):
 def test_cli_getclip_equals_reference_on_random_samples(tmp_path, seed, mode):
     """`seeksv getclip` file to file against the real reference on generated BAMs (the generator of tests/test_random_differential_gpu.py,
     restricted to inputs the reference defines): the four gzip outputs decompress to the same bytes, with the BAM decoded on the host or on the GPU"""
+    ref = reference_outputs()["getclip"][str(seed)]
+    bam = str(tmp_path / "s.bam")
+    getclip_sample(bam, seed)
+    for tag, flags in GETCLIP_RUNS:
+        o = subprocess.run([SEEKSV, "getclip"] + mode + flags + ["-o", str(tmp_path / ("our" + tag)), bam], capture_output=True, text=True)
+        assert o.returncode == 0, o.stderr[-300:]
+        for ext in GZ_OUTPUTS:
+            assert gz_sha(str(tmp_path / f"our{tag}.{ext}")) == ref[tag][ext], (seed, tag, ext)
+
+
+def getclip_sample(bam, seed):
     from test_random_differential_gpu import random_sample
     from test_random_oracle_vs_reference import write_sample
     names, lens, b, rng, recs = random_sample(seed, n=2500, safe=True, want_records=True)
-    bam = str(tmp_path / "s.bam")
-    write_sample(bam, names, lens, recs)
-    for tag, flags in (("a", []), ("b", ["-t", "0.8", "-q", "0", "-s"])):
-        r = subprocess.run([REF, "getclip"] + flags + ["-o", str(tmp_path / ("ref" + tag)), bam], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-300:]
-        o = subprocess.run([SEEKSV, "getclip"] + mode + flags + ["-o", str(tmp_path / ("our" + tag)), bam], capture_output=True, text=True)
-        assert o.returncode == 0, o.stderr[-300:]
-        for ext in ("clip.gz", "clip.fq.gz", "unmapped_1.fq.gz", "unmapped_2.fq.gz"):
-            assert gzip.open(str(tmp_path / f"our{tag}.{ext}")).read() == gzip.open(str(tmp_path / f"ref{tag}.{ext}")).read(), (seed, tag, ext)
+    write_sample(bam, names, lens, recs, index=False)
+
+
+def unmapped_pairs_sample(bam):
+    """the generator's pairs with one unmapped end, 3 % of the records -> the number of such records"""
+    from seeksv_amd import host, synth
+    w = synth.Workload(genome_frac=1 / 4096, depth=30, n_sv=12, unmap_permille=30)
+    b = w.generate_host(0, w.n_total, all_seq=True)
+    n_un = int(((b["flag"] & 12) != 0).sum())
+    assert 0.02 * w.n_total < n_un < 0.04 * w.n_total and n_un % 2 == 0
+    host.write_bam(bam, w.names, w.lens, [b])
+    return n_un
+
+
+def table_columns_sample(bam):
+    from seeksv_amd import host, synth
+    w = synth.Workload(genome_frac=1 / 128, depth=30, n_sv=80)
+    b = w.generate_host(0, w.n_total, all_seq=True)
+    host.write_bam(bam, w.names, w.lens, [b])
 
 
 @pytest.mark.parametrize("mode,env", [([], {}), (["-Z"], {}), (["-Z"], {"SSV_CHUNK_INFLATED_MB": "1"}), ([], {"SSV_HOST_BATCH_RECORDS": "997"})], ids=["host", "device", "device-small-chunks", "host-small-batches"])
 def test_cli_getclip_unmapped_pairs_of_the_synthetic_sample(tmp_path, mode, env):
     """The generator's pairs with one unmapped end (synth_core.h: unmap_permille, 3 % here) through `seeksv getclip`: the side channel (unmapped_pairs.h: a
     thread of its own over the readers' raw records) writes what the reference's std::map loop writes (clip_reads.h:172-219), mates a batch apart included."""
-    from seeksv_amd import host, synth
-    w = synth.Workload(genome_frac=1 / 4096, depth=30, n_sv=12, unmap_permille=30)
-    b = w.generate_host(0, w.n_total, all_seq=True)
-    n_un = int(((b["flag"] & 12) != 0).sum())
-    assert 0.02 * w.n_total < n_un < 0.04 * w.n_total and n_un % 2 == 0
+    ref = reference_outputs()["unmapped_pairs"]
     bam = str(tmp_path / "u.bam")
-    host.write_bam(bam, w.names, w.lens, [b])
-    r = subprocess.run([REF, "getclip", "-o", str(tmp_path / "ref"), bam], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-300:]
+    n_un = unmapped_pairs_sample(bam)
     o = subprocess.run([SEEKSV, "getclip"] + mode + ["-o", str(tmp_path / "our"), bam], capture_output=True, text=True, env=dict(os.environ, **env))
     assert o.returncode == 0, o.stderr[-300:]
-    for ext in ("clip.gz", "clip.fq.gz", "unmapped_1.fq.gz", "unmapped_2.fq.gz"):
-        want = gzip.open(str(tmp_path / f"ref.{ext}")).read()
-        assert gzip.open(str(tmp_path / f"our.{ext}")).read() == want, ext
+    for ext in GZ_OUTPUTS:
+        assert gz_sha(str(tmp_path / f"our.{ext}")) == ref[ext], ext
         if ext.startswith("unmapped"):
-            assert want.count(b"\n") == 4 * (n_un // 2)
+            assert ref[ext + ".lines"] == 4 * (n_un // 2)
 
 
 def test_cli_getclip_table_columns_both_ways(tmp_path):
     """The cluster table's columns - dense cluster index, CIGAR offset, string offset of every sorted slot - come out of scans over TILES of 256 slots
     (k_cluster_tile_sums / k_scan_sums_lists / k_cluster_cols3_tiles, table3_kernels.h), or the round-5 way out of two words per slot and two device-wide
     scans (SSV_PACK_COLS=split).  A sample with some hundred tiles: both write what the real reference writes."""
-    from seeksv_amd import host, synth
-    w = synth.Workload(genome_frac=1 / 128, depth=30, n_sv=80)
-    b = w.generate_host(0, w.n_total, all_seq=True)
+    ref = reference_outputs()["table_columns"]
     bam = str(tmp_path / "t.bam")
-    host.write_bam(bam, w.names, w.lens, [b])
-    r = subprocess.run([REF, "getclip", "-o", str(tmp_path / "ref"), bam], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-300:]
-    want = {ext: gzip.open(str(tmp_path / f"ref.{ext}")).read() for ext in ("clip.gz", "clip.fq.gz")}
-    assert want["clip.gz"].count(b"\n") > 64 * 256 * 2   # (rows = clusters: more than a hundred tiles)
+    table_columns_sample(bam)
+    assert ref["clip.gz.lines"] > 64 * 256 * 2   # (rows = clusters: more than a hundred tiles)
     for tag, env in (("tiles", {}), ("split", {"SSV_PACK_COLS": "split"})):
         o = subprocess.run([SEEKSV, "getclip", "-Z", "-o", str(tmp_path / tag), bam], capture_output=True, text=True, env=dict(os.environ, **env))
         assert o.returncode == 0, o.stderr[-300:]
-        for ext, data in want.items():
-            assert gzip.open(str(tmp_path / f"{tag}.{ext}")).read() == data, (tag, ext)
+        for ext in ("clip.gz", "clip.fq.gz"):
+            assert gz_sha(str(tmp_path / f"{tag}.{ext}")) == ref[ext], (tag, ext)

@@ -7,7 +7,7 @@
 #     inflate_kernel_stats.csv rocprofv3 --kernel-trace --stats of the real-reads run (per-kernel average durations)
 tag=${1:-bamdec}; o=gpurun_out/$tag; mkdir -p $o
 export TMPDIR=/tmp
-python3 bench.py > $o/bench_default.json 2> $o/bench.err
+python3 bench.py --full > $o/bench_default.json 2> $o/bench.err
 export SSV_PROFILE=1
 SSV_CHUNK_COMP_GB=2 python3 tools/bamdec_bench.py example 1200 2>&1 | tail -1 > $o/real_1200.json
 SSV_CHUNK_COMP_GB=3 python3 tools/bamdec_bench.py example 2000 2>&1 | tail -1 > $o/real_2000.json

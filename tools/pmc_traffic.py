@@ -4,7 +4,7 @@ into profiles/<tag>_pmc_fetch_write.csv (per kernel) and profiles/traffic.json (
 
 usage: python tools/pmc_traffic.py <fetch_dir> <write_dir> <records> <steps> [tag]
   each dir holds <something>_counter_collection.csv as written by
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <dir> -o x -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-overlap
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <dir> -o x -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-overlap
   (steps = the steps that run of bench.py executed: setup 4 - warmup, timed, breakdown = 4 + 1 + 3 = 8 with --warmup 0 --steps 1: the dispatch count of k_getsv_scan in the trace)
 FETCH_SIZE / WRITE_SIZE are reported in KB.  gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE shows exactly half the bytes of a
 wide coalesced streaming read (16 B/lane), so it is doubled for the two streaming scans, whose loads are all of that kind; other
@@ -89,7 +89,7 @@ def main():
     wk, _, _ = per_kernel(write)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", f"{tag}_pmc_fetch_write.csv"), "w") as o:
-        o.write(f"# rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-overlap` ({records:,} records, {steps} steps run)\n")
+        o.write(f"# rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-overlap` ({records:,} records, {steps} steps run)\n")
         o.write("# values in KB as reported, averaged over the kernel's dispatches. gfx950: FETCH_SIZE counts a 16-B/lane coalesced stream at HALF its bytes (MI355X_MICROARCH.md, HBM); other widths are uncalibrated\n")
         o.write("kernel,dispatches,FETCH_SIZE_KB_avg,WRITE_SIZE_KB_avg,avg_duration_us_in_pmc_run\n")
         for k in sorted(set(fk) | set(wk)):
