@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9: ssv_table_block_bytes(left_len, right_len) lost the parameters of the removed formats; ssv_bamdec_info.unmapped_raw stays valid for one more decode.
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
+                             v9: ssv_table_block_bytes(left_len, right_len) lost the parameters of the removed formats; ssv_bamdec_info.unmapped_raw stays valid for one more decode.
                              v8: table formats 1 and 2 (four-piece blocks with 4-bit bases) removed - 0 ASCII or 3 compact; ssv_group with SSV_GROUP_RCCL_ONE */
 
 typedef enum {
@@ -461,6 +462,10 @@ int ssv_bamdec_expect(ssv_ctx *ctx, uint64_t inflated_bytes);
  * more pass over bytes that are in HBM anyway) and refuse the chunk on a mismatch.  Off by default, like libbam 0.1.16's reader (sam/sam.h:73), which
  * checks no CRC: a block whose deflate structure is valid but whose bytes were damaged decodes silently there - and here, without this. */
 int ssv_bamdec_verify_crc(ssv_ctx *ctx, int on);
+/* Optional, after ssv_bamdec_begin: on != 0 accepts a file in any record order (getsv -F reads split alignments in read order): a chunk with more than
+ * 65536 contig changes among its mapped-pair records, which is otherwise refused as "not coordinate sorted", is decoded; its contig-change list is then
+ * not handed out (ssv_bamdec_info.n_tid_runs = 0).  Off by default. */
+int ssv_bamdec_any_order(ssv_ctx *ctx, int on);
 /* ... and that starts inside the file: the contig of the last mapped-pair record before it (0 at the start of the file, clip_reads.h:407) -
  * ssv_bamdec_info's contig-change list continues from there.  After ssv_bamdec_begin, before the first decode. */
 int ssv_bamdec_prev_tid(ssv_ctx *ctx, int32_t tid);
@@ -481,6 +486,19 @@ int ssv_bamdec_prefetch_drop(ssv_ctx *ctx);
  * is unfinished).  keep_all_seq as in ssvh_bam_read_batch.  Synchronises the stream. */
 int ssv_bamdec_decode(ssv_ctx *ctx, const void *comp, size_t comp_bytes, const ssv_bgzf_block *blocks, int64_t n_blocks, int keep_all_seq, ssv_batch_t *out);
 int ssv_bamdec_last(ssv_ctx *ctx, ssv_bamdec_info *info);
+
+/* The read names of a batch, beside ssv_batch_t (which has no field for them): record i's NUL-terminated name (at most 255 bytes with the NUL) starts at
+ * base + off[i] + bias.  mem as in ssv_batch_t (SSV_MEM_HOST: base[bytes] and off[n] are copied to the GPU; SSV_MEM_DEVICE: used in place, bytes unused). */
+typedef struct {
+	int32_t mem;
+	int32_t pad;
+	int64_t bias;
+	const char *base;
+	const uint64_t *off;
+	int64_t bytes;
+} ssv_names_t;
+/* The names of the last chunk ssv_bamdec_decode handed out, in HBM (valid as long as that batch). */
+int ssv_bamdec_names(ssv_ctx *ctx, ssv_names_t *out);
 /* Copy a device batch into host arrays owned by the context (valid until the next call): tests and debugging. */
 int ssv_batch_to_host(ssv_ctx *ctx, const ssv_batch_t *device_batch, ssv_batch_t *host_batch);
 
@@ -525,6 +543,41 @@ int ssv_realign_index(ssv_ctx *ctx, const uint64_t *ref2bit, int32_t mem, int64_
  * bases come back unaligned. */
 int ssv_realign_query(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits);
 int ssv_realign_free(ssv_ctx *ctx);
+
+/* ---- getsv -F: junctions from read-through split alignments: replaces FindJunction (process_bwasw.cpp:5-227, seeksv.cpp:221-225) -----------
+ * The file's records go through ssv_rt_scan batch by batch in file order (their bases are needed: keep_all_seq).  A record is kept unless
+ * mapq < min_mapq, it is unmapped or a duplicate, its first or last CIGAR operation is H, both are S or both are M (code 0), it has no CIGAR or its
+ * tid is not a contig.  Kept records are paired by read name in file order as the reference's std::map does; ssv_rt_finish returns one line per pair
+ * in the order of the record that completed it: the junction, its microhomology, the two seqs and the CIGAR sources of the two SeqInfo values.  The
+ * caller applies them to its junction map in that order (find: insert, or count against the found entry's seq lengths).  Calls out of sequence:
+ * SSV_E_STATE. */
+typedef struct {
+	int32_t min_mapq;          /* -w, default 1 */
+	int32_t n_targets;
+	const int32_t *name_rank;  /* [n_targets] host: the contig's place when the header's names are sorted byte-wise (make_pair(chr, pos) < compares names) */
+} ssv_rt_params;
+typedef struct {
+	int32_t up_tid, up_pos, down_tid, down_pos; /* the junction (1-based positions) */
+	int8_t up_strand, down_strand;              /* '+' / '-' */
+	int16_t kind;                               /* construction case, process_bwasw.cpp:94-197: 0/1 same strand (microhomology / none), 2/3 opposite, 5' sides, 4/5 opposite, 3' sides */
+	int32_t microhomology;
+	int32_t up_left_clipped, up_right_clipped, down_left_clipped, down_right_clipped;
+	int32_t up_len, down_len;                   /* the seqs: up at seqs + seq_off, down right behind it */
+	int32_t up_cig_n, down_cig_n;               /* the CIGAR sources (GenerateCigar: S and H dropped): up at cigars + cig_off, down behind it, BAM encoding */
+	int32_t up_cig_edit, down_cig_edit;         /* 0 as is, 1 MinusCigarRight(microhomology), 2 AddCigarLeft(microhomology) (clip_reads.cpp:507-558) */
+	uint64_t seq_off, cig_off;
+	int64_t first_record, second_record;        /* file-order indices of the held record and of the one that completed the pair */
+} ssv_rt_pair;
+typedef struct {
+	int64_t n_pairs;
+	int64_t n_candidates;                       /* kept records */
+	const ssv_rt_pair *pairs;                   /* host memory owned by the context, valid until the next ssv_rt_begin */
+	const char *seqs;
+	const uint32_t *cigars;
+} ssv_rt_result;
+int ssv_rt_begin(ssv_ctx *ctx, const ssv_rt_params *p);
+int ssv_rt_scan(ssv_ctx *ctx, const ssv_batch_t *b, const ssv_names_t *names);
+int ssv_rt_finish(ssv_ctx *ctx, ssv_rt_result *out);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,10 @@ const int32_t *ssvh_bam_target_lens(const ssvh_bam *b);
  * out->n == 0 at end of file.  keep_all_seq != 0 ships bases/qualities for every record.
  */
 int ssvh_bam_read_batch(ssvh_bam *b, int64_t max_records, int keep_all_seq, ssv_batch_t *out);
+/* Keep the read names of the records of every following batch (off by default); ssvh_bam_batch_names hands out those of the batch
+ * ssvh_bam_read_batch returned last (host memory, valid as long as that batch).  getsv -F pairs its records by name (ssv_rt_scan). */
+int ssvh_bam_keep_names(ssvh_bam *b, int on);
+int ssvh_bam_batch_names(const ssvh_bam *b, ssv_names_t *out);
 
 /*
  * Range-partitioned reading (the reference reaches a region through the .bai: seeksv.cpp:272-280 bam_index_load,

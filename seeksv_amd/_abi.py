@@ -156,6 +156,28 @@ class JunctionIn(C.Structure):
                 ("up_strand", C.c_char), ("down_strand", C.c_char)]
 
 
+class Names(C.Structure):
+    """ssv_names_t: record i's NUL-terminated read name at base + off[i] + bias"""
+    _fields_ = [("mem", C.c_int32), ("pad", C.c_int32), ("bias", C.c_int64), ("base", C.c_void_p), ("off", C.c_void_p), ("bytes", C.c_int64)]
+
+
+class RtParams(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("n_targets", C.c_int32), ("name_rank", C.POINTER(C.c_int32))]
+
+
+class RtPair(C.Structure):
+    _fields_ = [("up_tid", C.c_int32), ("up_pos", C.c_int32), ("down_tid", C.c_int32), ("down_pos", C.c_int32),
+                ("up_strand", C.c_int8), ("down_strand", C.c_int8), ("kind", C.c_int16), ("microhomology", C.c_int32),
+                ("up_left_clipped", C.c_int32), ("up_right_clipped", C.c_int32), ("down_left_clipped", C.c_int32), ("down_right_clipped", C.c_int32),
+                ("up_len", C.c_int32), ("down_len", C.c_int32), ("up_cig_n", C.c_int32), ("down_cig_n", C.c_int32),
+                ("up_cig_edit", C.c_int32), ("down_cig_edit", C.c_int32), ("seq_off", C.c_uint64), ("cig_off", C.c_uint64),
+                ("first_record", C.c_int64), ("second_record", C.c_int64)]
+
+
+class RtResult(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_candidates", C.c_int64), ("pairs", C.POINTER(RtPair)), ("seqs", C.c_void_p), ("cigars", C.POINTER(C.c_uint32))]
+
+
 def make_batch(arrays, mem=MEM_HOST, n=None):
     """Build an ssv_batch_t over numpy arrays (host) or raw device pointers (ints). Returns (Batch, keepalive)."""
     b = Batch()
@@ -342,5 +364,10 @@ def hip_lib():
         lib.ssv_prof_reset.argtypes = [V]
         lib.ssv_prof_get.argtypes = [V, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.ssv_prof_names.restype = C.c_char_p
+        lib.ssv_bamdec_names.argtypes = [V, C.POINTER(Names)]
+        lib.ssv_bamdec_any_order.argtypes = [V, C.c_int]
+        lib.ssv_rt_begin.argtypes = [V, C.POINTER(RtParams)]
+        lib.ssv_rt_scan.argtypes = [V, C.POINTER(Batch), C.POINTER(Names)]
+        lib.ssv_rt_finish.argtypes = [V, C.POINTER(RtResult)]
         lib._typed = True
     return lib

@@ -10,6 +10,7 @@ struct ssv_bamdec_state {
 	std::vector<uint64_t> htokoff;
 	uint64_t limit = UINT64_MAX; // ssv_bamdec_limit: where the next chunk's records end (inflated bytes into its blocks)
 	bool verify_crc = false;      // ssv_bamdec_verify_crc
+	bool any_order = false;       // ssv_bamdec_any_order: chunks with more contig changes than the list holds go through without the list
 	DBuf crc_tab;
 	uint64_t expect_inflated = 0; // ssv_bamdec_expect: the largest chunk that will come (buffers are sized for it by the first, smaller one)
 	DBuf inf_scratch, inf_dbg, tokens, tok_off, n_tok, carrybuf, comp, blocks, u_off, stream, status, chain, count, base, rec_off, stitch, tile_last, tile_prev, runs, small;
@@ -65,6 +66,7 @@ int ssv_bamdec_begin(ssv_ctx *c, int32_t n_targets, uint64_t first_record_offset
 	if (!c->bd) c->bd = new ssv_bamdec_state();
 	c->bd->have_tlen = false;
 	c->bd->n_targets = n_targets; c->bd->start = first_record_offset; c->bd->prev_tid = 0; c->bd->carry = 0; c->bd->limit = UINT64_MAX; c->bd->expect_inflated = 0; c->bd->verify_crc = false;
+	c->bd->any_order = false;
 	for (auto &sl : c->bd->slot) sl.host = nullptr; // (a copy still on its way lands in a slot nobody asks for)
 	memset(&c->bd->info, 0, sizeof(c->bd->info));
 	return SSV_OK;
@@ -90,6 +92,15 @@ int ssv_bamdec_expect(ssv_ctx *c, uint64_t inflated_bytes)
 {
 	if (!c || !c->bd) return SSV_E_ARG;
 	c->bd->expect_inflated = inflated_bytes;
+	return SSV_OK;
+}
+
+// Optional, after ssv_bamdec_begin: a file in any record order (getsv -F: split alignments in read order).  A chunk with more than 65536 contig
+// changes among its mapped-pair records is then decoded like any other; only its contig-change list (ssv_bamdec_info.n_tid_runs) is not handed out.
+int ssv_bamdec_any_order(ssv_ctx *c, int on)
+{
+	if (!c || !c->bd) return SSV_E_ARG;
+	c->bd->any_order = on != 0;
 	return SSV_OK;
 }
 
@@ -410,8 +421,11 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
 	const uint32_t *hs = P<uint32_t>(d.h_small);
-	const uint32_t n_runs = hs[2];
-	if (n_runs > run_cap) { c->err = "more than 65536 contig changes in one chunk: the BAM is not coordinate sorted"; return SSV_E_ARG; }
+	uint32_t n_runs = hs[2];
+	if (n_runs > run_cap) {
+		if (!d.any_order) { c->err = "more than 65536 contig changes in one chunk: the BAM is not coordinate sorted"; return SSV_E_ARG; }
+		n_runs = 0; // (ssv_bamdec_any_order: the list is incomplete - not handed out; the kernel wrote no more than run_cap entries)
+	}
 	d.prev_tid = (int32_t)hs[3];
 	// the small host-side lists
 	CHECK(ensure_host(c, d.h_runs, (size_t)n_runs * sizeof(ssv::TidRun) + 64 + (size_t)n_runs * 8));
@@ -445,6 +459,17 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 			out->tid_runs = d.tid_runs.data(); out->n_tid_runs = (int64_t)nr;
 		}
 	}
+	return SSV_OK;
+}
+
+// the names of the last decoded chunk's records: in the inflated stream, behind each record's block_size and 32-byte core
+int ssv_bamdec_names(ssv_ctx *c, ssv_names_t *out)
+{
+	if (!c || !out) return SSV_E_ARG;
+	if (!c->bd) { c->err = "ssv_bamdec_names before ssv_bamdec_begin"; return SSV_E_STATE; }
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_DEVICE; out->bias = 36;
+	out->base = P<char>(c->bd->stream); out->off = P<uint64_t>(c->bd->rec_off);
 	return SSV_OK;
 }
 

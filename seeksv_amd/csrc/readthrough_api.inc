@@ -1,0 +1,215 @@
+// readthrough_api.inc - C ABI of `getsv -F` (FindJunction, process_bwasw.cpp:5-227); included by seeksv_hip.hip, kernels in readthrough_kernels.h
+
+static_assert(sizeof(ssv::RtPairOut) == sizeof(ssv_rt_pair), "RtPairOut is the ABI line");
+
+struct ssv_rt_state {
+	enum { IDLE, SCANNING, FINISHED } phase = IDLE;
+	int32_t min_mapq = 1, n_targets = 0;
+	uint64_t hash_mask = ~0ull;
+	int hash_bits = 64;
+	uint64_t rec_base = 0;                 // records scanned so far (file order)
+	int64_t n_cand = 0;                    // candidates gathered so far
+	uint64_t name_used = 0, seq_used = 0, cig_used = 0;
+	DBuf rank, keep, at, cand, nbytes, sbytes, cops, small, hnames, hoff;
+	DBuf cands, hash, names, seqs, cigs;   // the store: grows like the other arenas, contents kept
+	DBuf keys[2], vals[2], held, partner, ev_flag, ev_at, ev_b, pairs, slices, cig_src, pseq, pcig, seq_out, cig_out;
+	HBuf h_small, h_pairs, h_seqs, h_cigs;
+};
+
+static void rt_free(ssv_ctx *c)
+{
+	if (!c->rt) return;
+	ssv_rt_state &R = *c->rt;
+	DBuf *d[] = {&R.rank, &R.keep, &R.at, &R.cand, &R.nbytes, &R.sbytes, &R.cops, &R.small, &R.hnames, &R.hoff, &R.cands, &R.hash, &R.names, &R.seqs, &R.cigs,
+	             &R.keys[0], &R.keys[1], &R.vals[0], &R.vals[1], &R.held, &R.partner, &R.ev_flag, &R.ev_at, &R.ev_b, &R.pairs, &R.slices, &R.cig_src, &R.pseq, &R.pcig,
+	             &R.seq_out, &R.cig_out};
+	for (DBuf *b : d) if (b->p) (void)hipFree(b->p);
+	HBuf *h[] = {&R.h_small, &R.h_pairs, &R.h_seqs, &R.h_cigs};
+	for (HBuf *b : h) if (b->p) (void)pinned_delete(b->p);
+	delete c->rt;
+	c->rt = nullptr;
+}
+
+int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p)
+{
+	if (!c) return SSV_E_ARG;
+	if (!p || p->n_targets < 0 || (p->n_targets > 0 && !p->name_rank)) { c->err = "ssv_rt_begin: bad parameters"; return SSV_E_ARG; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	if (!c->rt) c->rt = new ssv_rt_state();
+	ssv_rt_state &R = *c->rt;
+	R.phase = ssv_rt_state::IDLE;
+	R.min_mapq = p->min_mapq; R.n_targets = p->n_targets;
+	// SSV_RT_HASH_BITS (tests): the name hash cut to its low bits, so that names collide and the exact path runs
+	const char *e = getenv("SSV_RT_HASH_BITS");
+	R.hash_bits = e ? std::max(1, std::min(64, atoi(e))) : 64;
+	R.hash_mask = R.hash_bits == 64 ? ~0ull : ((1ull << R.hash_bits) - 1);
+	R.rec_base = 0; R.n_cand = 0; R.name_used = R.seq_used = R.cig_used = 0;
+	CHECK(ensure(c, R.rank, (size_t)p->n_targets * 4 + 16));
+	if (p->n_targets) HIPCHECK(c, hipMemcpyAsync(R.rank.p, p->name_rank, (size_t)p->n_targets * 4, hipMemcpyHostToDevice, c->st));
+	CHECK(ensure(c, R.small, 256)); CHECK(ensure_host(c, R.h_small, 256));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	R.phase = ssv_rt_state::SCANNING;
+	return SSV_OK;
+}
+
+int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->rt || c->rt->phase != ssv_rt_state::SCANNING) { c->err = "ssv_rt_scan before ssv_rt_begin"; return SSV_E_STATE; }
+	if (!b || !nm || (b->n > 0 && (!nm->base || !nm->off)) || (nm->mem != SSV_MEM_HOST && nm->mem != SSV_MEM_DEVICE) || nm->bias < 0) { c->err = "ssv_rt_scan: bad arguments"; return SSV_E_ARG; }
+	ssv_rt_state &R = *c->rt;
+	HIPCHECK(c, hipSetDevice(c->device));
+	DevBatch d;
+	CHECK(stage_batch(c, b, d));
+	const int64_t n = d.n;
+	if (n == 0) return SSV_OK;
+	ProfScope ps(c, P_RT_SCAN, n);
+	if (!d.ends) {
+		CHECK(ensure(c, c->ends_buf, (size_t)n + 16));
+		k_build_ends<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
+		HIPCHECK(c, hipGetLastError());
+		d.ends = P<uint8_t>(c->ends_buf);
+	}
+	RtNames names;
+	if (nm->mem == SSV_MEM_DEVICE) names = RtNames{nm->base, nm->off, nm->bias};
+	else {
+		CHECK(ensure(c, R.hnames, (size_t)nm->bytes + 16)); CHECK(ensure(c, R.hoff, (size_t)n * 8 + 16));
+		if (nm->bytes) HIPCHECK(c, hipMemcpyAsync(R.hnames.p, nm->base, (size_t)nm->bytes, hipMemcpyHostToDevice, c->st));
+		HIPCHECK(c, hipMemsetAsync(P<char>(R.hnames) + nm->bytes, 0, 16, c->st)); // (a name without its NUL ends here)
+		HIPCHECK(c, hipMemcpyAsync(R.hoff.p, nm->off, (size_t)n * 8, hipMemcpyHostToDevice, c->st));
+		names = RtNames{P<char>(R.hnames), P<uint64_t>(R.hoff), nm->bias};
+	}
+	// ---- select: the ends column (and behind a passing pair the flag / mapq of the line) -> ordered compaction ----
+	CHECK(ensure(c, R.keep, (size_t)n * 4 + 16)); CHECK(ensure(c, R.at, (size_t)n * 4 + 16)); CHECK(ensure(c, R.cand, (size_t)n * 4 + 16));
+	CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(n) * 4)); CHECK(ensure(c, c->scan_scratch64, scan_scratch_elems(n) * 8));
+	uint32_t *sm = P<uint32_t>(R.small);
+	HIPCHECK(c, hipMemsetAsync(R.small.p, 0, 256, c->st));
+	k_rt_select<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, R.min_mapq, R.n_targets, P<uint32_t>(R.keep));
+	exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(R.keep), P<uint32_t>(R.at), n, 0u, P<uint32_t>(c->scan_scratch), sm);
+	k_rt_place<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.keep), P<uint32_t>(R.at), n, P<uint32_t>(R.cand));
+	HIPCHECK(c, hipGetLastError());
+	HIPCHECK(c, hipMemcpyAsync(R.h_small.p, R.small.p, 16, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	const int64_t m = P<uint32_t>(R.h_small)[0];
+	if (m > 0) {
+		if (R.n_cand + m >= (int64_t)0xffffffffll) { c->err = "more than 2^32 read-through candidates"; return SSV_E_RANGE; }
+		// ---- gather: sizes -> offsets in the store (carried over the batches) -> copies ----
+		const size_t M1 = (size_t)m + 1;
+		CHECK(ensure(c, R.nbytes, M1 * 8)); CHECK(ensure(c, R.sbytes, M1 * 8)); CHECK(ensure(c, R.cops, M1 * 8));
+		CHECK(ensure(c, R.hash, (size_t)(R.n_cand + m) * 8 + 16, true, (size_t)R.n_cand * 8));
+		CHECK(ensure(c, R.cands, (size_t)(R.n_cand + m) * sizeof(RtCand) + 64, true, (size_t)R.n_cand * sizeof(RtCand)));
+		k_rt_measure<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.hash_mask, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                      P<uint64_t>(R.hash) + R.n_cand, sm + 8);
+		HIPCHECK(c, hipGetLastError());
+		exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.nbytes), P<uint64_t>(R.nbytes), m, (uint64_t)R.name_used, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.nbytes) + m);
+		exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.sbytes), P<uint64_t>(R.sbytes), m, (uint64_t)R.seq_used, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.sbytes) + m);
+		exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.cops), P<uint64_t>(R.cops), m, (uint64_t)R.cig_used, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.cops) + m);
+		HIPCHECK(c, hipMemcpyAsync(P<uint64_t>(R.h_small) + 4, P<uint64_t>(R.nbytes) + m, 8, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipMemcpyAsync(P<uint64_t>(R.h_small) + 5, P<uint64_t>(R.sbytes) + m, 8, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipMemcpyAsync(P<uint64_t>(R.h_small) + 6, P<uint64_t>(R.cops) + m, 8, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(R.h_small) + 16, sm + 8, 4, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+		if (P<uint32_t>(R.h_small)[16]) { c->err = "ssv_rt_scan: a kept record comes without its bases (read the file with keep_all_seq)"; return SSV_E_ARG; }
+		const uint64_t name_end = P<uint64_t>(R.h_small)[4], seq_end = P<uint64_t>(R.h_small)[5], cig_end = P<uint64_t>(R.h_small)[6];
+		CHECK(ensure(c, R.names, name_end + 16, true, R.name_used));
+		CHECK(ensure(c, R.seqs, seq_end + 16, true, R.seq_used));
+		CHECK(ensure(c, R.cigs, cig_end * 4 + 16, true, R.cig_used * 4));
+		k_rt_gather<<<grid_for(m, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.rec_base, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                               P<RtCand>(R.cands) + R.n_cand, P<char>(R.names), P<uint8_t>(R.seqs), P<uint32_t>(R.cigs));
+		HIPCHECK(c, hipGetLastError());
+		R.n_cand += m; R.name_used = name_end; R.seq_used = seq_end; R.cig_used = cig_end;
+	}
+	R.rec_base += (uint64_t)n;
+	HIPCHECK(c, hipStreamSynchronize(c->st)); // the caller may reuse the batch (and its names) once this returns
+	return SSV_OK;
+}
+
+// The candidate store and the finish temporaries hold every kept record's line, name, bases and CIGAR (GBs for a large -F file): handed back once the
+// results are in host memory - the passes that follow on the same context (insert sizes, discordant pairs, depth) get that memory.
+static void rt_release_store(ssv_ctx *c)
+{
+	ssv_rt_state &R = *c->rt;
+	(void)hipStreamSynchronize(c->st);
+	DBuf *d[] = {&R.keep, &R.at, &R.cand, &R.nbytes, &R.sbytes, &R.cops, &R.hnames, &R.hoff, &R.cands, &R.hash, &R.names, &R.seqs, &R.cigs,
+	             &R.keys[0], &R.keys[1], &R.vals[0], &R.vals[1], &R.held, &R.partner, &R.ev_flag, &R.ev_at, &R.ev_b, &R.pairs, &R.slices, &R.cig_src, &R.pseq, &R.pcig,
+	             &R.seq_out, &R.cig_out};
+	for (DBuf *b : d) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+	R.n_cand = 0; R.name_used = R.seq_used = R.cig_used = 0;
+}
+
+static int rt_finish(ssv_ctx *c, ssv_rt_result *out);
+
+int ssv_rt_finish(ssv_ctx *c, ssv_rt_result *out)
+{
+	const int rc = rt_finish(c, out);
+	if (c && c->rt && c->rt->phase == ssv_rt_state::FINISHED) rt_release_store(c);
+	return rc;
+}
+
+static int rt_finish(ssv_ctx *c, ssv_rt_result *out)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->rt || c->rt->phase != ssv_rt_state::SCANNING) { c->err = "ssv_rt_finish before ssv_rt_begin"; return SSV_E_STATE; }
+	if (!out) { c->err = "ssv_rt_finish: no result"; return SSV_E_ARG; }
+	ssv_rt_state &R = *c->rt;
+	HIPCHECK(c, hipSetDevice(c->device));
+	memset(out, 0, sizeof(*out));
+	const int64_t n = R.n_cand;
+	out->n_candidates = n;
+	R.phase = ssv_rt_state::FINISHED;
+	if (n == 0) return SSV_OK;
+	ProfScope ps(c, P_RT_FINISH, n);
+	// ---- pair: stable sort of (hash, candidate) - candidates are in file order - then one lane per run of equal hashes ----
+	const size_t N = (size_t)n;
+	CHECK(ensure(c, R.keys[0], N * 8 + 16)); CHECK(ensure(c, R.keys[1], N * 8 + 16)); CHECK(ensure(c, R.vals[0], N * 4 + 16)); CHECK(ensure(c, R.vals[1], N * 4 + 16));
+	const int64_t nt = rs_tiles(n);
+	CHECK(ensure(c, c->ghist, (size_t)256 * nt * 4)); CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(256 * nt) * 4));
+	HIPCHECK(c, hipMemcpyAsync(R.keys[0].p, R.hash.p, N * 8, hipMemcpyDeviceToDevice, c->st));
+	k_iota<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.vals[0]), n);
+	uint64_t *kp[2] = {P<uint64_t>(R.keys[0]), P<uint64_t>(R.keys[1])};
+	uint32_t *vp[2] = {P<uint32_t>(R.vals[0]), P<uint32_t>(R.vals[1])};
+	const int cur = radix_sort_pairs(c->st, kp, vp, n, (R.hash_bits + 7) / 8 * 8, P<uint32_t>(c->ghist), P<uint32_t>(c->scan_scratch));
+	CHECK(ensure(c, R.held, N * 4 + 16)); CHECK(ensure(c, R.partner, N * 4 + 16));
+	HIPCHECK(c, hipMemsetAsync(R.partner.p, 0xff, N * 4, c->st));
+	k_rt_pair<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(kp[cur], vp[cur], n, P<RtCand>(R.cands), P<char>(R.names), P<int32_t>(R.held), P<int32_t>(R.partner));
+	HIPCHECK(c, hipGetLastError());
+	// ---- pair events in the order of their completing record ----
+	CHECK(ensure(c, R.ev_flag, N * 4 + 16)); CHECK(ensure(c, R.ev_at, N * 4 + 16)); CHECK(ensure(c, R.ev_b, N * 4 + 16));
+	CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(n) * 4)); CHECK(ensure(c, c->scan_scratch64, scan_scratch_elems(n) * 8));
+	uint32_t *sm = P<uint32_t>(R.small);
+	HIPCHECK(c, hipMemsetAsync(R.small.p, 0, 256, c->st));
+	k_rt_flag_pairs<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<int32_t>(R.partner), n, P<uint32_t>(R.ev_flag));
+	exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(R.ev_flag), P<uint32_t>(R.ev_at), n, 0u, P<uint32_t>(c->scan_scratch), sm);
+	k_rt_place<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.ev_flag), P<uint32_t>(R.ev_at), n, P<uint32_t>(R.ev_b));
+	HIPCHECK(c, hipGetLastError());
+	HIPCHECK(c, hipMemcpyAsync(R.h_small.p, R.small.p, 16, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	const int64_t m = P<uint32_t>(R.h_small)[0];
+	out->n_pairs = m;
+	if (m == 0) return SSV_OK;
+	// ---- per event: key, microhomology, seqs as slices; then the seqs in ASCII and the CIGAR sources ----
+	const size_t M = (size_t)m, M1 = M + 1;
+	CHECK(ensure(c, R.pairs, M * sizeof(RtPairOut) + 64)); CHECK(ensure(c, R.slices, M * 2 * sizeof(RtSlice) + 64)); CHECK(ensure(c, R.cig_src, M * 8 + 16));
+	CHECK(ensure(c, R.pseq, M1 * 8)); CHECK(ensure(c, R.pcig, M1 * 8));
+	k_rt_keys<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.ev_b), P<int32_t>(R.partner), m, P<RtCand>(R.cands), P<int32_t>(R.rank), P<RtPairOut>(R.pairs),
+	                                                   P<RtSlice>(R.slices), P<uint32_t>(R.cig_src), P<uint64_t>(R.pseq), P<uint64_t>(R.pcig));
+	HIPCHECK(c, hipGetLastError());
+	exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.pseq), P<uint64_t>(R.pseq), m, 0ull, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.pseq) + m);
+	exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.pcig), P<uint64_t>(R.pcig), m, 0ull, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.pcig) + m);
+	HIPCHECK(c, hipMemcpyAsync(P<uint64_t>(R.h_small) + 4, P<uint64_t>(R.pseq) + m, 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipMemcpyAsync(P<uint64_t>(R.h_small) + 5, P<uint64_t>(R.pcig) + m, 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	const uint64_t seq_total = P<uint64_t>(R.h_small)[4], cig_total = P<uint64_t>(R.h_small)[5];
+	CHECK(ensure(c, R.seq_out, seq_total + 16)); CHECK(ensure(c, R.cig_out, cig_total * 4 + 16));
+	k_rt_emit<<<grid_for(m, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(m, P<RtCand>(R.cands), P<uint8_t>(R.seqs), P<uint32_t>(R.cigs), P<RtSlice>(R.slices), P<uint32_t>(R.cig_src),
+	                                                             P<uint64_t>(R.pseq), P<uint64_t>(R.pcig), P<RtPairOut>(R.pairs), P<char>(R.seq_out), P<uint32_t>(R.cig_out));
+	HIPCHECK(c, hipGetLastError());
+	CHECK(ensure_host(c, R.h_pairs, M * sizeof(RtPairOut) + 64)); CHECK(ensure_host(c, R.h_seqs, seq_total + 16)); CHECK(ensure_host(c, R.h_cigs, cig_total * 4 + 16));
+	HIPCHECK(c, hipMemcpyAsync(R.h_pairs.p, R.pairs.p, M * sizeof(RtPairOut), hipMemcpyDeviceToHost, c->st));
+	if (seq_total) HIPCHECK(c, hipMemcpyAsync(R.h_seqs.p, R.seq_out.p, seq_total, hipMemcpyDeviceToHost, c->st));
+	if (cig_total) HIPCHECK(c, hipMemcpyAsync(R.h_cigs.p, R.cig_out.p, cig_total * 4, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	prof_collect(c);
+	out->pairs = P<ssv_rt_pair>(R.h_pairs); out->seqs = P<char>(R.h_seqs); out->cigars = P<uint32_t>(R.h_cigs);
+	return SSV_OK;
+}

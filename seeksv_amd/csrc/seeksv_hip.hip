@@ -34,6 +34,7 @@
 #include "cpus.h"
 #include "getsv_kernels.h"
 #include "radix_sort.h"
+#include "readthrough_kernels.h"
 #include "scan.h"
 
 using namespace ssv;
@@ -43,9 +44,9 @@ namespace {
 thread_local std::string g_create_error; // (per thread: ssv_last_error(NULL) is asked by the thread whose call failed; rank and reader threads run side by side)
 
 // timed kernel groups (ssv_prof_*)
-enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_COUNT };
-const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve"};
-const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve";
+enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_RT_SCAN, P_RT_FINISH, P_COUNT };
+const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve", "rt_scan", "rt_finish"};
+const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve\nrt_scan\nrt_finish";
 
 struct DBuf { // grow-only device buffer
 	void *p = nullptr;
@@ -258,6 +259,8 @@ struct ssv_ctx {
 	struct ssv_bamdec_state *bd = nullptr;
 	// ---- clipped-sequence re-aligner (realign_api.inc) ----
 	struct ssv_realign_state *ra = nullptr;
+	// ---- getsv -F read-through pass (readthrough_api.inc) ----
+	struct ssv_rt_state *rt = nullptr;
 	HBuf h_batch;
 
 	// ---- profiling ----
@@ -822,6 +825,7 @@ int ssv_ctx_create(int device, ssv_ctx **out)
 
 static void bamdec_free(ssv_ctx *c); // bamdec_api.inc
 static void realign_free(ssv_ctx *c); // realign_api.inc
+static void rt_free(ssv_ctx *c);      // readthrough_api.inc
 
 void ssv_ctx_destroy(ssv_ctx *c)
 {
@@ -832,6 +836,7 @@ void ssv_ctx_destroy(ssv_ctx *c)
 	for (auto &t : c->tab) if (t.in_flight && t.via_link) { table_link_wait(c, t); t.in_flight = false; } // (a table still on its way out: its buffers go below)
 	bamdec_free(c);
 	realign_free(c);
+	rt_free(c);
 	if (c->h_batch.p) (void)pinned_delete(c->h_batch.p);
 	if (c->h_qual_lut.p) (void)pinned_delete(c->h_qual_lut.p);
 	if (c->h_pair_lut.p) (void)pinned_delete(c->h_pair_lut.p);
@@ -2156,6 +2161,7 @@ const char *ssv_prof_names(void) { return kProfNameList; }
 
 #include "bamdec_api.inc"
 #include "realign_api.inc"
+#include "readthrough_api.inc"
 #include "group_api.inc"
 
 } // extern "C"

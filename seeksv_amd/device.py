@@ -65,6 +65,41 @@ class Context:
             return b, None
         return _abi.make_batch(b)
 
+    # ---- getsv -F: junctions from read-through split alignments (ssv_rt_*) ----
+    def readthrough(self, batches, names, min_mapq=1, target_names=(), raw=False):
+        """FindJunction (process_bwasw.cpp:5-227) over host batches in file order.  batches: dicts of arrays (or _abi.Batch) that carry every kept
+        record's bases; names[k]: the read names of batch k (str).  Returns one dict per pair, in the order of the record that completed it:
+        the junction (contig names when target_names is given, else tids), microhomology, kind, the two seqs and CIGAR sources with their edits."""
+        nt = len(target_names)
+        order = sorted(range(nt), key=lambda t: target_names[t].encode())
+        rank = np.zeros(max(nt, 1), dtype=np.int32)
+        for k, t in enumerate(order):
+            rank[t] = k
+        p = _abi.RtParams(int(min_mapq), nt, rank.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(self._lib.ssv_rt_begin(self._h, C.byref(p)), "ssv_rt_begin")
+        for b, nm in zip(batches, names):
+            bb, keep = self._as_batch(b)
+            blob = b"".join(x.encode() + b"\0" for x in nm)
+            off = np.zeros(len(nm) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x.encode()) + 1 for x in nm])
+            buf = C.create_string_buffer(blob, len(blob) + 1)
+            n = _abi.Names(_abi.MEM_HOST, 0, 0, C.cast(buf, C.c_void_p), off.ctypes.data, len(blob))
+            self._check(self._lib.ssv_rt_scan(self._h, C.byref(bb), C.byref(n)), "ssv_rt_scan")
+        r = _abi.RtResult()
+        self._check(self._lib.ssv_rt_finish(self._h, C.byref(r)), "ssv_rt_finish")
+        out = []
+        for k in range(r.n_pairs):
+            q = r.pairs[k]
+            seqs = C.string_at(r.seqs + q.seq_off, q.up_len + q.down_len).decode() if q.up_len + q.down_len else ""
+            ops = [r.cigars[q.cig_off + j] for j in range(q.up_cig_n + q.down_cig_n)]
+            ctg = (lambda t: target_names[t]) if nt else (lambda t: t)
+            out.append(dict(key=(ctg(q.up_tid), q.up_pos, chr(q.up_strand), ctg(q.down_tid), q.down_pos, chr(q.down_strand)),
+                            microhomology=q.microhomology, kind=q.kind, up_seq=seqs[:q.up_len], down_seq=seqs[q.up_len:],
+                            clipped=(q.up_left_clipped, q.up_right_clipped, q.down_left_clipped, q.down_right_clipped),
+                            up_cigar=ops[:q.up_cig_n], down_cigar=ops[q.up_cig_n:], edits=(q.up_cig_edit, q.down_cig_edit),
+                            records=(q.first_record, q.second_record)))
+        return (out, r.n_candidates) if raw else out
+
     # ---- device-side BGZF inflate + BAM decode ----
     def bamdec_target_lens(self, lens):
         """after ssv_bamdec_begin: the contig lengths sharpen the speculation of record starts (results do not depend on it)"""

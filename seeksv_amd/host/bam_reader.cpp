@@ -424,11 +424,14 @@ struct ssvh_bam {
 		std::vector<uint8_t> unmapped_raw;  // the UNMAP|MUNMAP records as they lie in the stream (block_size prefixed), in order
 		std::vector<size_t> unmapped_off;   // where each starts
 		std::vector<ssv_tid_run> tid_runs; // the tid column as runs (ssv_batch_t.tid_runs)
+		std::vector<char> names;           // ssvh_bam_keep_names: the records' read names, NUL-terminated, at name_off[i]
+		std::vector<uint64_t> name_off;
 		void use(const HostAlloc *a) { tid.a = pos.a = l_qseq.a = mtid.a = mpos.a = isize.a = a; flag.a = n_cigar.a = a; mapq.a = xc.a = seqqual.a = ends.a = a; cigar_off.a = cigar.a = a; seq_off.a = a; }
 	} buf[3];
 	HostAlloc alloc;
 	int cur = 0;
 	bool readahead = false;
+	bool keep_names = false;
 	std::thread ra_thread;
 	int ra_rc = 0; std::string ra_err; ssv_batch_t ra_batch; int64_t ra_max = 0; int ra_keep = 0;
 	long raw_end_coff = -1;      // raw mode over a range (ssvh_bam_raw_begin_range)
@@ -971,6 +974,22 @@ static int decode_batch(ssvh_bam *b, ssvh_bam::BatchBuf &B, int64_t max_records,
 		max_span = std::max(max_span, span_of[(size_t)t]);
 		B.unmapped_raw.insert(B.unmapped_raw.end(), un[(size_t)t].begin(), un[(size_t)t].end());
 	}
+	if (b->keep_names) { // (before the window is handed back: the names are copied out of the inflated records)
+		B.name_off.resize((size_t)n + 1);
+		uint64_t tot = 0;
+		for (int64_t i = 0; i < n; ++i) { B.name_off[(size_t)i] = tot; tot += base[off[(size_t)i] + 4 + 8]; }
+		B.name_off[(size_t)n] = tot;
+		B.names.resize((size_t)tot + 1);
+		pool().run(nt, [&](int t) {
+			for (int64_t i = n * t / nt, i1 = n * (t + 1) / nt; i < i1; ++i) {
+				const uint8_t *r = base + off[(size_t)i] + 4;
+				const size_t ln = r[8];
+				char *dst = B.names.data() + B.name_off[(size_t)i];
+				memcpy(dst, r + 32, ln);
+				if (ln) dst[ln - 1] = 0; // (l_read_name counts the NUL)
+			}
+		});
+	}
 	if (timing) fprintf(stderr, "[read_batch] n=%lld inflate+find %.3f s, sizes %.3f s, decode %.3f s, window %zu MB\n", (long long)n, t1 - t0, t2 - t1, now() - t2, z.ulen >> 20);
 	// the batch's raw bytes are consumed; records already located behind them stay queued for the next call
 	b->found_pos = (size_t)n;
@@ -1016,6 +1035,25 @@ int ssvh_bam_set_allocator(ssvh_bam *b, void *(*alloc)(size_t), void (*release)(
 	if (b->ra_thread.joinable()) { g_err = "a read-ahead is in flight"; return -1; }
 	b->alloc.alloc = alloc; b->alloc.release = release;
 	for (auto &B : b->buf) B.use(&b->alloc); // arrays that exist keep their memory until they have to grow
+	return 0;
+}
+
+int ssvh_bam_keep_names(ssvh_bam *b, int on)
+{
+	if (b->ra_thread.joinable()) { g_err = "a read-ahead is in flight"; return -1; }
+	b->keep_names = on != 0;
+	return 0;
+}
+
+int ssvh_bam_batch_names(const ssvh_bam *b, ssv_names_t *out)
+{
+	if (!out) { g_err = "ssvh_bam_batch_names: no output"; return -1; }
+	if (!b->keep_names) { g_err = "ssvh_bam_batch_names: names are not kept (ssvh_bam_keep_names)"; return -1; }
+	const ssvh_bam::BatchBuf &B = b->buf[b->cur];
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_HOST;
+	out->base = B.names.data(); out->off = B.name_off.data();
+	out->bytes = B.name_off.empty() ? 0 : (int64_t)B.name_off.back();
 	return 0;
 }
 

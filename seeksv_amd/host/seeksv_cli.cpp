@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "junction_stage.h"
+#include "readthrough_stage.h"
 #include "somatic_stage.h"
 #include "unmapped_pairs.h"
 #include "../csrc/thp.h"
@@ -126,7 +127,9 @@ static void release_ctx(ssv_ctx *ctx);
 [[noreturn]] static void usage_getsv()
 {
 	cerr << "Usage: seeksv getsv [options] <input clipped sequence bam> <input orignal sorted bam> <soft-clipped reads file(*clip.gz)> <output SVs> <output unmaped clipped sequence fastq>\n"
-	     << "Options: -B <FILE>             junction table (23 columns, as written by getsv) to evaluate in addition\n"
+	     << "Options: -F <FILE>             BAM of connected read-through reads (split alignments, e.g. bwa bwasw): their junctions are evaluated in addition\n"
+	     << "         -w <int>              Minimum mapping quality of the -F reads [1]\n"
+	     << "         -B <FILE>             junction table (23 columns, as written by getsv) to evaluate in addition\n"
 	     << "         -l <int>              Maximum search length to find microhomology [50]\n"
 	     << "         -q <int>              Minimum mapping quality of discordant read pair [20]\n"
 	     << "         -n <int>              Number of read pairs used to calculate insert size [5000000]; < 100000 switches the discordant pass off\n"
@@ -139,7 +142,7 @@ static void release_ctx(ssv_ctx *ctx);
 	     << "         -m <int>              Minimum length of up_seq / down_seq when no read pair supports the junction [30]\n"
 	     << "         -i <int>              Maximum indel number of up_seq / down_seq when no read pair supports the junction [1]\n"
 	     << "         -L <int>              Flank length for the average depths [200]\n"
-	     << "         -t <double> -Q <int> -w <int>   accepted for compatibility\n"
+	     << "         -t <double> -Q <int>  accepted for compatibility\n"
 	     << "         -G <int>[,<int>...]   GPU ordinal(s) [0; with -N: all GPUs of the machine in order]\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU; the ranks' tallies and depths meet in one RCCL all-gather [1]\n"
 	     << "         -Z                    inflate and decode the BAM on the GPU (compressed blocks over PCIe) instead of on the host threads" << endl
@@ -398,6 +401,8 @@ struct BatchSource {
 	ssv_ctx *ctx = nullptr;
 	bool on_device = false;
 	bool resident = false;   // the records are in HBM already (g_resident)
+	bool allow_resident = true; // (getsv -F reads its file itself: the resident batches carry no read names)
+	bool any_order = false;     // -Z: a file in any record order (getsv -F: split alignments in read order) - ssv_bamdec_any_order
 	size_t resident_next = 0;
 	// ---- device mode: a reader thread runs up to three chunks ahead of the decoder ----
 	// A chunk = whole BGZF blocks, the file's bytes as they are.  Two ways to get them to the GPU:
@@ -448,7 +453,7 @@ struct BatchSource {
 		if (ssvh_bam_open(path.c_str(), &bam) != 0) die(open_error);
 		if (g_resident.ctx || !on_device) ctx = get_ctx();
 		ssv_ctx *const c = ctx;
-		if (!ranged && !g_resident.collect && c && g_resident.ctx == c && !g_resident.batches.empty() && path == g_resident.path) { resident = true; on_device = true; return; }
+		if (allow_resident && !ranged && !g_resident.collect && c && g_resident.ctx == c && !g_resident.batches.empty() && path == g_resident.path) { resident = true; on_device = true; return; }
 		if (!on_device) {
 			if (ranged && ssvh_bam_set_range(bam, r_start_coff, r_start_uoff, r_end_coff, r_end_uoff) != 0) die(string("[seeksv] ") + ssvh_last_error());
 			use_pinned_batches(bam);
@@ -478,6 +483,7 @@ struct BatchSource {
 		if (ssv_bamdec_begin(ctx, ssvh_bam_n_targets(bam), first) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 		if (ssv_bamdec_target_lens(ctx, ssvh_bam_target_lens(bam)) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 		if (g_verify_crc) ssv_bamdec_verify_crc(ctx, 1);
+		if (any_order && ssv_bamdec_any_order(ctx, 1) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 		if (ranged) ssv_bamdec_prev_tid(ctx, r_prev_tid);
 		if (!file_bytes || file_bytes > first_bytes_default()) ssv_bamdec_expect(ctx, chunk_inflated);
 	}
@@ -1219,11 +1225,51 @@ static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const st
 
 static void resident_alignments(seeksv::AlnRecords &R); // `seeksv run`: the aligner step's records as the join reads them
 
+// getsv -F: FindJunction (process_bwasw.cpp:5-227).  The file goes through the same readers as the original BAM (host threads, or the GPU with -Z);
+// selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
+static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, bool device_inflate, JunctionMap &junction2other)
+{
+	static const char *kOpenError = "[main_samview] fail to open file for reading.";
+	// a name without ".bam" is SAM text to the reference (samopen mode "r"): this build reads BAM only
+	if (path.size() < 4 || path.rfind(".bam") != path.size() - 4) die(kOpenError);
+	ssvh_bam *hdr = nullptr;
+	if (ssvh_bam_open(path.c_str(), &hdr) != 0) die(kOpenError);
+	const int32_t nt = ssvh_bam_n_targets(hdr);
+	vector<string> names((size_t)nt);
+	for (int32_t t = 0; t < nt; ++t) { const char *z = ssvh_bam_target_name(hdr, t); names[(size_t)t] = z ? z : ""; }
+	ssvh_bam_close(hdr);
+	// contigs in byte-wise name order: the device compares (rank, pos) where the reference compares make_pair(chr, pos)
+	vector<int32_t> order((size_t)nt), rank((size_t)nt);
+	for (int32_t t = 0; t < nt; ++t) order[(size_t)t] = t;
+	std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return names[(size_t)a] < names[(size_t)b]; });
+	for (int32_t k = 0; k < nt; ++k) rank[(size_t)order[(size_t)k]] = k;
+	ssv_rt_params rp;
+	memset(&rp, 0, sizeof(rp));
+	rp.min_mapq = min_mapq; rp.n_targets = nt; rp.name_rank = rank.data();
+	if (ssv_rt_begin(ctx, &rp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	BatchSource src;
+	src.allow_resident = false;
+	src.any_order = true; // (a bwasw file is in read order, not coordinate order)
+	src.open(path, ctx, device_inflate, kOpenError);
+	if (!src.on_device && ssvh_bam_keep_names(src.bam, 1) != 0) die(string("[seeksv] ") + ssvh_last_error());
+	ssv_batch_t b;
+	while (src.next(&b, 1)) { // (every record's bases: the 3'-branch records without S are kept too)
+		ssv_names_t nm;
+		const int rc = src.on_device ? ssv_bamdec_names(ctx, &nm) : (ssvh_bam_batch_names(src.bam, &nm) == 0 ? SSV_OK : SSV_E_ARG);
+		if (rc != SSV_OK) die(string("[seeksv] ") + (src.on_device ? ssv_last_error(ctx) : ssvh_last_error()));
+		if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	}
+	src.close();
+	ssv_rt_result res;
+	if (ssv_rt_finish(ctx, &res) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	seeksv::apply_readthrough(res, names, junction2other);
+}
+
 static int cmd_getsv(int argc, char **argv)
 {
 	string connect_bam, temp_breakpoint, dump_junctions;
 	double frequency = 0.1;
-	int c, min_mapQ = 20, read_pair_used = 5000000, sum_min_no_both_clipped_reads = 3, min_distance = 50, microhomology_length = 50, times = 4, device = 0,
+	int c, min_mapQ2 = 1, min_mapQ = 20, read_pair_used = 5000000, sum_min_no_both_clipped_reads = 3, min_distance = 50, microhomology_length = 50, times = 4, device = 0,
 	       min_abnormal_read_pair_no = 0, flank_length = 200, min_seq_len = 30, max_seq_indel_no = 1, flank = 50, n_ranks = 1;
 	bool output_depth = true, device_inflate = device_inflate_default();
 	vector<int> devices;
@@ -1249,13 +1295,13 @@ static int cmd_getsv(int argc, char **argv)
 		case 'C': g_verify_crc = true; break;
 		case 'N': n_ranks = atoi(optarg); break;
 		case 'J': dump_junctions = optarg; break;
-		default: break; // -t -Q -w -a -R -r: accepted, unused (as in the reference, where -t / -Q no longer reach the join)
+		case 'w': min_mapQ2 = atoi(optarg); break; // -F's mapping-quality floor (seeksv.cpp:221-225)
+		default: break; // -t -Q -a -R -r: accepted, unused (as in the reference, where -t / -Q no longer reach the join)
 		}
 	}
 	if (argc != optind + 5) usage_getsv();
 	if (flank > 90 || flank < 0 || min_seq_len < 0 || n_ranks < 1) usage_getsv();
 	const string clip_bam = argv[optind], original_bam = argv[optind + 1], clipfile = argv[optind + 2], breakpoint_file = argv[optind + 3], clip_unmap_fq_file = argv[optind + 4];
-	if (!connect_bam.empty()) die("[seeksv] -F (bwasw read-through input) is not supported by this build");
 
 	JunctionMap junction2other;
 	if (!temp_breakpoint.empty()) { // ReadBreakpoint, getsv.cpp:1292-1323
@@ -1278,6 +1324,13 @@ static int cmd_getsv(int argc, char **argv)
 			junction2other.insert(make_pair(j, o));
 		}
 		cerr << "[ReadBreakpoint] finish" << endl;
+	}
+	ssv_ctx *rt_ctx = nullptr;
+	if (!connect_bam.empty()) { // FindJunction (seeksv.cpp:221-225): after the -B rows, before the clip join; with -N n once, on the first device
+		rt_ctx = acquire_ctx(device);
+		readthrough_pass(connect_bam, min_mapQ2, rt_ctx, device_inflate, junction2other);
+		cerr << "'FindJunction' finished" << endl;
+		pt.lap("readthrough (-F)");
 	}
 	{ // InputSoftInfoStoreBreakpoint + GetJunction (getsv.h:423, getsv.cpp:1705): clip clusters x re-alignments of their clipped sequences
 		string err;
@@ -1309,7 +1362,7 @@ static int cmd_getsv(int argc, char **argv)
 	pt.lap("junction_stage");
 	ssvh_bam *bam = nullptr;
 	if (ssvh_bam_open(original_bam.c_str(), &bam) != 0) die("[main_samview] fail to open file " + original_bam + "for reading.");
-	ssv_ctx *ctx = nullptr;
+	ssv_ctx *ctx = rt_ctx;
 	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(device); return ctx; }; // (main() started it before the junction stage)
 
 	int mean_insert_size = 0, deviation = 0;
