@@ -37,33 +37,23 @@ struct ssv_bamdec_state {
 	ssv_bamdec_info info{};
 };
 
-static void bamdec_free(ssv_ctx *c)
+// before the context's buffers go (ssv_ctx_destroy): a copy still on its way into a slot lands, and the events and HSA signals are destroyed while c->link is valid
+static void bamdec_release_handles(ssv_ctx *c)
 {
-	ssv_bamdec_state *d = c->bd;
+	ssv_bamdec_state *d = c->bd.get();
 	if (!d) return;
-	if (d->raw_runs.p) (void)hipFree(d->raw_runs.p);
-	if (d->h_raw_runs.p) (void)pinned_delete(d->h_raw_runs.p);
-	DBuf *db[] = {&d->inf_scratch, &d->inf_dbg, &d->tokens, &d->tok_off, &d->n_tok, &d->carrybuf, &d->comp, &d->blocks, &d->u_off, &d->stream, &d->status, &d->chain, &d->count, &d->base, &d->rec_off, &d->stitch, &d->tile_last, &d->tile_prev, &d->runs, &d->small,
-	              &d->tlen, &d->rel, &d->stash, &d->seq_list, &d->tid, &d->pos, &d->l_qseq, &d->mtid, &d->mpos, &d->isize, &d->flag, &d->n_cigar, &d->mapq, &d->xc, &d->ends, &d->seq_bytes, &d->raw_bytes, &d->cigar_off, &d->seq_off, &d->raw_off, &d->cigar,
-	              &d->seqqual, &d->raw, &d->crc_tab};
-	for (DBuf *b : db) if (b->p) (void)hipFree(b->p);
 	for (auto &sl : d->slot) {
 		if (sl.via_link && sl.host) link_wait(c, sl.up_sig); // (a copy still on its way into the slot)
-		if (sl.buf.p) (void)hipFree(sl.buf.p); if (sl.up) (void)hipEventDestroy(sl.up); if (sl.done) (void)hipEventDestroy(sl.done);
+		if (sl.up) (void)hipEventDestroy(sl.up); if (sl.done) (void)hipEventDestroy(sl.done);
 		if (c->link.signal_destroy && sl.up_sig.handle) (void)c->link.signal_destroy(sl.up_sig);
 	}
 	if (c->link.signal_destroy && d->own_sig.handle) (void)c->link.signal_destroy(d->own_sig);
-
-	HBuf *hb[] = {&d->h_stage[0], &d->h_stage[1], &d->h_stage[2], &d->h_small, &d->h_raw[0], &d->h_raw[1], &d->h_runs, &d->h_status};
-	for (HBuf *b : hb) if (b->p) (void)pinned_delete(b->p);
-	delete d;
-	c->bd = nullptr;
 }
 
 int ssv_bamdec_begin(ssv_ctx *c, int32_t n_targets, uint64_t first_record_offset)
 {
 	if (!c || n_targets < 0) return SSV_E_ARG;
-	if (!c->bd) c->bd = new ssv_bamdec_state();
+	if (!c->bd) c->bd.reset(new ssv_bamdec_state());
 	c->bd->have_tlen = false;
 	c->bd->n_targets = n_targets; c->bd->start = first_record_offset; c->bd->prev_tid = 0; c->bd->carry = 0; c->bd->limit = UINT64_MAX; c->bd->expect_inflated = 0; c->bd->verify_crc = false;
 	c->bd->any_order = false;

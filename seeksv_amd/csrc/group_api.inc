@@ -86,9 +86,8 @@ void ssv_group_destroy(ssv_group *g)
 	if (!g) return;
 	for (rcclComm_t c : g->comm) if (c) (void)g_rccl.CommDestroy(c);
 	for (size_t k = 0; k < g->d_send.size(); ++k) {
-		(void)hipSetDevice(g->ctx[k]->device);
-		if (g->d_send[k].p) (void)hipFree(g->d_send[k].p);
-		if (g->d_recv[k].p) (void)hipFree(g->d_recv[k].p);
+		(void)hipSetDevice(g->ctx[k]->device); // (a rank's buffers go with its device current)
+		g->d_send[k].reset(); g->d_recv[k].reset();
 	}
 	delete g;
 }

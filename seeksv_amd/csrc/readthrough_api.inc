@@ -16,26 +16,12 @@ struct ssv_rt_state {
 	HBuf h_small, h_pairs, h_seqs, h_cigs;
 };
 
-static void rt_free(ssv_ctx *c)
-{
-	if (!c->rt) return;
-	ssv_rt_state &R = *c->rt;
-	DBuf *d[] = {&R.rank, &R.keep, &R.at, &R.cand, &R.nbytes, &R.sbytes, &R.cops, &R.small, &R.hnames, &R.hoff, &R.cands, &R.hash, &R.names, &R.seqs, &R.cigs,
-	             &R.keys[0], &R.keys[1], &R.vals[0], &R.vals[1], &R.held, &R.partner, &R.ev_flag, &R.ev_at, &R.ev_b, &R.pairs, &R.slices, &R.cig_src, &R.pseq, &R.pcig,
-	             &R.seq_out, &R.cig_out};
-	for (DBuf *b : d) if (b->p) (void)hipFree(b->p);
-	HBuf *h[] = {&R.h_small, &R.h_pairs, &R.h_seqs, &R.h_cigs};
-	for (HBuf *b : h) if (b->p) (void)pinned_delete(b->p);
-	delete c->rt;
-	c->rt = nullptr;
-}
-
 int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p)
 {
 	if (!c) return SSV_E_ARG;
 	if (!p || p->n_targets < 0 || (p->n_targets > 0 && !p->name_rank)) { c->err = "ssv_rt_begin: bad parameters"; return SSV_E_ARG; }
 	HIPCHECK(c, hipSetDevice(c->device));
-	if (!c->rt) c->rt = new ssv_rt_state();
+	if (!c->rt) c->rt.reset(new ssv_rt_state());
 	ssv_rt_state &R = *c->rt;
 	R.phase = ssv_rt_state::IDLE;
 	R.min_mapq = p->min_mapq; R.n_targets = p->n_targets;
@@ -130,10 +116,9 @@ static void rt_release_store(ssv_ctx *c)
 {
 	ssv_rt_state &R = *c->rt;
 	(void)hipStreamSynchronize(c->st);
-	DBuf *d[] = {&R.keep, &R.at, &R.cand, &R.nbytes, &R.sbytes, &R.cops, &R.hnames, &R.hoff, &R.cands, &R.hash, &R.names, &R.seqs, &R.cigs,
-	             &R.keys[0], &R.keys[1], &R.vals[0], &R.vals[1], &R.held, &R.partner, &R.ev_flag, &R.ev_at, &R.ev_b, &R.pairs, &R.slices, &R.cig_src, &R.pseq, &R.pcig,
-	             &R.seq_out, &R.cig_out};
-	for (DBuf *b : d) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+	for (DBuf *b : {&R.keep, &R.at, &R.cand, &R.nbytes, &R.sbytes, &R.cops, &R.hnames, &R.hoff, &R.cands, &R.hash, &R.names, &R.seqs, &R.cigs,
+	                &R.keys[0], &R.keys[1], &R.vals[0], &R.vals[1], &R.held, &R.partner, &R.ev_flag, &R.ev_at, &R.ev_b, &R.pairs, &R.slices, &R.cig_src, &R.pseq, &R.pcig,
+	                &R.seq_out, &R.cig_out}) b->reset();
 	R.n_cand = 0; R.name_used = R.seq_used = R.cig_used = 0;
 }
 

@@ -9,21 +9,12 @@ struct ssv_realign_state {
 	bool ready = false;
 };
 
-static void realign_free(ssv_ctx *c)
-{
-	if (!c->ra) return;
-	DBuf *bufs[] = {&c->ra->ref, &c->ra->ctg, &c->ra->table, &c->ra->seqs, &c->ra->offs, &c->ra->hits, &c->ra->dropped};
-	for (DBuf *b : bufs) if (b->p) (void)hipFree(b->p);
-	delete c->ra;
-	c->ra = nullptr;
-}
-
 int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped)
 {
 	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
 	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
 	HIPCHECK(c, hipSetDevice(c->device));
-	if (!c->ra) c->ra = new ssv_realign_state();
+	if (!c->ra) c->ra.reset(new ssv_realign_state());
 	ssv_realign_state &R = *c->ra;
 	R.ready = false;
 	const size_t words = (size_t)((n_bases + 31) / 32);
@@ -89,6 +80,6 @@ int ssv_realign_free(ssv_ctx *c)
 	if (!c) return SSV_E_ARG;
 	HIPCHECK(c, hipSetDevice(c->device));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
-	realign_free(c);
+	c->ra.reset();
 	return SSV_OK;
 }
