@@ -70,6 +70,15 @@ class Context:
         """FindJunction (process_bwasw.cpp:5-227) over host batches in file order.  batches: dicts of arrays (or _abi.Batch) that carry every kept
         record's bases; names[k]: the read names of batch k (str).  Returns one dict per pair, in the order of the record that completed it:
         the junction (contig names when target_names is given, else tids), microhomology, kind, the two seqs and CIGAR sources with their edits."""
+        self.rt_begin(min_mapq, target_names)
+        for b, nm in zip(batches, names):
+            self.rt_scan(b, nm)
+        r = self.rt_finish()
+        out = self.rt_decode(r, target_names)
+        return (out, r.n_candidates) if raw else out
+
+    def rt_begin(self, min_mapq=1, target_names=()):
+        """ssv_rt_begin: a new -F file; target_names give the contigs' byte-wise name order (and the number of contigs a tid may name)"""
         nt = len(target_names)
         order = sorted(range(nt), key=lambda t: target_names[t].encode())
         rank = np.zeros(max(nt, 1), dtype=np.int32)
@@ -77,28 +86,43 @@ class Context:
             rank[t] = k
         p = _abi.RtParams(int(min_mapq), nt, rank.ctypes.data_as(C.POINTER(C.c_int32)))
         self._check(self._lib.ssv_rt_begin(self._h, C.byref(p)), "ssv_rt_begin")
-        for b, nm in zip(batches, names):
-            bb, keep = self._as_batch(b)
-            blob = b"".join(x.encode() + b"\0" for x in nm)
-            off = np.zeros(len(nm) + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(x.encode()) + 1 for x in nm])
+
+    def rt_scan(self, batch, names):
+        """ssv_rt_scan: the next batch in file order.  names: the batch's read names (list of str), or an _abi.Names that says where they lie -
+        bamdec_names() for a batch of the device decoder"""
+        bb, keep = self._as_batch(batch)
+        if isinstance(names, _abi.Names):
+            n = names
+        else:
+            blob = b"".join(x.encode() + b"\0" for x in names)
+            off = np.zeros(len(names) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x.encode()) + 1 for x in names])
             buf = C.create_string_buffer(blob, len(blob) + 1)
             n = _abi.Names(_abi.MEM_HOST, 0, 0, C.cast(buf, C.c_void_p), off.ctypes.data, len(blob))
-            self._check(self._lib.ssv_rt_scan(self._h, C.byref(bb), C.byref(n)), "ssv_rt_scan")
+        self._check(self._lib.ssv_rt_scan(self._h, C.byref(bb), C.byref(n)), "ssv_rt_scan")
+
+    def rt_finish(self):
+        """ssv_rt_finish -> _abi.RtResult: host memory of the context, valid until the next rt_begin (decode it with rt_decode)"""
         r = _abi.RtResult()
         self._check(self._lib.ssv_rt_finish(self._h, C.byref(r)), "ssv_rt_finish")
+        return r
+
+    @staticmethod
+    def rt_decode(r, target_names=()):
+        """the pairs of an _abi.RtResult as dicts (see readthrough)"""
+        nt = len(target_names)
+        ctg = (lambda t: target_names[t]) if nt else (lambda t: t)
         out = []
         for k in range(r.n_pairs):
             q = r.pairs[k]
             seqs = C.string_at(r.seqs + q.seq_off, q.up_len + q.down_len).decode() if q.up_len + q.down_len else ""
             ops = [r.cigars[q.cig_off + j] for j in range(q.up_cig_n + q.down_cig_n)]
-            ctg = (lambda t: target_names[t]) if nt else (lambda t: t)
             out.append(dict(key=(ctg(q.up_tid), q.up_pos, chr(q.up_strand), ctg(q.down_tid), q.down_pos, chr(q.down_strand)),
                             microhomology=q.microhomology, kind=q.kind, up_seq=seqs[:q.up_len], down_seq=seqs[q.up_len:],
                             clipped=(q.up_left_clipped, q.up_right_clipped, q.down_left_clipped, q.down_right_clipped),
                             up_cigar=ops[:q.up_cig_n], down_cigar=ops[q.up_cig_n:], edits=(q.up_cig_edit, q.down_cig_edit),
                             records=(q.first_record, q.second_record)))
-        return (out, r.n_candidates) if raw else out
+        return out
 
     # ---- device-side BGZF inflate + BAM decode ----
     def bamdec_target_lens(self, lens):
@@ -106,7 +130,13 @@ class Context:
         arr = (C.c_int32 * max(1, len(lens)))(*[int(x) for x in lens])
         self._check(self._lib.ssv_bamdec_target_lens(self._h, arr), "ssv_bamdec_target_lens")
 
-    def bam_batches(self, reader, chunk_bytes=64 << 20, max_blocks=1 << 16, keep_all_seq=False, chunk_inflated=1 << 31, prefetch=True, verify_crc=False):
+    def bamdec_names(self):
+        """ssv_bamdec_names: where the read names of the batch bam_batches handed out last lie in HBM (valid as long as that batch)"""
+        n = _abi.Names()
+        self._check(self._lib.ssv_bamdec_names(self._h, C.byref(n)), "ssv_bamdec_names")
+        return n
+
+    def bam_batches(self, reader, chunk_bytes=64 << 20, max_blocks=1 << 16, keep_all_seq=False, chunk_inflated=1 << 31, prefetch=True, verify_crc=False, any_order=False):
         """Generator over SSV_MEM_DEVICE batches of a whole BAM file (host.BamReader), decoded on the GPU: yields (Batch, info dict).
         The batch is valid until the next iteration.  prefetch: chunk k+1 is read into the second staging buffer and announced
         (ssv_bamdec_prefetch) before chunk k is decoded, so its bytes cross PCIe while chunk k's kernels run."""
@@ -116,6 +146,8 @@ class Context:
             raise IOError(hl.ssvh_last_error().decode())
         self._check(self._lib.ssv_bamdec_begin(self._h, len(reader.target_names), first.value), "ssv_bamdec_begin")
         self.bamdec_target_lens(reader.target_lens)
+        if any_order:    # a file in read order (getsv -F): any number of contig changes per chunk
+            self._check(self._lib.ssv_bamdec_any_order(self._h, 1), "ssv_bamdec_any_order")
         if verify_crc:   # every inflated block against the CRC32 in its BGZF trailer (off by default, like libbam 0.1.16)
             self._check(self._lib.ssv_bamdec_verify_crc(self._h, 1), "ssv_bamdec_verify_crc")
         stages, blocks = [None, None], [None, None]

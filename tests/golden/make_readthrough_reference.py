@@ -3,7 +3,9 @@
 `getsv -F` on the seeded inputs of tests/readthrough_inputs.py.  The small hand-made file: the .sv text and stdout whole, and the order of
 the stderr lines; the random files: sha256 digests.  The tests rebuild the inputs from the seeds.  CPU only.
 
-usage: python tests/golden/make_readthrough_reference.py
+model_anchor: generated samples of tests/readthrough_model.py, the .sv text and stdout whole (held against the Python model of FindJunction).
+
+usage: python tests/golden/make_readthrough_reference.py [section ...]     (all sections by default)
 """
 import hashlib
 import json
@@ -77,10 +79,45 @@ def large(d):
     return {"records": len(recs), "contig_changes": RT.contig_changes(recs), "sv": sha(text), "stdout": sha(r.stdout), "sv_lines": text.count("\n")}
 
 
+def model_anchor(d):
+    """generated samples (tests/readthrough_model.py, safe: only inputs the reference defines) with contigs of their own: the original BAM is a
+    few hundred proper pairs on the sample's first contig, indexed through the reference's libbam; the .sv text and stdout whole"""
+    import bamio
+    import readthrough_model as M
+    out = {}
+    for seed in M.ANCHOR_SEEDS:
+        sd = os.path.join(d, f"a{seed}")
+        os.makedirs(sd)
+        s = M.anchor_sample(seed)
+        fbam, bg = os.path.join(sd, "f.bam"), os.path.join(sd, "bg.bam")
+        bamio.write_bam(fbam, s["contigs"], s["lens"], M.sample_records(s))
+        pairs = []
+        for k in range(300):
+            p = 1000 + 20 * k
+            pairs.append(dict(qname=f"p{k}", flag=99, tid=0, pos=p, mapq=60, cigar="100M", mtid=0, mpos=p + 200, isize=300, seq="A" * 100, qual="I" * 100))
+            pairs.append(dict(qname=f"p{k}", flag=147, tid=0, pos=p + 200, mapq=60, cigar="100M", mtid=0, mpos=p, isize=-300, seq="A" * 100, qual="I" * 100))
+        bamio.write_bam(bg, s["contigs"], s["lens"], sorted(pairs, key=lambda r: r["pos"]))
+        subprocess.check_call([os.path.join(ROOT, "oracle", "_ref", "bamidx"), bg])
+        clip_bam, clip = os.path.join(sd, "e.clip.bam"), os.path.join(sd, "e.clip")
+        bamio.write_bam(clip_bam, s["contigs"], s["lens"], [])
+        open(clip, "w").close()
+        e = out[str(seed)] = {"records": len(s["qnames"])}
+        for tag, w in M.ANCHOR_RUNS:
+            sv = os.path.join(sd, f"o.{tag}.sv")
+            r = ref(["getsv"] + RT.LOOSE + ["-w", str(w), "-F", fbam, clip_bam, bg, clip, sv, os.path.join(sd, "x.fq")])
+            e[tag] = {"sv": open(sv).read(), "stdout": r.stdout}
+    return out
+
+
+SECTIONS = (("small", small), ("random", random), ("large", large), ("model_anchor", model_anchor))
+
+
 def main():
     assert os.path.exists(REF), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
-    for name, fn in (("small", small), ("random", random), ("large", large)):
+    for name, fn in SECTIONS:
+        if len(sys.argv) > 1 and name not in sys.argv[1:]:
+            continue
         with tempfile.TemporaryDirectory() as d:
             data = fn(d)
         with open(os.path.join(OUT, name + ".json"), "w") as f:
