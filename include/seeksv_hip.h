@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
+                             v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
                              v9: ssv_table_block_bytes(left_len, right_len) lost the parameters of the removed formats; ssv_bamdec_info.unmapped_raw stays valid for one more decode.
                              v8: table formats 1 and 2 (four-piece blocks with 4-bit bases) removed - 0 ASCII or 3 compact; ssv_group with SSV_GROUP_RCCL_ONE */
 
@@ -499,6 +500,47 @@ typedef struct {
 } ssv_names_t;
 /* The names of the last chunk ssv_bamdec_decode handed out, in HBM (valid as long as that batch). */
 int ssv_bamdec_names(ssv_ctx *ctx, ssv_names_t *out);
+/* ---- device-side SAM text decode (getsv -F: `bwa bwasw` writes SAM text; process_bwasw.cpp:12-16 opens every name without ".bam" as text) ----
+ * What libbam 0.1.16's sam_read1 does per line on one core, for a whole chunk of the file on the GPU: the caller hands over the file's TEXT as it is
+ * (after the header) and gets the records as an SSV_MEM_DEVICE batch, like ssv_bamdec_decode's with keep_all_seq, plus the read names.
+ * Grammar: well-formed lines decode to what libbam's text reader gives; everything else is refused (SSV_E_ARG, "Parse error at line N: reason" in
+ * ssv_last_error; lines are counted over the whole file, header included) - fewer than 11 fields, an empty line, an '@' line among the records, a
+ * name that is empty or longer than 254 bytes, a number that is none or out of range (FLAG decimal - without a leading 0, which is octal to libbam - or 0x hex, up to 65535, POS / PNEXT 0..2^31-1 stored
+ * minus 1, MAPQ 0..255, TLEN signed 32 bits with '-' as the only sign: a leading '+' is refused, though libbam's atoi takes it, CIGAR lengths below 2^28), a CIGAR with a character outside MIDNSHP=X, an operation without a length or
+ * more than 65535 operations, "CIGAR and sequence length are inconsistent", "sequence and quality are inconsistent", a QUAL byte below 33, a NUL byte.
+ * RNAME / RNEXT: '*' and names that are not in the header give -1, RNEXT '=' gives tid.  SEQ bytes: '=' 0, "ACMGRSVTWYHKDBN" in either case 1..15,
+ * "0123" 1 2 4 8, every other byte 15; '*' gives l_qseq 0.  CIGAR '*' gives n_cigar 0 and sets flag 4, as libbam does ("mapped sequence without CIGAR").  QUAL '*' gives 0xff bytes.  A '\r' before the newline is dropped.  Optional fields are
+ * ignored except XC:i: (xc = 1 when its value is not 0).  '=' and 'X' in a CIGAR are BAM's codes 7 and 8 (libbam's text reader aborts on them). */
+typedef struct {
+	int32_t n_targets;                 /* contigs of the header (@SQ lines, in order) */
+	int32_t pad;
+	const char *const *target_names;   /* [n_targets] host, NUL-terminated; read during the call */
+	uint64_t first_line;               /* 1-based line number, in the file, of the first line that will be handed to ssv_samdec_decode */
+} ssv_samdec_params;
+
+typedef struct {
+	int64_t n_records;       /* records of the last decode */
+	uint64_t lines_consumed; /* lines decoded since ssv_samdec_begin */
+	uint64_t carried_bytes;  /* bytes of the unfinished last line kept for the next decode */
+	uint64_t refused_line;   /* 0, or the file line number of the first line that was refused */
+	const char *refused_reason; /* NULL, or why (static text) */
+} ssv_samdec_info;
+
+int ssv_samdec_begin(ssv_ctx *ctx, const ssv_samdec_params *p);
+/* Optional: announce the next chunk (host memory, best page-locked): its bytes start their way to the GPU on the upload stream at once, under the kernels of the
+ * chunk before; ssv_samdec_decode of the same (text, bytes) finds them there.  The memory must stay untouched until that decode returns.  Two may be announced. */
+int ssv_samdec_prefetch(ssv_ctx *ctx, const void *text, size_t bytes);
+/* The next `bytes` bytes of the file, cut ANYWHERE (mem: SSV_MEM_HOST or SSV_MEM_DEVICE).  The unfinished last line is carried inside the context and moved,
+ * on the device, in front of the next chunk's bytes: every line is contiguous in HBM.  last != 0: the file ends here - a final line without a newline is a
+ * record (bytes == 0 with last flushes); the next call must be ssv_samdec_begin.  *out: an SSV_MEM_DEVICE batch owned by the context, valid until the next
+ * decode (stream ordered): hot columns, cigar_ends, record lines (rec), all CIGAR operations, every record's packed bases and qualities; n_tid_runs = 0 (the
+ * file is in read order).  carry + bytes must stay below 4 GB.  After a refused line only ssv_samdec_begin is accepted.  Synchronises the stream. */
+int ssv_samdec_decode(ssv_ctx *ctx, const void *text, size_t bytes, int mem, int last, ssv_batch_t *out);
+/* The read names of the last decoded batch: C strings inside the context's copy of the text (the first tab of every line is overwritten with a NUL),
+ * off[i] = where line i starts.  Valid as long as that batch. */
+int ssv_samdec_names(ssv_ctx *ctx, ssv_names_t *out);
+int ssv_samdec_last(ssv_ctx *ctx, ssv_samdec_info *info);
+
 /* Copy a device batch into host arrays owned by the context (valid until the next call): tests and debugging. */
 int ssv_batch_to_host(ssv_ctx *ctx, const ssv_batch_t *device_batch, ssv_batch_t *host_batch);
 

@@ -246,6 +246,16 @@ class BamdecInfo(C.Structure):
                 ("unmapped_raw", C.c_void_p), ("unmapped_bytes", C.c_uint64), ("n_tid_runs", C.c_uint32), ("tid_run_index", C.c_void_p), ("tid_run_tid", C.c_void_p)]
 
 
+class SamdecParams(C.Structure):
+    """ssv_samdec_params (include/seeksv_hip.h)"""
+    _fields_ = [("n_targets", C.c_int32), ("pad", C.c_int32), ("target_names", C.POINTER(C.c_char_p)), ("first_line", C.c_uint64)]
+
+
+class SamdecInfo(C.Structure):
+    """ssv_samdec_info (include/seeksv_hip.h)"""
+    _fields_ = [("n_records", C.c_int64), ("lines_consumed", C.c_uint64), ("carried_bytes", C.c_uint64), ("refused_line", C.c_uint64), ("refused_reason", C.c_char_p)]
+
+
 _libs = {}
 
 
@@ -369,5 +379,10 @@ def hip_lib():
         lib.ssv_rt_begin.argtypes = [V, C.POINTER(RtParams)]
         lib.ssv_rt_scan.argtypes = [V, C.POINTER(Batch), C.POINTER(Names)]
         lib.ssv_rt_finish.argtypes = [V, C.POINTER(RtResult)]
+        lib.ssv_samdec_begin.argtypes = [V, C.POINTER(SamdecParams)]
+        lib.ssv_samdec_prefetch.argtypes = [V, V, C.c_size_t]
+        lib.ssv_samdec_decode.argtypes = [V, V, C.c_size_t, C.c_int, C.c_int, C.POINTER(Batch)]
+        lib.ssv_samdec_names.argtypes = [V, C.POINTER(Names)]
+        lib.ssv_samdec_last.argtypes = [V, C.POINTER(SamdecInfo)]
         lib._typed = True
     return lib

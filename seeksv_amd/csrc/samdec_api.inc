@@ -1,0 +1,260 @@
+// samdec_api.inc - host side of the device SAM-text decoder (included by seeksv_hip.hip inside extern "C"); kernels in samdec_kernels.h.
+// Per chunk: [carried line | text] in one buffer -> k_sam_count -> scans of the tile sums -> (sync: separators, lines) -> k_sam_marks -> k_sam_sizes ->
+// scans -> (sync: totals) -> k_sam_fields, k_sam_seqqual, the unfinished line to the side buffer -> (sync: refusals) -> device batch + names.
+
+struct ssv_samdec_state {
+	enum { IDLE, ACTIVE, ENDED, FAILED } phase = IDLE;
+	int32_t n_targets = 0;
+	uint64_t first_line = 1, lines_done = 0, carry = 0;
+	uint32_t ref_mask = 15;
+	DBuf ref_slots, ref_off, ref_blob;
+	DBuf text, carrybuf, tile_sep, tile_nl, sep, nlidx, small;
+	DBuf tid, pos, l_qseq, mtid, mpos, isize, flag, n_cigar, mapq, xc, ends, seq_bytes, cigar_off, seq_off, name_off, rec, cigar, seqqual;
+	HBuf h_small;
+	// chunks announced ahead (ssv_samdec_prefetch): on the upload stream into one of two slots, moved behind the carried line by the decode call
+	struct Slot { DBuf buf; const void *host = nullptr; size_t bytes = 0; hipEvent_t up = nullptr, done = nullptr; bool read = false; } slot[2];
+	int next_slot = 0;
+	bool have_batch = false;
+	uint64_t text_bytes = 0;
+	ssv_samdec_info info{};
+};
+
+static const char *const kSamReasons[ssv::SAM_E_COUNT] = {
+	"", "fewer than 11 fields", "empty line", "header line among the records", "read name is empty or longer than 254 bytes", "a number is missing, malformed or out of range",
+	"invalid CIGAR character", "CIGAR operation without a length", "more than 65535 CIGAR operations", "CIGAR and sequence length are inconsistent", "sequence and quality are inconsistent",
+	"quality byte below 33", "NUL byte"};
+
+static void samdec_release_handles(ssv_ctx *c)
+{
+	ssv_samdec_state *d = c->sd.get();
+	if (!d) return;
+	for (auto &sl : d->slot) { if (sl.up) (void)hipEventDestroy(sl.up); if (sl.done) (void)hipEventDestroy(sl.done); }
+}
+
+int ssv_samdec_begin(ssv_ctx *c, const ssv_samdec_params *p)
+{
+	if (!c) return SSV_E_ARG;
+	if (!p || p->n_targets < 0 || (p->n_targets > 0 && !p->target_names) || p->first_line < 1) { c->err = "ssv_samdec_begin: bad parameters"; return SSV_E_ARG; }
+	for (int32_t t = 0; t < p->n_targets; ++t) if (!p->target_names[t]) { c->err = "ssv_samdec_begin: bad parameters"; return SSV_E_ARG; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	if (!c->sd) c->sd.reset(new ssv_samdec_state());
+	ssv_samdec_state &d = *c->sd;
+	d.phase = ssv_samdec_state::IDLE;
+	{ // copies still on their way into a slot land in a slot nobody asks for
+		bool any = false;
+		for (auto &sl : d.slot) { any = any || sl.host; sl.host = nullptr; }
+		if (any) HIPCHECK(c, hipStreamSynchronize(c->st_h2d));
+	}
+	d.n_targets = p->n_targets; d.first_line = p->first_line; d.lines_done = 0; d.carry = 0; d.have_batch = false;
+	memset(&d.info, 0, sizeof(d.info));
+	// the contig names as a hash table: FNV-1a, linear probing, at most half full; the first of two equal names wins
+	uint32_t size = 16;
+	while (size < 2u * (uint32_t)p->n_targets) size <<= 1;
+	std::vector<uint32_t> slots(size, 0u), off((size_t)p->n_targets + 1, 0u);
+	std::string blob;
+	for (int32_t t = 0; t < p->n_targets; ++t) {
+		const char *z = p->target_names[t];
+		const size_t len = strlen(z);
+		off[(size_t)t] = (uint32_t)blob.size();
+		blob.append(z, len);
+		uint32_t h = 2166136261u;
+		for (size_t k = 0; k < len; ++k) h = (h ^ (uint8_t)z[k]) * 16777619u;
+		bool dup = false;
+		uint32_t at = h & (size - 1);
+		for (; slots[at]; at = (at + 1) & (size - 1)) {
+			const uint32_t u = slots[at] - 1;
+			if (off[u + 1] - off[u] == len && memcmp(blob.data() + off[u], z, len) == 0) { dup = true; break; }
+		}
+		off[(size_t)t + 1] = (uint32_t)blob.size();
+		if (!dup) slots[at] = (uint32_t)t + 1;
+	}
+	d.ref_mask = size - 1;
+	CHECK(ensure(c, d.ref_slots, (size_t)size * 4)); CHECK(ensure(c, d.ref_off, off.size() * 4)); CHECK(ensure(c, d.ref_blob, blob.size() + 16));
+	HIPCHECK(c, hipMemcpyAsync(d.ref_slots.p, slots.data(), (size_t)size * 4, hipMemcpyHostToDevice, c->st));
+	HIPCHECK(c, hipMemcpyAsync(d.ref_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->st));
+	if (!blob.empty()) HIPCHECK(c, hipMemcpyAsync(d.ref_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->st));
+	CHECK(ensure(c, d.small, 256)); CHECK(ensure_host(c, d.h_small, 256));
+	HIPCHECK(c, hipStreamSynchronize(c->st)); // (the vectors go with the call)
+	d.phase = ssv_samdec_state::ACTIVE;
+	return SSV_OK;
+}
+
+int ssv_samdec_prefetch(ssv_ctx *c, const void *text, size_t bytes)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->sd || c->sd->phase != ssv_samdec_state::ACTIVE) { c->err = "ssv_samdec_prefetch before ssv_samdec_begin"; return SSV_E_STATE; }
+	if (!text || !bytes) { c->err = "ssv_samdec_prefetch: bad arguments"; return SSV_E_ARG; }
+	ssv_samdec_state &d = *c->sd;
+	HIPCHECK(c, hipSetDevice(c->device));
+	for (auto &sl : d.slot) {
+		if (sl.host == text && sl.bytes == bytes) return SSV_OK; // announced already
+		if (sl.host == text) sl.host = nullptr;                    // the same memory with other contents: what was announced is given up
+	}
+	auto &sl = d.slot[d.next_slot];
+	if (sl.host) return SSV_OK; // both slots are taken: this chunk is copied by its decode call
+	d.next_slot ^= 1;
+	if (!sl.up) { HIPCHECK(c, hipEventCreateWithFlags(&sl.up, hipEventDisableTiming)); HIPCHECK(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)); }
+	if (sl.buf.cap < bytes + 64 && sl.read) HIPCHECK(c, hipEventSynchronize(sl.done)); // (growing frees the old slot)
+	CHECK(ensure(c, sl.buf, bytes + 64));
+	if (sl.read) HIPCHECK(c, hipStreamWaitEvent(c->st_h2d, sl.done, 0)); // the chunk that was in this slot may still be on its way into the text buffer
+	HIPCHECK(c, hipMemcpyAsync(sl.buf.p, text, bytes, hipMemcpyHostToDevice, c->st_h2d));
+	HIPCHECK(c, hipEventRecord(sl.up, c->st_h2d));
+	sl.host = text; sl.bytes = bytes; sl.read = false;
+	return SSV_OK;
+}
+
+static int samdec_refuse(ssv_ctx *c, unsigned long long word)
+{
+	ssv_samdec_state &d = *c->sd;
+	const uint32_t code = (uint32_t)(word & 0xffu);
+	const uint64_t line = d.first_line + d.lines_done + (uint64_t)(word >> 8);
+	d.info.refused_line = line;
+	d.info.refused_reason = code < ssv::SAM_E_COUNT ? kSamReasons[code] : "malformed line";
+	c->err = "Parse error at line " + std::to_string(line) + ": " + d.info.refused_reason;
+	d.phase = ssv_samdec_state::FAILED;
+	return SSV_E_ARG;
+}
+
+int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int last, ssv_batch_t *out)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->sd || c->sd->phase != ssv_samdec_state::ACTIVE) { c->err = "ssv_samdec_decode before ssv_samdec_begin (or behind the file's end or a refused line)"; return SSV_E_STATE; }
+	if (!out || (bytes && !text) || (mem != SSV_MEM_HOST && mem != SSV_MEM_DEVICE)) { c->err = "ssv_samdec_decode: bad arguments"; return SSV_E_ARG; }
+	ssv_samdec_state &d = *c->sd;
+	if (d.carry + (uint64_t)bytes >= 0xfffffff0ull) { c->err = "ssv_samdec_decode: the carried line and the chunk must stay below 4 GB"; return SSV_E_ARG; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	hipStream_t st = c->st;
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_DEVICE;
+	d.have_batch = false;
+	d.info.n_records = 0;
+	const uint64_t total = d.carry + bytes;
+	CHECK(ensure(c, d.text, (size_t)total + 128));
+	uint8_t *tx = P<uint8_t>(d.text);
+	if (d.carry) HIPCHECK(c, hipMemcpyAsync(tx, d.carrybuf.p, d.carry, hipMemcpyDeviceToDevice, st)); // the unfinished line of the chunk before, in front
+	if (bytes) {
+		ssv_samdec_state::Slot *from = nullptr;
+		if (mem == SSV_MEM_HOST) for (auto &sl : d.slot) {
+			if (sl.host == text && sl.bytes == bytes) from = &sl;
+			else if (sl.host == text) sl.host = nullptr; // announced with another size: the slot is free again, this call copies the chunk itself
+		}
+		if (from) {
+			HIPCHECK(c, hipStreamWaitEvent(st, from->up, 0));
+			HIPCHECK(c, hipMemcpyAsync(tx + d.carry, from->buf.p, bytes, hipMemcpyDeviceToDevice, st));
+			HIPCHECK(c, hipEventRecord(from->done, st));
+			from->read = true; from->host = nullptr;
+		} else HIPCHECK(c, hipMemcpyAsync(tx + d.carry, text, bytes, mem == SSV_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+	}
+	d.text_bytes = total;
+	if (total == 0) {
+		HIPCHECK(c, hipStreamSynchronize(st));
+		d.info.carried_bytes = 0;
+		if (last) d.phase = ssv_samdec_state::ENDED;
+		d.have_batch = true;
+		return SSV_OK;
+	}
+	// a last line without its newline gets one (the kernels count it unless a newline stands in front of it)
+	const int64_t len = (int64_t)total + (last ? 1 : 0), virt_at = last ? (int64_t)total : -1;
+	if (last) HIPCHECK(c, hipMemsetAsync(tx + total, '\n', 1, st));
+	const int64_t n_tiles = (len + ssv::SAM_TILE - 1) / ssv::SAM_TILE;
+	CHECK(ensure(c, d.tile_sep, (size_t)n_tiles * 4 + 16)); CHECK(ensure(c, d.tile_nl, (size_t)n_tiles * 4 + 16));
+	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n_tiles) * 8 + 64));
+	// d.small: [0..1] the smallest refused (line << 8 | reason) u64, [2] separators, [3] lines, [4] CIGAR operations, [6..7] seqqual bytes u64, [8] max span i32
+	uint32_t *sm = P<uint32_t>(d.small);
+	unsigned long long *errw = P<unsigned long long>(d.small);
+	HIPCHECK(c, hipMemsetAsync(d.small.p, 0, 256, st));
+	HIPCHECK(c, hipMemsetAsync(d.small.p, 0xff, 8, st));
+	k_sam_count<<<(unsigned)n_tiles, BLOCK, 0, st>>>(tx, len, virt_at, P<uint32_t>(d.tile_sep), P<uint32_t>(d.tile_nl));
+	HIPCHECK(c, hipGetLastError());
+	exclusive_scan<uint32_t, uint32_t>(st, P<uint32_t>(d.tile_sep), P<uint32_t>(d.tile_sep), n_tiles, 0u, P<uint32_t>(c->scan_scratch), sm + 2);
+	exclusive_scan<uint32_t, uint32_t>(st, P<uint32_t>(d.tile_nl), P<uint32_t>(d.tile_nl), n_tiles, 0u, P<uint32_t>(c->scan_scratch), sm + 3);
+	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
+	HIPCHECK(c, hipStreamSynchronize(st));
+	const uint32_t *hs = P<uint32_t>(d.h_small);
+	const uint32_t n_sep = hs[2];
+	const int64_t n = hs[3];
+	if (n == 0) { // not one finished line: everything is carried
+		CHECK(ensure(c, d.carrybuf, (size_t)total + 64));
+		HIPCHECK(c, hipMemcpyAsync(d.carrybuf.p, tx, total, hipMemcpyDeviceToDevice, st));
+		HIPCHECK(c, hipStreamSynchronize(st));
+		d.carry = total; d.info.carried_bytes = total;
+		d.have_batch = true;
+		return SSV_OK;
+	}
+	const size_t N = (size_t)n;
+	CHECK(ensure(c, d.sep, (size_t)n_sep * 4 + 16)); CHECK(ensure(c, d.nlidx, N * 4 + 16));
+	CHECK(ensure(c, d.tid, N * 4 + 16)); CHECK(ensure(c, d.pos, N * 4 + 16)); CHECK(ensure(c, d.l_qseq, N * 4 + 16)); CHECK(ensure(c, d.mtid, N * 4 + 16)); CHECK(ensure(c, d.mpos, N * 4 + 16));
+	CHECK(ensure(c, d.isize, N * 4 + 16)); CHECK(ensure(c, d.flag, N * 2 + 16)); CHECK(ensure(c, d.n_cigar, N * 2 + 16)); CHECK(ensure(c, d.mapq, N + 16)); CHECK(ensure(c, d.xc, N + 16));
+	CHECK(ensure(c, d.ends, N + 16)); CHECK(ensure(c, d.seq_bytes, N * 4 + 16)); CHECK(ensure(c, d.cigar_off, N * 4 + 16)); CHECK(ensure(c, d.seq_off, N * 8 + 16));
+	CHECK(ensure(c, d.name_off, N * 8 + 16)); CHECK(ensure(c, d.rec, N * sizeof(ssv_record) + 64));
+	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n) * 8 + 64)); CHECK(ensure(c, c->scan_scratch64, (size_t)scan_scratch_elems(n) * 8 + 64));
+	ssv::SamColumns col;
+	col.tid = P<int32_t>(d.tid); col.pos = P<int32_t>(d.pos); col.l_qseq = P<int32_t>(d.l_qseq); col.mtid = P<int32_t>(d.mtid); col.mpos = P<int32_t>(d.mpos); col.isize = P<int32_t>(d.isize);
+	col.flag = P<uint16_t>(d.flag); col.n_cigar = P<uint16_t>(d.n_cigar); col.mapq = P<uint8_t>(d.mapq); col.xc = P<uint8_t>(d.xc); col.ends = P<uint8_t>(d.ends);
+	col.seq_bytes = P<uint32_t>(d.seq_bytes); col.cigar_off = P<uint32_t>(d.cigar_off); col.seq_off = P<uint64_t>(d.seq_off); col.name_off = P<uint64_t>(d.name_off);
+	col.rec = P<ssv_record>(d.rec); col.cigar = nullptr;
+	k_sam_marks<<<(unsigned)n_tiles, BLOCK, 0, st>>>(tx, len, virt_at, P<uint32_t>(d.tile_sep), P<uint32_t>(d.tile_nl), (uint32_t)n, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), errw);
+	k_sam_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col, errw);
+	HIPCHECK(c, hipGetLastError());
+	exclusive_scan<uint16_t, uint32_t>(st, P<uint16_t>(d.n_cigar), P<uint32_t>(d.cigar_off), n, 0u, P<uint32_t>(c->scan_scratch), sm + 4);
+	exclusive_scan<uint32_t, uint64_t>(st, P<uint32_t>(d.seq_bytes), P<uint64_t>(d.seq_off), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 6));
+	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
+	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 16, P<uint32_t>(d.nlidx) + (n - 1), 4, hipMemcpyDeviceToHost, st));
+	HIPCHECK(c, hipStreamSynchronize(st));
+	// (a line k_sam_sizes refused has sizes of zero: the kernels below still run, so that the FIRST refused line is named whichever kernel refuses it)
+	unsigned long long werr;
+	const uint32_t cigar_total = hs[4], last_nl_sep = hs[16];
+	uint64_t seq_total;
+	memcpy(&seq_total, hs + 6, 8);
+	CHECK(ensure(c, d.cigar, (size_t)cigar_total * 4 + 64)); CHECK(ensure(c, d.seqqual, (size_t)seq_total + 64));
+	col.cigar = P<uint32_t>(d.cigar);
+	ssv::SamRefTable T{P<uint32_t>(d.ref_slots), d.ref_mask, P<uint32_t>(d.ref_off), P<uint8_t>(d.ref_blob)};
+	// where the last finished line ends (k_sam_fields puts NULs over the first tabs of finished lines only: the unfinished one is carried as it is)
+	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 17, P<uint32_t>(d.sep) + last_nl_sep, 4, hipMemcpyDeviceToHost, st));
+	k_sam_fields<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, reinterpret_cast<int32_t *>(sm + 8), errw);
+	k_sam_seqqual<<<(unsigned)std::min<int64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, P<int32_t>(d.l_qseq),
+	                                                                                                                 P<uint64_t>(d.seq_off), P<uint8_t>(d.seqqual), errw);
+	HIPCHECK(c, hipGetLastError());
+	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
+	HIPCHECK(c, hipStreamSynchronize(st));
+	memcpy(&werr, d.h_small.p, 8);
+	if (werr != ssv::SAM_NO_ERROR) return samdec_refuse(c, werr);
+	// the unfinished last line: kept aside, moved in front of the next chunk's bytes by the next decode
+	const uint64_t consumed = last ? total : (uint64_t)hs[17] + 1u;
+	const uint64_t carry = total - consumed;
+	if (carry) {
+		CHECK(ensure(c, d.carrybuf, (size_t)carry + 64));
+		HIPCHECK(c, hipMemcpyAsync(d.carrybuf.p, tx + consumed, carry, hipMemcpyDeviceToDevice, st));
+		HIPCHECK(c, hipStreamSynchronize(st));
+	}
+	d.carry = carry;
+	d.lines_done += (uint64_t)n;
+	d.info.n_records = n; d.info.lines_consumed = d.lines_done; d.info.carried_bytes = carry;
+	if (last) d.phase = ssv_samdec_state::ENDED;
+	d.have_batch = true;
+	out->n = n; out->max_ref_span = (int32_t)hs[8] > 0 ? (int32_t)hs[8] : 1;
+	out->tid = col.tid; out->pos = col.pos; out->flag = col.flag; out->mapq = col.mapq; out->n_cigar = col.n_cigar; out->l_qseq = col.l_qseq; out->mtid = col.mtid; out->mpos = col.mpos;
+	out->isize = col.isize; out->cigar_off = col.cigar_off; out->cigar = col.cigar; out->xc = col.xc; out->seq_off = col.seq_off; out->seqqual = P<uint8_t>(d.seqqual);
+	out->n_cigar_total = (int64_t)cigar_total; out->seqqual_bytes = (int64_t)seq_total;
+	out->rec = col.rec; out->cigar_ends = col.ends;
+	out->tid_runs = nullptr; out->n_tid_runs = 0;
+	return SSV_OK;
+}
+
+int ssv_samdec_names(ssv_ctx *c, ssv_names_t *out)
+{
+	if (!c || !out) return SSV_E_ARG;
+	if (!c->sd || !c->sd->have_batch) { c->err = "ssv_samdec_names before a successful ssv_samdec_decode"; return SSV_E_STATE; }
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_DEVICE; out->bias = 0;
+	out->base = P<char>(c->sd->text); out->off = P<uint64_t>(c->sd->name_off); out->bytes = (int64_t)c->sd->text_bytes;
+	return SSV_OK;
+}
+
+int ssv_samdec_last(ssv_ctx *c, ssv_samdec_info *info)
+{
+	if (!c || !info) return SSV_E_ARG;
+	if (!c->sd || c->sd->phase == ssv_samdec_state::IDLE) { c->err = "ssv_samdec_last before ssv_samdec_begin"; return SSV_E_STATE; }
+	*info = c->sd->info;
+	return SSV_OK;
+}

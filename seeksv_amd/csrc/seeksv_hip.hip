@@ -37,6 +37,7 @@
 #include "getsv_kernels.h"
 #include "radix_sort.h"
 #include "readthrough_kernels.h"
+#include "samdec_kernels.h"
 #include "scan.h"
 
 using namespace ssv;
@@ -164,6 +165,7 @@ struct ssv_getsv_state;  // getsv_api.inc
 struct ssv_bamdec_state; // bamdec_api.inc
 struct ssv_realign_state; // realign_api.inc
 struct ssv_rt_state;     // readthrough_api.inc
+struct ssv_samdec_state; // samdec_api.inc
 
 struct ssv_ctx { // (created and deleted below the stage files only: the state structs are complete there)
 	int device = 0;
@@ -211,6 +213,7 @@ struct ssv_ctx { // (created and deleted below the stage files only: the state s
 	std::unique_ptr<ssv_bamdec_state> bd;
 	std::unique_ptr<ssv_realign_state> ra;
 	std::unique_ptr<ssv_rt_state> rt;
+	std::unique_ptr<ssv_samdec_state> sd;
 
 	// ---- profiling ----
 	int prof_mode = 0;
@@ -926,6 +929,7 @@ const char *ssv_prof_names(void) { return kProfNameList; }
 #include "bamdec_api.inc"
 #include "realign_api.inc"
 #include "readthrough_api.inc"
+#include "samdec_api.inc"
 #include "group_api.inc"
 
 
@@ -939,6 +943,7 @@ void ssv_ctx_destroy(ssv_ctx *c)
 
 	for (auto &t : c->clip->tab) if (t.in_flight && t.via_link) { table_link_wait(c, t); t.in_flight = false; } // (a table still on its way out)
 	bamdec_release_handles(c);
+	samdec_release_handles(c);
 	if (c->st_h2d) { (void)hipStreamSynchronize(c->st_h2d); (void)hipStreamDestroy(c->st_h2d); }
 	for (auto &a : c->arenas) if (a.base) (void)hipFree(a.base);
 	for (auto &a : c->spare_arenas) (void)hipFree(a.base);

@@ -192,6 +192,42 @@ class Context:
             d["unmapped"] = unm
             yield b, d
 
+    # ---- device-side SAM text decode (getsv -F on `bwa bwasw` output) ----
+    def samdec_begin(self, target_names, first_line=1):
+        """ssv_samdec_begin: a new SAM text file whose header names these contigs; first_line: the file's line number of the first record line"""
+        arr = (C.c_char_p * max(1, len(target_names)))(*[x.encode() if isinstance(x, str) else x for x in target_names])
+        p = _abi.SamdecParams(len(target_names), 0, arr, int(first_line))
+        self._check(self._lib.ssv_samdec_begin(self._h, C.byref(p)), "ssv_samdec_begin")
+
+    def samdec_decode(self, text, last=False):
+        """ssv_samdec_decode: the next bytes of the file (bytes, cut anywhere) -> Batch (SSV_MEM_DEVICE, valid until the next decode)"""
+        b = _abi.Batch()
+        buf = C.create_string_buffer(text, len(text)) if len(text) else None
+        self._check(self._lib.ssv_samdec_decode(self._h, buf, len(text), _abi.MEM_HOST, int(bool(last)), C.byref(b)), "ssv_samdec_decode")
+        return b
+
+    def samdec_names(self):
+        """ssv_samdec_names: where the read names of the batch decoded last lie in HBM (valid as long as that batch)"""
+        n = _abi.Names()
+        self._check(self._lib.ssv_samdec_names(self._h, C.byref(n)), "ssv_samdec_names")
+        return n
+
+    def samdec_last(self):
+        info = _abi.SamdecInfo()
+        self._check(self._lib.ssv_samdec_last(self._h, C.byref(info)), "ssv_samdec_last")
+        return dict(n_records=info.n_records, lines_consumed=info.lines_consumed, carried_bytes=info.carried_bytes, refused_line=info.refused_line,
+                    refused_reason=info.refused_reason.decode() if info.refused_reason else None)
+
+    def sam_batches(self, text, target_names, first_line=1, chunk_bytes=64 << 20, cuts=None):
+        """Generator over the SSV_MEM_DEVICE batches of SAM record text (bytes, the file behind its header) decoded on the GPU: yields (Batch, Names).
+        The text is handed over in chunks of chunk_bytes, or cut at the byte offsets `cuts`; both are valid until the next iteration."""
+        self.samdec_begin(target_names, first_line)
+        bounds = sorted(set(cuts)) if cuts is not None else list(range(chunk_bytes, len(text), chunk_bytes))
+        bounds = [0] + [x for x in bounds if 0 < x < len(text)] + [len(text)]
+        for k in range(len(bounds) - 1):
+            b = self.samdec_decode(text[bounds[k]:bounds[k + 1]], last=k == len(bounds) - 2)
+            yield b, self.samdec_names()
+
     def batch_retain(self, dev_batch):
         """a device batch (the decoder's: valid until the next decode) copied into device memory of its own; -> Batch (SSV_MEM_DEVICE |
         SSV_MEM_PERSISTENT), to be given back with batch_release"""

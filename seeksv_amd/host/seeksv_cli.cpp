@@ -41,6 +41,7 @@
 
 #include "junction_stage.h"
 #include "readthrough_stage.h"
+#include "sam_text.h"
 #include "somatic_stage.h"
 #include "unmapped_pairs.h"
 #include "../csrc/thp.h"
@@ -127,7 +128,8 @@ static void release_ctx(ssv_ctx *ctx);
 [[noreturn]] static void usage_getsv()
 {
 	cerr << "Usage: seeksv getsv [options] <input clipped sequence bam> <input orignal sorted bam> <soft-clipped reads file(*clip.gz)> <output SVs> <output unmaped clipped sequence fastq>\n"
-	     << "Options: -F <FILE>             BAM of connected read-through reads (split alignments, e.g. bwa bwasw): their junctions are evaluated in addition\n"
+	     << "Options: -F <FILE>             Samfile/Bamfile of connected read-through reads (split alignments, e.g. bwa bwasw): their junctions are evaluated in addition;\n"
+	     << "                               a name ending in .bam is BAM, every other name SAM text (plain or gzip), which is parsed on the GPU\n"
 	     << "         -w <int>              Minimum mapping quality of the -F reads [1]\n"
 	     << "         -B <FILE>             junction table (23 columns, as written by getsv) to evaluate in addition\n"
 	     << "         -l <int>              Maximum search length to find microhomology [50]\n"
@@ -1225,19 +1227,14 @@ static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const st
 
 static void resident_alignments(seeksv::AlnRecords &R); // `seeksv run`: the aligner step's records as the join reads them
 
-// getsv -F: FindJunction (process_bwasw.cpp:5-227).  The file goes through the same readers as the original BAM (host threads, or the GPU with -Z);
-// selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
-static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, bool device_inflate, JunctionMap &junction2other)
+// getsv -F: FindJunction (process_bwasw.cpp:5-227).  A name that ends in ".bam" is BAM, every other name SAM text (the reference's rule, process_bwasw.cpp:12-16).
+// A BAM goes through the same readers as the original BAM (host threads, or the GPU with -Z); SAM text is always parsed on the GPU (ssv_samdec_*), whatever -Z
+// says.  Selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
+static const char *kRtOpenError = "[main_samview] fail to open file for reading.";
+
+static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx)
 {
-	static const char *kOpenError = "[main_samview] fail to open file for reading.";
-	// a name without ".bam" is SAM text to the reference (samopen mode "r"): this build reads BAM only
-	if (path.size() < 4 || path.rfind(".bam") != path.size() - 4) die(kOpenError);
-	ssvh_bam *hdr = nullptr;
-	if (ssvh_bam_open(path.c_str(), &hdr) != 0) die(kOpenError);
-	const int32_t nt = ssvh_bam_n_targets(hdr);
-	vector<string> names((size_t)nt);
-	for (int32_t t = 0; t < nt; ++t) { const char *z = ssvh_bam_target_name(hdr, t); names[(size_t)t] = z ? z : ""; }
-	ssvh_bam_close(hdr);
+	const int32_t nt = (int32_t)names.size();
 	// contigs in byte-wise name order: the device compares (rank, pos) where the reference compares make_pair(chr, pos)
 	vector<int32_t> order((size_t)nt), rank((size_t)nt);
 	for (int32_t t = 0; t < nt; ++t) order[(size_t)t] = t;
@@ -1247,19 +1244,83 @@ static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, boo
 	memset(&rp, 0, sizeof(rp));
 	rp.min_mapq = min_mapq; rp.n_targets = nt; rp.name_rank = rank.data();
 	if (ssv_rt_begin(ctx, &rp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-	BatchSource src;
-	src.allow_resident = false;
-	src.any_order = true; // (a bwasw file is in read order, not coordinate order)
-	src.open(path, ctx, device_inflate, kOpenError);
-	if (!src.on_device && ssvh_bam_keep_names(src.bam, 1) != 0) die(string("[seeksv] ") + ssvh_last_error());
-	ssv_batch_t b;
-	while (src.next(&b, 1)) { // (every record's bases: the 3'-branch records without S are kept too)
-		ssv_names_t nm;
-		const int rc = src.on_device ? ssv_bamdec_names(ctx, &nm) : (ssvh_bam_batch_names(src.bam, &nm) == 0 ? SSV_OK : SSV_E_ARG);
-		if (rc != SSV_OK) die(string("[seeksv] ") + (src.on_device ? ssv_last_error(ctx) : ssvh_last_error()));
-		if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+}
+
+static void *sam_stage_alloc(size_t bytes) { void *p = nullptr; return ssv_host_alloc(bytes, &p) == SSV_OK ? p : nullptr; }
+static void sam_stage_free(void *p) { ssv_host_free(p); }
+
+// the -F file as SAM text: the header on the host, the records' text to the GPU as it is, in chunks cut anywhere (SSV_SAM_CHUNK_KB: their size, 256 MB by
+// default); a reader thread fills page-locked buffers ahead, and chunk k + 1 crosses the host link under chunk k's kernels (ssv_samdec_prefetch)
+static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
+{
+	seeksv::SamTextReader rd;
+	string err;
+	if (!rd.open(path, err)) die(kRtOpenError);
+	names = rd.target_names();
+	if (names.empty()) { // (the reference goes on and aborts at its first record: "[sam_read1] missing header? Abort!")
+		cerr << "[samopen] no @SQ lines in the header." << endl;
+		die(kRtOpenError);
 	}
-	src.close();
+	cerr << "[samopen] SAM header is present: " << names.size() << " sequences." << endl;
+	rt_begin_for(names, min_mapq, ctx);
+	vector<const char *> cnames;
+	for (const string &s : names) cnames.push_back(s.c_str());
+	ssv_samdec_params sp;
+	memset(&sp, 0, sizeof(sp));
+	sp.n_targets = (int32_t)names.size(); sp.target_names = cnames.data(); sp.first_line = rd.first_record_line();
+	if (ssv_samdec_begin(ctx, &sp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	const char *e = getenv("SSV_SAM_CHUNK_KB");
+	const size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) << 10 : (size_t)256 << 20;
+	rd.start(chunk, sam_stage_alloc, sam_stage_free);
+	seeksv::SamTextReader::Chunk ck, nx;
+	bool ended = false;
+	ssv_batch_t b;
+	auto decode = [&](const void *text, size_t bytes, int last) {
+		if (ssv_samdec_decode(ctx, text, bytes, SSV_MEM_HOST, last, &b) != SSV_OK) {
+			const string m = ssv_last_error(ctx);
+			die(m.compare(0, 11, "Parse error") == 0 ? m : "[seeksv] " + m);
+		}
+		ssv_names_t nm;
+		if (ssv_samdec_names(ctx, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		if (b.n && ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	};
+	while (rd.next(ck, err)) {
+		if (!ck.last && rd.ready_behind(nx) && ssv_samdec_prefetch(ctx, nx.data, nx.bytes) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		decode(ck.data, ck.bytes, ck.last ? 1 : 0);
+		ended = ck.last;
+	}
+	if (!err.empty()) die(err);
+	if (!ended) decode(nullptr, 0, 1);
+	if (ssv_sync(ctx) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); // (the staging buffers go with the reader)
+	rd.close();
+}
+
+static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, bool device_inflate, JunctionMap &junction2other)
+{
+	vector<string> names;
+	if (path.size() < 4 || path.rfind(".bam") != path.size() - 4) readthrough_pass_sam(path, min_mapq, ctx, names);
+	else {
+		ssvh_bam *hdr = nullptr;
+		if (ssvh_bam_open(path.c_str(), &hdr) != 0) die(kRtOpenError);
+		const int32_t nt = ssvh_bam_n_targets(hdr);
+		names.resize((size_t)nt);
+		for (int32_t t = 0; t < nt; ++t) { const char *z = ssvh_bam_target_name(hdr, t); names[(size_t)t] = z ? z : ""; }
+		ssvh_bam_close(hdr);
+		rt_begin_for(names, min_mapq, ctx);
+		BatchSource src;
+		src.allow_resident = false;
+		src.any_order = true; // (a bwasw file is in read order, not coordinate order)
+		src.open(path, ctx, device_inflate, kRtOpenError);
+		if (!src.on_device && ssvh_bam_keep_names(src.bam, 1) != 0) die(string("[seeksv] ") + ssvh_last_error());
+		ssv_batch_t b;
+		while (src.next(&b, 1)) { // (every record's bases: the 3'-branch records without S are kept too)
+			ssv_names_t nm;
+			const int rc = src.on_device ? ssv_bamdec_names(ctx, &nm) : (ssvh_bam_batch_names(src.bam, &nm) == 0 ? SSV_OK : SSV_E_ARG);
+			if (rc != SSV_OK) die(string("[seeksv] ") + (src.on_device ? ssv_last_error(ctx) : ssvh_last_error()));
+			if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		}
+		src.close();
+	}
 	ssv_rt_result res;
 	if (ssv_rt_finish(ctx, &res) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 	seeksv::apply_readthrough(res, names, junction2other);
