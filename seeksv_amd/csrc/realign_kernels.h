@@ -111,13 +111,15 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 // orientations, probes the table and records the diagonals (reference position of query base 0) of verified seeds.  3. duplicates
 // out (a matching stretch of m bases yields ~(m - K) / SAMPLE seeds on one diagonal).  4. one lane per distinct diagonal scores the
 // whole query along it: best local segment under +1 / -4, extended to an end of the query when that loses less than the clipping
-// penalty (bwa mem's rule).  5. best and second best locus -> hit.
+// penalty (bwa mem's rule); every candidate's score stays in LDS.  5. best locus over the lanes, then the runner-up over ALL scored
+// candidates (a lane scores one candidate per round of 64 and keeps only its best: the lanes' bests alone would miss a runner-up
+// that the winner's lane scored in another round, and a sequence present twice would come back with MAPQ 60) -> hit.
 __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 {
 	__shared__ uint8_t s_code[WAVES_PER_BLOCK][2][RA_MAX_Q];
 	__shared__ int64_t s_diag[WAVES_PER_BLOCK][RA_MAX_CAND];
-	__shared__ uint16_t s_so[WAVES_PER_BLOCK][RA_MAX_CAND]; // seed offset in the query | strand << 15
-	__shared__ uint16_t s_tid[WAVES_PER_BLOCK][RA_MAX_CAND]; // contig of the seed (a query can hang over a contig's end: same diagonal, two contigs)
+	__shared__ uint16_t s_ss[WAVES_PER_BLOCK][RA_MAX_CAND]; // strand << 15 | score of the candidate (<= RA_MAX_Q; 0 until it is scored: a duplicate, or not reported)
+	__shared__ int32_t s_tid[WAVES_PER_BLOCK][RA_MAX_CAND]; // contig of the seed (a query can hang over a contig's end: same diagonal, two contigs); n_targets is an int32
 	__shared__ int s_n[WAVES_PER_BLOCK];
 	const int w = wave_id(), lane = lane_id();
 	const int64_t q = (int64_t)blockIdx.x * WAVES_PER_BLOCK + w;
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 				const int64_t p = (int64_t)(v - 1u) * RA_SAMPLE;
 				if (ra_kmer_at(ix.ref, p) == km) {
 					const int at = atomicAdd(&s_n[w], 1);
-					if (at < RA_MAX_CAND) { s_diag[w][at] = p - o; s_so[w][at] = (uint16_t)(o | (st << 15)); s_tid[w][at] = (uint16_t)ra_contig_of(ix, p); }
+					if (at < RA_MAX_CAND) { s_diag[w][at] = p - o; s_ss[w][at] = (uint16_t)(st << 15); s_tid[w][at] = ra_contig_of(ix, p); }
 				}
 				slot = (slot + 1) & ix.mask;
 			}
@@ -169,8 +171,8 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 		int64_t d = 0;
 		int st = 0, t = 0;
 		if (mine) {
-			d = s_diag[w][c]; st = s_so[w][c] >> 15; t = s_tid[w][c];
-			for (int e = 0; e < c; ++e) if (s_diag[w][e] == d && (s_so[w][e] >> 15) == st && s_tid[w][e] == t) { mine = false; break; }
+			d = s_diag[w][c]; st = s_ss[w][c] >> 15; t = s_tid[w][c];
+			for (int e = 0; e < c; ++e) if (s_diag[w][e] == d && (s_ss[w][e] >> 15) == st && s_tid[w][e] == t) { mine = false; break; }
 		}
 		if (!mine) continue;
 		const uint8_t *code = s_code[w][st];
@@ -200,12 +202,13 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 				if (sc > -RA_CLIP) { bs += sc; be = n; }
 			}
 		}
+		s_ss[w][c] = (uint16_t)((st << 15) | bs);
 		int mm = 0;
 		for (int i = bb; i < be; ++i) mm += (code[i] < 4 && (uint32_t)code[i] == ra_base_at(ix.ref, d + i)) ? 0 : 1;
 		const bool better = bs > best_score || (bs == best_score && best_tid >= 0 && (st < best_st || (st == best_st && d < best_diag)));
 		if (better) { best_score = bs; best_beg = bb; best_end = be; best_mm = mm; best_st = st; best_diag = d; best_tid = t; }
 	}
-	// ---- best locus over the lanes; second best = best score among diagonals that are not the winner's neighbourhood ----
+	// ---- best locus over the lanes; second best = best score among all candidates that are not the winner's neighbourhood ----
 	int win_score = best_score, win_lane = lane;
 	int64_t win_diag = best_diag;
 	int win_st = best_st;
@@ -218,8 +221,15 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 	}
 	if (win_score < RA_MIN_SCORE) { if (lane == 0) a.hits[q] = out; return; }
 	const int win_tid = __shfl(best_tid, win_lane, 64);
-	const bool same_locus = best_score > 0 && best_st == win_st && best_tid == win_tid && (best_diag - win_diag <= 32 && win_diag - best_diag <= 32);
-	int second = (best_score > 0 && !same_locus) ? best_score : 0;
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	int second = 0;
+	for (int c = lane; c < m; c += WAVE) {
+		const int sc = s_ss[w][c] & 0x7fff;
+		const int64_t d = s_diag[w][c];
+		const bool same_locus = (s_ss[w][c] >> 15) == win_st && s_tid[w][c] == win_tid && (d - win_diag <= 32 && win_diag - d <= 32);
+		if (sc > second && !same_locus) second = sc;
+	}
 	second = wave_max(second);
 	if (lane == win_lane) {
 		out.tid = best_tid;
