@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
+                             v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
                              v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
                              v9: ssv_table_block_bytes(left_len, right_len) lost the parameters of the removed formats; ssv_bamdec_info.unmapped_raw stays valid for one more decode.
                              v8: table formats 1 and 2 (four-piece blocks with 4-bit bases) removed - 0 ASCII or 3 compact; ssv_group with SSV_GROUP_RCCL_ONE */
@@ -540,6 +541,25 @@ int ssv_samdec_decode(ssv_ctx *ctx, const void *text, size_t bytes, int mem, int
  * off[i] = where line i starts.  Valid as long as that batch. */
 int ssv_samdec_names(ssv_ctx *ctx, ssv_names_t *out);
 int ssv_samdec_last(ssv_ctx *ctx, ssv_samdec_info *info);
+
+/* ---- the clipped-sequence re-alignments of `getsv` out of a decoded batch (getsv.h:437-446 opens every name without ".bam" as SAM text) ----
+ * What the host join (InputSoftInfoStoreBreakpoint + GetAlignInfo, getsv.h:423-541, getsv.cpp:25-71) reads of every record of clip.bam / clip.sam: tid, pos, flag,
+ * mapq, the CIGAR, the read name - which is the clipped sequence itself - and a 64-bit hash of that name, the join's first compare.  ssv_aln_pack takes a batch
+ * (SSV_MEM_DEVICE: ssv_samdec_decode's or ssv_bamdec_decode's, used in place; SSV_MEM_HOST: staged like any scan call's) and its names (ssv_names_t, as ssv_rt_scan
+ * takes them: device names in place, host names copied, `bias` added) and hands these columns out in page-locked HOST memory owned by the context, valid until
+ * the next ssv_aln_pack on it: the names packed back to back in record order on the GPU and hashed there over their bytes without the NUL -
+ *   h = 0x9E3779B97F4A7C15 ^ n;  per little-endian 8-byte word w (the tail zero padded): h = (h ^ w) * 0xFF51AFD7ED558CCD, h ^= h >> 29;  result h * 0xC4CEB9FE1A85EC53
+ * (libseeksv_host's clip_text_hash).  cigar_off[i] indexes this call's cigar[], which holds the batch's n_cigar_total operations.  n == 0 is a valid call (empty
+ * columns).  A name is at most 254 bytes without its NUL.  Synchronises the stream.  Its rate has not been measured. */
+typedef struct {
+	int64_t n, n_cigar_total, name_bytes;
+	const int32_t *tid, *pos; const uint16_t *flag, *n_cigar; const uint8_t *mapq;
+	const uint32_t *cigar_off, *cigar;   /* cigar_off relative to this call's cigar[] */
+	const uint64_t *name_off;            /* record i's name: names + name_off[i], NUL-terminated, names packed back to back in record order */
+	const char *names;
+	const uint64_t *name_hash;
+} ssv_aln_cols;
+int ssv_aln_pack(ssv_ctx *ctx, const ssv_batch_t *b, const ssv_names_t *names, ssv_aln_cols *out);
 
 /* Copy a device batch into host arrays owned by the context (valid until the next call): tests and debugging. */
 int ssv_batch_to_host(ssv_ctx *ctx, const ssv_batch_t *device_batch, ssv_batch_t *host_batch);

@@ -161,6 +161,13 @@ class Names(C.Structure):
     _fields_ = [("mem", C.c_int32), ("pad", C.c_int32), ("bias", C.c_int64), ("base", C.c_void_p), ("off", C.c_void_p), ("bytes", C.c_int64)]
 
 
+class AlnCols(C.Structure):
+    """ssv_aln_cols (include/seeksv_hip.h): what the host join reads of the clipped-sequence re-alignments; page-locked host memory of the context"""
+    _fields_ = [("n", C.c_int64), ("n_cigar_total", C.c_int64), ("name_bytes", C.c_int64), ("tid", C.c_void_p), ("pos", C.c_void_p), ("flag", C.c_void_p),
+                ("n_cigar", C.c_void_p), ("mapq", C.c_void_p), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p), ("name_off", C.c_void_p), ("names", C.c_void_p),
+                ("name_hash", C.c_void_p)]
+
+
 class RtParams(C.Structure):
     _fields_ = [("min_mapq", C.c_int32), ("n_targets", C.c_int32), ("name_rank", C.POINTER(C.c_int32))]
 
@@ -384,5 +391,6 @@ def hip_lib():
         lib.ssv_samdec_decode.argtypes = [V, V, C.c_size_t, C.c_int, C.c_int, C.POINTER(Batch)]
         lib.ssv_samdec_names.argtypes = [V, C.POINTER(Names)]
         lib.ssv_samdec_last.argtypes = [V, C.POINTER(SamdecInfo)]
+        lib.ssv_aln_pack.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(AlnCols)]
         lib._typed = True
     return lib

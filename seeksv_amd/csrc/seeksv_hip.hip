@@ -38,6 +38,7 @@
 #include "radix_sort.h"
 #include "readthrough_kernels.h"
 #include "samdec_kernels.h"
+#include "alnpack_kernels.h"
 #include "scan.h"
 
 using namespace ssv;
@@ -166,6 +167,7 @@ struct ssv_bamdec_state; // bamdec_api.inc
 struct ssv_realign_state; // realign_api.inc
 struct ssv_rt_state;     // readthrough_api.inc
 struct ssv_samdec_state; // samdec_api.inc
+struct ssv_alnpack_state; // alnpack_api.inc
 
 struct ssv_ctx { // (created and deleted below the stage files only: the state structs are complete there)
 	int device = 0;
@@ -214,6 +216,7 @@ struct ssv_ctx { // (created and deleted below the stage files only: the state s
 	std::unique_ptr<ssv_realign_state> ra;
 	std::unique_ptr<ssv_rt_state> rt;
 	std::unique_ptr<ssv_samdec_state> sd;
+	std::unique_ptr<ssv_alnpack_state> ap;
 
 	// ---- profiling ----
 	int prof_mode = 0;
@@ -930,6 +933,7 @@ const char *ssv_prof_names(void) { return kProfNameList; }
 #include "realign_api.inc"
 #include "readthrough_api.inc"
 #include "samdec_api.inc"
+#include "alnpack_api.inc"
 #include "group_api.inc"
 
 

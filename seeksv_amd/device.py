@@ -65,6 +65,18 @@ class Context:
             return b, None
         return _abi.make_batch(b)
 
+    @staticmethod
+    def _as_names(names):
+        """an _abi.Names as it is, or one over host memory for a list of names (str or bytes); -> (Names, keepalive)"""
+        if isinstance(names, _abi.Names):
+            return names, None
+        raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        blob = b"".join(x + b"\0" for x in raw)
+        off = np.zeros(len(raw) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) + 1 for x in raw])
+        buf = C.create_string_buffer(blob, len(blob) + 1)
+        return _abi.Names(_abi.MEM_HOST, 0, 0, C.cast(buf, C.c_void_p), off.ctypes.data, len(blob)), (buf, off)
+
     # ---- getsv -F: junctions from read-through split alignments (ssv_rt_*) ----
     def readthrough(self, batches, names, min_mapq=1, target_names=(), raw=False):
         """FindJunction (process_bwasw.cpp:5-227) over host batches in file order.  batches: dicts of arrays (or _abi.Batch) that carry every kept
@@ -91,14 +103,7 @@ class Context:
         """ssv_rt_scan: the next batch in file order.  names: the batch's read names (list of str), or an _abi.Names that says where they lie -
         bamdec_names() for a batch of the device decoder"""
         bb, keep = self._as_batch(batch)
-        if isinstance(names, _abi.Names):
-            n = names
-        else:
-            blob = b"".join(x.encode() + b"\0" for x in names)
-            off = np.zeros(len(names) + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(x.encode()) + 1 for x in names])
-            buf = C.create_string_buffer(blob, len(blob) + 1)
-            n = _abi.Names(_abi.MEM_HOST, 0, 0, C.cast(buf, C.c_void_p), off.ctypes.data, len(blob))
+        n, keep_names = self._as_names(names)
         self._check(self._lib.ssv_rt_scan(self._h, C.byref(bb), C.byref(n)), "ssv_rt_scan")
 
     def rt_finish(self):
@@ -227,6 +232,29 @@ class Context:
         for k in range(len(bounds) - 1):
             b = self.samdec_decode(text[bounds[k]:bounds[k + 1]], last=k == len(bounds) - 2)
             yield b, self.samdec_names()
+
+    # ---- getsv: the clipped-sequence re-alignments as the host join reads them (ssv_aln_pack) ----
+    def aln_pack(self, batch, names):
+        """ssv_aln_pack: a batch (dict of host arrays, or an _abi.Batch - a decoder's device batch) and its read names (list of str / bytes, or an _abi.Names:
+        samdec_names() / bamdec_names()) -> dict of numpy copies of the join's columns (tid, pos, flag, n_cigar, mapq, cigar_off, cigar, name_off, name_hash,
+        names_blob: the names back to back with their NULs, name_bytes) plus `names`, the list of names (bytes)"""
+        bb, keep = self._as_batch(batch)
+        n, keep_names = self._as_names(names)
+        c = _abi.AlnCols()
+        self._check(self._lib.ssv_aln_pack(self._h, C.byref(bb), C.byref(n), C.byref(c)), "ssv_aln_pack")
+
+        def col(ptr, dt, cnt):
+            if not cnt:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer((C.c_uint8 * (cnt * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt, count=cnt).copy()
+
+        out = dict(n=int(c.n), name_bytes=int(c.name_bytes), tid=col(c.tid, np.int32, c.n), pos=col(c.pos, np.int32, c.n), flag=col(c.flag, np.uint16, c.n),
+                   n_cigar=col(c.n_cigar, np.uint16, c.n), mapq=col(c.mapq, np.uint8, c.n), cigar_off=col(c.cigar_off, np.uint32, c.n),
+                   cigar=col(c.cigar, np.uint32, c.n_cigar_total), name_off=col(c.name_off, np.uint64, c.n), name_hash=col(c.name_hash, np.uint64, c.n))
+        blob = col(c.names, np.uint8, c.name_bytes).tobytes()
+        out["names_blob"] = blob
+        out["names"] = [blob[int(a):blob.index(b"\0", int(a))] for a in out["name_off"]]
+        return out
 
     def batch_retain(self, dev_batch):
         """a device batch (the decoder's: valid until the next decode) copied into device memory of its own; -> Batch (SSV_MEM_DEVICE |

@@ -66,10 +66,12 @@ struct RecSource {
 	const AlnRecords *mem = nullptr;
 	int64_t at = 0;
 	std::vector<uint64_t> qhash; // mem: text_hash of every read name (made by all threads before the join starts)
+	const uint64_t *hashes = nullptr; // ... or the ones the records came with (AlnRecords::qhash)
 	uint64_t h = 0;              // ... of the record next() handed out last
 	void hash_names()
 	{
 		if (!mem || mem->n == 0) return;
+		if (mem->qhash) { hashes = mem->qhash; return; }
 		qhash.resize((size_t)mem->n);
 		const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ssv::effective_cpus(), 64, mem->n / 65536 + 1}));
 		std::vector<std::thread> th;
@@ -77,13 +79,14 @@ struct RecSource {
 			for (int64_t i = mem->n * w / nt, e = mem->n * (w + 1) / nt; i < e; ++i) qhash[(size_t)i] = text_hash(mem->qname[i], strlen(mem->qname[i]));
 		});
 		for (auto &t : th) t.join();
+		hashes = qhash.data();
 	}
 	int next(ssvh_record *out) // 1: a record, 0: the end, < 0: error (ssvh_last_error)
 	{
 		if (bam) { const int rc = ssvh_bam_next_record(bam, out); if (rc == 1) h = text_hash(out->qname, strlen(out->qname)); return rc; }
 		if (at >= mem->n) return 0;
 		const int64_t i = at++;
-		h = qhash[(size_t)i];
+		h = hashes[(size_t)i];
 		out->tid = mem->tid[i]; out->pos = mem->pos[i]; out->flag = mem->flag[i]; out->mapq = mem->mapq[i]; out->n_cigar = mem->n_cigar[i];
 		out->cigar = mem->cigar + mem->cigar_off[i]; out->qname = mem->qname[i];
 		out->l_qseq = 0; out->seq = nullptr; out->qual = nullptr;
@@ -523,7 +526,8 @@ static std::string assemble_junctions_view(const std::vector<TextView> &texts, c
 	return "";
 }
 
-std::string assemble_junctions(const std::string &clipfile, const std::string &clip_bam, JunctionMap &j2o)
+// clip.gz read whole, then joined with clip.bam (mem == nullptr) or with alignment records in memory
+static std::string assemble_junctions_file(const std::string &clipfile, const std::string &clip_bam, const AlnRecords *mem, JunctionMap &j2o)
 {
 	const auto t0 = std::chrono::steady_clock::now();
 	static const bool serial = getenv("SSV_SERIAL") && strstr(getenv("SSV_SERIAL"), "gz"); // SSV_SERIAL=gz (tests): one inflate stream
@@ -538,8 +542,11 @@ std::string assemble_junctions(const std::string &clipfile, const std::string &c
 		view = TextView{text.data(), text.size()};
 	}
 	if (getenv("SSV_TIMING")) std::cerr << "[timing] (junction stage: " << view.size() << " bytes of rows read in " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s)" << std::endl;
-	return assemble_junctions_view(std::vector<TextView>(1, view), clip_bam, nullptr, j2o);
+	return assemble_junctions_view(std::vector<TextView>(1, view), clip_bam, mem, j2o);
 }
+
+std::string assemble_junctions(const std::string &clipfile, const std::string &clip_bam, JunctionMap &j2o) { return assemble_junctions_file(clipfile, clip_bam, nullptr, j2o); }
+std::string assemble_junctions_file_records(const std::string &clipfile, const AlnRecords &aln, JunctionMap &j2o) { return assemble_junctions_file(clipfile, "", &aln, j2o); }
 
 void merge_junctions(JunctionMap &j2o, int search_length)
 {

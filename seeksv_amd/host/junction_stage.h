@@ -75,9 +75,11 @@ struct AlnRecords {
 	const uint8_t *mapq = nullptr;
 	const uint32_t *cigar_off = nullptr, *cigar = nullptr;
 	const char *const *qname = nullptr;
+	const uint64_t *qhash = nullptr; // optional: clip_text_hash of every read name without its NUL (ssv_aln_pack computes them); null: the join hashes the names itself
 	std::vector<std::string> target_names;
 };
 std::string assemble_junctions_records(const std::vector<TextView> &clip_rows, const AlnRecords &aln, JunctionMap &junction2other);
+std::string assemble_junctions_file_records(const std::string &clipfile, const AlnRecords &aln, JunctionMap &junction2other); // ... with the rows read from clip.gz (clip alignments that came as SAM text)
 // ... and the rows as the process that wrote clip.gz kept them (views into the text it wrote, h = clip_text_hash(clipped_seq)): nothing to parse.  Only for
 // rows the text parser would split the same way - nine non-empty fields without white space (the caller checks while it writes them).
 std::string assemble_junctions_rows(const std::vector<const std::vector<ClipRow> *> &rows, const AlnRecords &aln, JunctionMap &junction2other);

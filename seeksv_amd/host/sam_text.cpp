@@ -45,16 +45,26 @@ static std::string header_field(const std::string &line, const char *tag)
 bool SamTextReader::open(const std::string &path, std::string &err)
 {
 	close();
-	fd_ = ::open(path.c_str(), O_RDONLY);
-	if (fd_ < 0) { err = "cannot open " + path; return false; }
-	unsigned char magic[2] = {0, 0};
-	const ssize_t got = pread(fd_, magic, 2, 0);
-	if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
-		const int dupfd = dup(fd_);
+	if (path == "-") {
+		// standard input: a pipe has no pread and nothing may be consumed before the format is known - zlib looks at the first two bytes itself and hands plain
+		// text through unchanged (gzread's transparent mode), so both forms go through gzread
+		const int dupfd = dup(STDIN_FILENO);
 		gzFile g = dupfd >= 0 ? gzdopen(dupfd, "rb") : nullptr;
-		if (!g) { if (dupfd >= 0) ::close(dupfd); err = "cannot open " + path; return false; }
+		if (!g) { if (dupfd >= 0) ::close(dupfd); err = "cannot open standard input"; return false; }
 		gzbuffer(g, 1u << 20);
 		gz_ = g;
+	} else {
+		fd_ = ::open(path.c_str(), O_RDONLY);
+		if (fd_ < 0) { err = "cannot open " + path; return false; }
+		unsigned char magic[2] = {0, 0};
+		const ssize_t got = pread(fd_, magic, 2, 0);
+		if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+			const int dupfd = dup(fd_);
+			gzFile g = dupfd >= 0 ? gzdopen(dupfd, "rb") : nullptr;
+			if (!g) { if (dupfd >= 0) ::close(dupfd); err = "cannot open " + path; return false; }
+			gzbuffer(g, 1u << 20);
+			gz_ = g;
+		}
 	}
 	// the header: every line up to the first one that does not begin with '@'
 	names_.clear(); lens_.clear(); pending_.clear(); pending_at_ = 0; file_off_ = 0;
@@ -84,6 +94,7 @@ bool SamTextReader::open(const std::string &path, std::string &err)
 	}
 	first_record_line_ = line_no;
 	pending_at_ = line_start;
+	gzip_ = gz_ && !gzdirect(static_cast<gzFile>(gz_));
 	return true;
 }
 

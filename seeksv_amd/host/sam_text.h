@@ -1,7 +1,9 @@
-// sam_text.h - reader of SAM text files for `getsv -F` (the reference opens every -F name without ".bam" as text, process_bwasw.cpp:12-16).
+// sam_text.h - reader of SAM text files for `getsv -F` and for getsv's clipped-sequence re-alignments (the reference opens every such name without ".bam" as
+// text, "-" as standard input: process_bwasw.cpp:12-16, getsv.h:437-446).
 // The header ('@' lines up to the first record; @SQ SN: / LN:) is parsed here on the host; the records are NOT: their text goes to the GPU as it is
 // (ssv_samdec_decode), in chunks cut anywhere, which a reader thread fills ahead of the decoder.  Plain files are read with pread, gzip-compressed ones
-// (detected by their magic bytes) with zlib's gzread: one stream on one thread - its rate has not been measured.
+// (detected by their magic bytes) with zlib's gzread: one stream on one thread - its rate has not been measured.  Standard input is read sequentially through gzread in
+// either form (zlib passes plain text through).
 #ifndef SEEKSV_SAM_TEXT_H_
 #define SEEKSV_SAM_TEXT_H_
 
@@ -31,12 +33,12 @@ public:
 	SamTextReader(const SamTextReader &) = delete;
 	SamTextReader &operator=(const SamTextReader &) = delete;
 
-	// opens the file and reads its header; false: err says why
+	// opens the file ("-": standard input, plain or gzip) and reads its header; false: err says why
 	bool open(const std::string &path, std::string &err);
 	const std::vector<std::string> &target_names() const { return names_; }
 	const std::vector<int32_t> &target_lens() const { return lens_; }
 	uint64_t first_record_line() const { return first_record_line_; } // 1-based, in the file
-	bool is_gzip() const { return gz_ != nullptr; }
+	bool is_gzip() const { return gzip_; }
 
 	// the reader thread: chunks of up to chunk_bytes into three buffers in turn
 	void start(size_t chunk_bytes, AllocFn alloc = nullptr, FreeFn free_fn = nullptr);
@@ -52,7 +54,8 @@ private:
 	void reader_main();
 
 	int fd_ = -1;
-	void *gz_ = nullptr; // gzFile
+	void *gz_ = nullptr; // gzFile (gzip files, and standard input in either form)
+	bool gzip_ = false;
 	uint64_t file_off_ = 0;
 	std::string pending_; // what was read behind the header
 	size_t pending_at_ = 0;

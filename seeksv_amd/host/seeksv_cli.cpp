@@ -127,7 +127,9 @@ static void release_ctx(ssv_ctx *ctx);
 
 [[noreturn]] static void usage_getsv()
 {
-	cerr << "Usage: seeksv getsv [options] <input clipped sequence bam> <input orignal sorted bam> <soft-clipped reads file(*clip.gz)> <output SVs> <output unmaped clipped sequence fastq>\n"
+	cerr << "Usage: seeksv getsv [options] <input clipped sequence bam or SAM text> <input orignal sorted bam> <soft-clipped reads file(*clip.gz)> <output SVs> <output unmaped clipped sequence fastq>\n"
+	     << "         <input clipped sequence ...>: a name ending in .bam is BAM; every other name SAM text (plain or gzip, e.g. `bwa mem` output as it is), parsed on the GPU;\n"
+	     << "                               - is standard input (SAM text)\n"
 	     << "Options: -F <FILE>             Samfile/Bamfile of connected read-through reads (split alignments, e.g. bwa bwasw): their junctions are evaluated in addition;\n"
 	     << "                               a name ending in .bam is BAM, every other name SAM text (plain or gzip), which is parsed on the GPU\n"
 	     << "         -w <int>              Minimum mapping quality of the -F reads [1]\n"
@@ -1249,9 +1251,12 @@ static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx
 static void *sam_stage_alloc(size_t bytes) { void *p = nullptr; return ssv_host_alloc(bytes, &p) == SSV_OK ? p : nullptr; }
 static void sam_stage_free(void *p) { ssv_host_free(p); }
 
-// the -F file as SAM text: the header on the host, the records' text to the GPU as it is, in chunks cut anywhere (SSV_SAM_CHUNK_KB: their size, 256 MB by
-// default); a reader thread fills page-locked buffers ahead, and chunk k + 1 crosses the host link under chunk k's kernels (ssv_samdec_prefetch)
-static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
+// A SAM text file through the device decoder: the header on the host, the records' text to the GPU as it is, in chunks cut anywhere (SSV_SAM_CHUNK_KB: their
+// size, 256 MB by default); a reader thread fills page-locked buffers ahead, and chunk k + 1 crosses the host link under chunk k's kernels
+// (ssv_samdec_prefetch).  begin(): once, behind the header; on_batch(): every decoded batch with its names, valid until the call returns.  Shared by the -F pass
+// and by the pass over the clipped-sequence re-alignments: they differ in what they do with a batch.
+static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &names, const std::function<void()> &begin,
+                          const std::function<void(const ssv_batch_t &, const ssv_names_t &)> &on_batch)
 {
 	seeksv::SamTextReader rd;
 	string err;
@@ -1262,7 +1267,7 @@ static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx,
 		die(kRtOpenError);
 	}
 	cerr << "[samopen] SAM header is present: " << names.size() << " sequences." << endl;
-	rt_begin_for(names, min_mapq, ctx);
+	begin();
 	vector<const char *> cnames;
 	for (const string &s : names) cnames.push_back(s.c_str());
 	ssv_samdec_params sp;
@@ -1282,7 +1287,7 @@ static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx,
 		}
 		ssv_names_t nm;
 		if (ssv_samdec_names(ctx, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		if (b.n && ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		if (b.n) on_batch(b, nm);
 	};
 	while (rd.next(ck, err)) {
 		if (!ck.last && rd.ready_behind(nx) && ssv_samdec_prefetch(ctx, nx.data, nx.bytes) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
@@ -1295,10 +1300,56 @@ static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx,
 	rd.close();
 }
 
+static bool is_bam_name(const string &path) { return path.size() >= 4 && path.rfind(".bam") == path.size() - 4; }
+
+// the -F file as SAM text
+static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
+{
+	sam_text_pass(path, ctx, names, [&] { rt_begin_for(names, min_mapq, ctx); },
+	              [&](const ssv_batch_t &b, const ssv_names_t &nm) { if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); });
+}
+
+// The re-alignments of the clipped sequences as SAM text (`bwa mem ref.fa out.clip.fq.gz > out.clip.sam`, or piped in: getsv.h:437-446 opens every name
+// without ".bam" as text): decoded on the GPU chunk by chunk, every batch packed there into the columns the join reads (ssv_aln_pack: fixed fields, names back
+// to back, their hashes) and appended here; offsets are rebased by the running totals.
+struct ClipAlignments {
+	vector<int32_t> tid, pos;
+	vector<uint16_t> flag, n_cigar;
+	vector<uint8_t> mapq;
+	vector<uint32_t> cigar_off, cigar;
+	vector<uint64_t> name_off, hash;
+	vector<char> names;
+	vector<const char *> qname;
+	seeksv::AlnRecords R;
+};
+
+static void clip_sam_pass(const string &path, ssv_ctx *ctx, ClipAlignments &A)
+{
+	sam_text_pass(path, ctx, A.R.target_names, [] {}, [&](const ssv_batch_t &b, const ssv_names_t &nm) {
+		ssv_aln_cols c;
+		if (ssv_aln_pack(ctx, &b, &nm, &c) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		const size_t n = (size_t)c.n, n0 = A.tid.size(), ops0 = A.cigar.size(), bytes0 = A.names.size();
+		if (ops0 + (size_t)c.n_cigar_total >= ((size_t)1 << 32)) die("[seeksv] more than 2^32 CIGAR operations among the clipped-sequence alignments");
+		A.tid.insert(A.tid.end(), c.tid, c.tid + n); A.pos.insert(A.pos.end(), c.pos, c.pos + n);
+		A.flag.insert(A.flag.end(), c.flag, c.flag + n); A.n_cigar.insert(A.n_cigar.end(), c.n_cigar, c.n_cigar + n);
+		A.mapq.insert(A.mapq.end(), c.mapq, c.mapq + n); A.hash.insert(A.hash.end(), c.name_hash, c.name_hash + n);
+		A.cigar.insert(A.cigar.end(), c.cigar, c.cigar + c.n_cigar_total);
+		A.names.insert(A.names.end(), c.names, c.names + c.name_bytes);
+		A.cigar_off.resize(n0 + n); A.name_off.resize(n0 + n);
+		for (size_t i = 0; i < n; ++i) { A.cigar_off[n0 + i] = c.cigar_off[i] + (uint32_t)ops0; A.name_off[n0 + i] = c.name_off[i] + bytes0; }
+	});
+	const size_t n = A.tid.size();
+	A.qname.resize(n);
+	for (size_t i = 0; i < n; ++i) A.qname[i] = A.names.data() + A.name_off[i];
+	seeksv::AlnRecords &R = A.R;
+	R.n = (int64_t)n; R.tid = A.tid.data(); R.pos = A.pos.data(); R.flag = A.flag.data(); R.n_cigar = A.n_cigar.data(); R.mapq = A.mapq.data();
+	R.cigar_off = A.cigar_off.data(); R.cigar = A.cigar.data(); R.qname = A.qname.data(); R.qhash = A.hash.data();
+}
+
 static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, bool device_inflate, JunctionMap &junction2other)
 {
 	vector<string> names;
-	if (path.size() < 4 || path.rfind(".bam") != path.size() - 4) readthrough_pass_sam(path, min_mapq, ctx, names);
+	if (!is_bam_name(path)) readthrough_pass_sam(path, min_mapq, ctx, names);
 	else {
 		ssvh_bam *hdr = nullptr;
 		if (ssvh_bam_open(path.c_str(), &hdr) != 0) die(kRtOpenError);
@@ -1395,16 +1446,27 @@ static int cmd_getsv(int argc, char **argv)
 	}
 	{ // InputSoftInfoStoreBreakpoint + GetJunction (getsv.h:423, getsv.cpp:1705): clip clusters x re-alignments of their clipped sequences
 		string err;
-		if (g_resident.ctx && clipfile == g_resident.clip_path && clip_bam == g_resident.aln.bam_path && g_resident.aln.rec) {
-			seeksv::AlnRecords R; // rows and alignments are both still in memory
-			resident_alignments(R);
+		const bool rows_resident = g_resident.ctx && clipfile == g_resident.clip_path;
+		auto join_records = [&](const seeksv::AlnRecords &R) { // the alignments in memory; the rows too when this process wrote them
+			if (!rows_resident) return seeksv::assemble_junctions_file_records(clipfile, R, junction2other);
 			if (g_resident.all_clean() && !getenv("SSV_RUN_PARSE_ROWS")) { // the rows as the formatter kept them: nothing is parsed (SSV_RUN_PARSE_ROWS, tests: the text is)
 				vector<const vector<seeksv::ClipRow> *> parts;
 				for (const auto &p : g_resident.pieces) parts.push_back(&p.parsed);
-				err = seeksv::assemble_junctions_rows(parts, R, junction2other);
-			} else err = seeksv::assemble_junctions_records(g_resident.row_views(), R, junction2other);
-		} else err = g_resident.ctx && clipfile == g_resident.clip_path ? seeksv::assemble_junctions_text(g_resident.row_views(), clip_bam, junction2other)
-		                                                                : seeksv::assemble_junctions(clipfile, clip_bam, junction2other);
+				return seeksv::assemble_junctions_rows(parts, R, junction2other);
+			}
+			return seeksv::assemble_junctions_records(g_resident.row_views(), R, junction2other);
+		};
+		if (!is_bam_name(clip_bam)) { // SAM text (the reference's rule, getsv.h:437-446): always parsed on the GPU, whatever -Z says; with -N n once, on the first device
+			if (!rt_ctx) { rt_ctx = acquire_ctx(device); pt.lap("context start-up (waited for in front of the SAM decode)"); }
+			ClipAlignments A;
+			clip_sam_pass(clip_bam, rt_ctx, A);
+			pt.lap("clip alignments (SAM text: decode + pack)");
+			err = join_records(A.R);
+		} else if (rows_resident && clip_bam == g_resident.aln.bam_path && g_resident.aln.rec) {
+			seeksv::AlnRecords R; // rows and alignments are both still in memory
+			resident_alignments(R);
+			err = join_records(R);
+		} else err = rows_resident ? seeksv::assemble_junctions_text(g_resident.row_views(), clip_bam, junction2other) : seeksv::assemble_junctions(clipfile, clip_bam, junction2other);
 		if (!err.empty()) die(err);
 	}
 	cerr << "'InputSoftInfoStoreBreakpoint' finished" << endl;
