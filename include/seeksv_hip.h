@@ -490,7 +490,8 @@ int ssv_bamdec_decode(ssv_ctx *ctx, const void *comp, size_t comp_bytes, const s
 int ssv_bamdec_last(ssv_ctx *ctx, ssv_bamdec_info *info);
 
 /* The read names of a batch, beside ssv_batch_t (which has no field for them): record i's NUL-terminated name (at most 255 bytes with the NUL) starts at
- * base + off[i] + bias.  mem as in ssv_batch_t (SSV_MEM_HOST: base[bytes] and off[n] are copied to the GPU; SSV_MEM_DEVICE: used in place, bytes unused). */
+ * base + off[i] + bias.  mem as in ssv_batch_t (SSV_MEM_HOST: base[bytes] and off[n] are copied to the GPU; SSV_MEM_DEVICE: used in place, bytes unused;
+ * any other mem, bias < 0, or bytes < 0 with SSV_MEM_HOST: SSV_E_ARG from every call that takes one). */
 typedef struct {
 	int32_t mem;
 	int32_t pad;

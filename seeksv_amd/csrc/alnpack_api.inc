@@ -11,9 +11,7 @@ int ssv_aln_pack(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, ssv_al
 {
 	if (!c) return SSV_E_ARG;
 	if (!b || !out) { c->err = "ssv_aln_pack: no batch or no result"; return SSV_E_ARG; }
-	if (b->n > 0 && (!nm || !nm->base || !nm->off || (nm->mem != SSV_MEM_HOST && nm->mem != SSV_MEM_DEVICE) || nm->bias < 0 || (nm->mem == SSV_MEM_HOST && nm->bytes < 0))) {
-		c->err = "ssv_aln_pack: a batch with records needs their names"; return SSV_E_ARG;
-	}
+	CHECK(check_names(c, nm, b->n, "ssv_aln_pack"));
 	if (b->n_cigar_total < 0 || b->n_cigar_total >= (1ll << 32)) { c->err = "ssv_aln_pack: bad n_cigar_total"; return SSV_E_ARG; }
 	HIPCHECK(c, hipSetDevice(c->device));
 	DevBatch d;
@@ -29,15 +27,8 @@ int ssv_aln_pack(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, ssv_al
 	CHECK(ensure_host(c, A.h_hash, N * 8 + 16)); CHECK(ensure_host(c, A.h_names, 16)); CHECK(ensure_host(c, A.h_small, 64));
 	uint64_t name_bytes = 0;
 	if (n > 0) {
-		AlnNames names;
-		if (nm->mem == SSV_MEM_DEVICE) names = AlnNames{nm->base, nm->off, nm->bias};
-		else {
-			CHECK(ensure(c, A.hnames, (size_t)nm->bytes + 16)); CHECK(ensure(c, A.hoff, N * 8 + 16));
-			if (nm->bytes) HIPCHECK(c, hipMemcpyAsync(A.hnames.p, nm->base, (size_t)nm->bytes, hipMemcpyHostToDevice, st));
-			HIPCHECK(c, hipMemsetAsync(P<char>(A.hnames) + nm->bytes, 0, 16, st)); // (a name without its NUL ends here)
-			HIPCHECK(c, hipMemcpyAsync(A.hoff.p, nm->off, N * 8, hipMemcpyHostToDevice, st));
-			names = AlnNames{P<char>(A.hnames), P<uint64_t>(A.hoff), nm->bias};
-		}
+		DevNames names;
+		CHECK(stage_names(c, nm, n, A.hnames, A.hoff, names));
 		CHECK(ensure(c, A.flag, N * 2 + 16)); CHECK(ensure(c, A.mapq, N + 16)); CHECK(ensure(c, A.cigar_off, N * 4 + 16)); CHECK(ensure(c, A.nbytes, N * 4 + 16));
 		CHECK(ensure(c, A.name_off, N * 8 + 16)); CHECK(ensure(c, A.hash, N * 8 + 16)); CHECK(ensure(c, A.small, 64));
 		CHECK(ensure(c, c->scan_scratch64, (size_t)scan_scratch_elems(n) * 8 + 64));

@@ -1,6 +1,6 @@
 // alnpack_kernels.h - a decoded batch of clipped-sequence re-alignments as the columns the host join reads (junction_stage.cpp, RecSource): the fixed
 // fields out of the record lines, the read names packed back to back, and the 64-bit hash of every name (text_hash, junction_stage.cpp:42-50), the join's
-// first compare.  k_aln_name_len (per record) -> exclusive_scan -> k_aln_pack (four lanes per record).
+// first compare.  k_aln_name_len (per record) -> exclusive_scan -> k_aln_pack (four lanes per record).  The names come as DevNames (common.h).
 // Names start at any byte of the decoder's text (or name) buffer and land at any byte of the blob: both kernels read whole ALIGNED 8-byte words only and
 // funnel-shift; a word is read only when at least one of its bytes belongs to the name or is its NUL, so no load leaves the 8-byte granule - let alone the
 // page - of a byte the name owns: no slack behind the buffers is relied on (ssv_samdec_decode leaves 128 bytes behind its text, ssv_bamdec_decode's names
@@ -14,11 +14,6 @@ namespace ssv {
 
 constexpr uint32_t ALN_NAME_MAX = 254; // bytes of a read name without its NUL (BAM's l_read_name is one byte; the SAM decoder refuses longer ones)
 
-// names of a batch: record i's NUL-terminated name at base + off[i] + bias (ssv_names_t)
-struct AlnNames { const char *base; const uint64_t *off; int64_t bias; };
-
-__device__ __forceinline__ uint64_t aln_name_addr(const AlnNames &nm, int64_t i) { return (uint64_t)(uintptr_t)nm.base + nm.off[i] + (uint64_t)nm.bias; }
-
 // flag, mapq and cigar_off out of the record lines (tid, pos and n_cigar are hot columns of the batch already)
 __global__ __launch_bounds__(BLOCK) void k_aln_cols(const ssv_record *__restrict__ rec, int64_t n, uint16_t *__restrict__ flag, uint8_t *__restrict__ mapq, uint32_t *__restrict__ cigar_off)
 {
@@ -31,11 +26,11 @@ __global__ __launch_bounds__(BLOCK) void k_aln_cols(const ssv_record *__restrict
 
 // per record: bytes of its name with the NUL.  One lane walks the aligned words from the one the name starts in to the one its NUL is in (a name without a
 // NUL within ALN_NAME_MAX + 1 bytes is cut there: the decoders hand out none).
-__global__ __launch_bounds__(BLOCK) void k_aln_name_len(AlnNames nm, int64_t n, uint32_t *__restrict__ nbytes)
+__global__ __launch_bounds__(BLOCK) void k_aln_name_len(DevNames nm, int64_t n, uint32_t *__restrict__ nbytes)
 {
 	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (i >= n) return;
-	const uint64_t s = aln_name_addr(nm, i);
+	const uint64_t s = (uint64_t)(uintptr_t)name_addr(nm, i);
 	uint64_t a = s & ~7ull;
 	const uint32_t lead = (uint32_t)(s & 7u);
 	uint64_t w = *global_at<uint64_t>(a);
@@ -71,13 +66,13 @@ __device__ __forceinline__ uint64_t aln_span_word(uint64_t p, uint64_t lo, uint6
 // of it).  Round r: lane q of the quad builds the name's r * 4 + q-th word twice - as the blob's aligned word sees it (stored: whole words inside the
 // name, single bytes where a word is shared with the neighbouring names) and as the hash sees it (from the name's first byte, the tail zero padded); the
 // quad's four hash words are then exchanged (DPP) and every lane runs the same serial chain over them.
-__global__ __launch_bounds__(BLOCK) void k_aln_pack(AlnNames nm, int64_t n, const uint32_t *__restrict__ nbytes, const uint64_t *__restrict__ name_off, char *__restrict__ blob,
+__global__ __launch_bounds__(BLOCK) void k_aln_pack(DevNames nm, int64_t n, const uint32_t *__restrict__ nbytes, const uint64_t *__restrict__ name_off, char *__restrict__ blob,
                                                    uint64_t *__restrict__ hash)
 {
 	const int64_t i = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 2;
 	const uint32_t q = threadIdx.x & 3u;
 	if (i >= n) return; // (a quad leaves together)
-	const uint64_t s = aln_name_addr(nm, i);
+	const uint64_t s = (uint64_t)(uintptr_t)name_addr(nm, i);
 	const uint32_t len = nbytes[i] - 1u;
 	const uint64_t end = s + len, o = name_off[i];
 	const uint32_t od = (uint32_t)(o & 7u);

@@ -16,7 +16,8 @@ struct ssv_bamdec_state {
 	DBuf inf_scratch, inf_dbg, tokens, tok_off, n_tok, carrybuf, comp, blocks, u_off, stream, status, chain, count, base, rec_off, stitch, tile_last, tile_prev, runs, small;
 	DBuf raw_runs; HBuf h_raw_runs; std::vector<ssv_tid_run> tid_runs; // the batch's tid column as runs (ssv_batch_t.tid_runs)
 	DBuf tlen; bool have_tlen = false; // contig lengths (optional: ssv_bamdec_target_lens)
-	DBuf rel, stash, seq_list, tid, pos, l_qseq, mtid, mpos, isize, flag, n_cigar, mapq, xc, ends, seq_bytes, raw_bytes, cigar_off, seq_off, raw_off, cigar, seqqual, raw;
+	DecodedColumns cols; // the batch handed out
+	DBuf rel, stash, seq_list, raw_bytes, raw_off, raw;
 	HBuf h_stage[3], h_small, h_raw[2], h_runs, h_status; // h_raw: two in turn - a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded (a thread beside the decoder pairs them up)
 	int raw_flip = 0;
 	// chunks announced ahead (ssv_bamdec_prefetch): their compressed bytes travel on the upload stream into one of two slots while the chunk before is inflated
@@ -194,7 +195,7 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 	// every buffer below is sized as if this chunk were as large as the largest one announced (ssv_bamdec_expect): in proportion
 	const double up = total > d.carry && d.expect_inflated > total - d.carry ? std::min(64.0, (double)d.expect_inflated / (double)(total - d.carry)) : 1.0;
 	if (total > d.carry) d.expect_inflated = 0; // the hint serves the FIRST decode behind it: a later, smaller chunk of another mix (a file's tail of unmapped reads) must not multiply its needs again
-	auto ensure_up = [&](DBuf &buf, size_t bytes) { return ensure(c, buf, up > 1.0 ? (size_t)((double)bytes * up) + 64 : bytes); };
+	auto ensure_up = [&](DBuf &buf, size_t bytes) { return ensure(c, buf, grown(bytes, up)); };
 	CHECK(ensure_up(d.stream, (size_t)total + 64));
 	if (d.carry) HIPCHECK(c, hipMemcpyAsync(d.stream.p, d.carrybuf.p, d.carry, hipMemcpyDeviceToDevice, st)); // the unfinished record of the previous chunk
 	if (n_blocks) {
@@ -360,11 +361,8 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 	// ---- records -> columns ----
 	const size_t N = (size_t)n;
 	CHECK(ensure_up(d.rec_off, N * 8 + 16));
-	CHECK(ensure_up(d.tid, N * 4 + 16)); CHECK(ensure_up(d.pos, N * 4 + 16)); CHECK(ensure_up(d.l_qseq, N * 4 + 16)); CHECK(ensure_up(d.mtid, N * 4 + 16)); CHECK(ensure_up(d.mpos, N * 4 + 16));
-	CHECK(ensure_up(d.isize, N * 4 + 16)); CHECK(ensure_up(d.flag, N * 2 + 16)); CHECK(ensure_up(d.n_cigar, N * 2 + 16)); CHECK(ensure_up(d.mapq, N + 16)); CHECK(ensure_up(d.xc, N + 16)); CHECK(ensure_up(d.ends, N + 16));
-	CHECK(ensure_up(d.stash, N * 8 + 16)); CHECK(ensure_up(d.seq_list, N * 4 + 16));
-	CHECK(ensure_up(d.seq_bytes, N * 4 + 16)); CHECK(ensure_up(d.raw_bytes, N * 4 + 16)); CHECK(ensure_up(d.cigar_off, N * 4 + 16)); CHECK(ensure_up(d.seq_off, N * 8 + 16));
-	CHECK(ensure_up(d.raw_off, N * 8 + 16));
+	CHECK(d.cols.reserve(c, N, up));
+	CHECK(ensure_up(d.stash, N * 8 + 16)); CHECK(ensure_up(d.seq_list, N * 4 + 16)); CHECK(ensure_up(d.raw_bytes, N * 4 + 16)); CHECK(ensure_up(d.raw_off, N * 8 + 16));
 	const int64_t n_tiles = (n + BLOCK - 1) / BLOCK;
 	CHECK(ensure_up(d.tile_last, (size_t)n_tiles * 4)); CHECK(ensure_up(d.tile_prev, (size_t)n_tiles * 4));
 	const uint32_t run_cap = 1u << 16;
@@ -378,13 +376,9 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 		ProfScope ps(c, P_BAM_DECODE, n);
 		hipLaunchKernelGGL(ssv::k_list_records, dim3((unsigned)((n_units + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<ssv::BlockChain>(d.chain), P<uint32_t>(d.count),
 		                   P<uint32_t>(d.base), n_units, P<uint16_t>(d.rel), P<uint64_t>(d.rec_off));
-		ssv::RecColumns rc;
-		rc.tid = P<int32_t>(d.tid); rc.pos = P<int32_t>(d.pos); rc.l_qseq = P<int32_t>(d.l_qseq); rc.mtid = P<int32_t>(d.mtid); rc.mpos = P<int32_t>(d.mpos); rc.isize = P<int32_t>(d.isize);
-		rc.flag = P<uint16_t>(d.flag); rc.n_cigar = P<uint16_t>(d.n_cigar); rc.mapq = P<uint8_t>(d.mapq); rc.xc = P<uint8_t>(d.xc); rc.ends = P<uint8_t>(d.ends); rc.seq_bytes = P<uint32_t>(d.seq_bytes);
-		rc.raw_bytes = P<uint32_t>(d.raw_bytes); rc.max_span = reinterpret_cast<int32_t *>(sm); rc.bad = sm + 1; rc.stash = P<uint2>(d.stash);
-		hipLaunchKernelGGL(ssv::k_record_fields, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, keep_all_seq, rc);
-		exclusive_scan<uint16_t, uint32_t>(st, P<uint16_t>(d.n_cigar), P<uint32_t>(d.cigar_off), n, 0u, P<uint32_t>(c->scan_scratch), sm + 4);
-		exclusive_scan<uint32_t, uint64_t>(st, P<uint32_t>(d.seq_bytes), P<uint64_t>(d.seq_off), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 6));
+		const ssv::RecColumns rc{P<uint32_t>(d.raw_bytes), P<uint2>(d.stash), reinterpret_cast<int32_t *>(sm), sm + 1};
+		hipLaunchKernelGGL(ssv::k_record_fields, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, keep_all_seq, d.cols.view(), rc);
+		d.cols.layout(st, n, P<uint32_t>(c->scan_scratch), P<uint64_t>(c->scan_scratch64), sm + 4, reinterpret_cast<uint64_t *>(sm + 6));
 		exclusive_scan<uint32_t, uint64_t>(st, P<uint32_t>(d.raw_bytes), P<uint64_t>(d.raw_off), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 8));
 	}
 	// sizes of the variable parts, then exactly sized buffers
@@ -394,18 +388,19 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 	const uint32_t cigar_total = P<uint32_t>(d.h_small)[4];
 	memcpy(&seq_total, P<uint32_t>(d.h_small) + 6, 8); memcpy(&raw_total, P<uint32_t>(d.h_small) + 8, 8);
 	if (P<uint32_t>(d.h_small)[1]) { c->err = "corrupt BAM record"; return SSV_E_ARG; }
-	CHECK(ensure_up(d.cigar, (size_t)cigar_total * 4 + 64)); CHECK(ensure_up(d.seqqual, (size_t)seq_total + 64)); CHECK(ensure_up(d.raw, (size_t)raw_total + 64));
+	CHECK(d.cols.reserve_variable(c, cigar_total, (size_t)seq_total, up)); CHECK(ensure_up(d.raw, (size_t)raw_total + 64));
+	const ssv::DecodedCols col = d.cols.view();
 	{
 		ProfScope ps(c, P_BAM_DECODE, n);
-		hipLaunchKernelGGL(ssv::k_record_cigars, dim3((unsigned)((n + BLOCK * ssv::CIGARS_PER_THREAD - 1) / (BLOCK * ssv::CIGARS_PER_THREAD))), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, P<uint16_t>(d.n_cigar),
-		                   P<uint32_t>(d.cigar_off), P<uint2>(d.stash), P<uint32_t>(d.seq_bytes), P<uint8_t>(d.xc), P<uint64_t>(d.seq_off), P<uint32_t>(d.cigar), P<uint32_t>(d.seq_list), sm + 10);
+		hipLaunchKernelGGL(ssv::k_record_cigars, dim3((unsigned)((n + BLOCK * ssv::CIGARS_PER_THREAD - 1) / (BLOCK * ssv::CIGARS_PER_THREAD))), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, col.n_cigar,
+		                   col.cigar_off, P<uint2>(d.stash), col.seq_bytes, col.xc, col.seq_off, col.cigar, P<uint32_t>(d.seq_list), sm + 10);
 		hipLaunchKernelGGL(ssv::k_record_seqs, dim3((unsigned)std::min<int64_t>((n * 16 + BLOCK - 1) / BLOCK, 2048)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off),
-		                   P<uint16_t>(d.n_cigar), P<uint32_t>(d.seq_bytes), P<uint64_t>(d.seq_off), P<uint32_t>(d.seq_list), sm + 10, P<uint8_t>(d.seqqual), P<uint8_t>(d.xc));
+		                   col.n_cigar, col.seq_bytes, col.seq_off, P<uint32_t>(d.seq_list), sm + 10, col.seqqual, col.xc);
 		hipLaunchKernelGGL(ssv::k_raw_copy, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, P<uint32_t>(d.raw_bytes), P<uint64_t>(d.raw_off), P<uint8_t>(d.raw));
-		hipLaunchKernelGGL(ssv::k_tid_tile_last, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, P<int32_t>(d.tid), P<uint16_t>(d.flag), n, P<int32_t>(d.tile_last));
+		hipLaunchKernelGGL(ssv::k_tid_tile_last, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, col.flag, n, P<int32_t>(d.tile_last));
 		hipLaunchKernelGGL(ssv::k_tid_tile_carry, dim3(1), dim3(WAVE), 0, st, P<int32_t>(d.tile_last), n_tiles, d.prev_tid, P<int32_t>(d.tile_prev), reinterpret_cast<int32_t *>(sm + 3));
-		hipLaunchKernelGGL(ssv::k_tid_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, P<int32_t>(d.tid), P<uint16_t>(d.flag), n, P<int32_t>(d.tile_prev), P<ssv::TidRun>(d.runs), run_cap, sm + 2);
-		hipLaunchKernelGGL(ssv::k_tid_raw_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, P<int32_t>(d.tid), n, P<ssv::TidRun>(d.raw_runs), RAW_RUN_CAP, sm + 11);
+		hipLaunchKernelGGL(ssv::k_tid_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, col.flag, n, P<int32_t>(d.tile_prev), P<ssv::TidRun>(d.runs), run_cap, sm + 2);
+		hipLaunchKernelGGL(ssv::k_tid_raw_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, n, P<ssv::TidRun>(d.raw_runs), RAW_RUN_CAP, sm + 11);
 		HIPCHECK(c, hipMemcpyAsync(d.h_raw_runs.p, d.raw_runs.p, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun), hipMemcpyDeviceToHost, st));
 	}
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
@@ -433,12 +428,8 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 		d.info.n_tid_runs = n_runs; d.info.tid_run_index = idx; d.info.tid_run_tid = tv;
 	}
 	d.info.unmapped_raw = P<uint8_t>(h_raw); d.info.unmapped_bytes = raw_total; d.info.last_tid = d.prev_tid;
-	out->n = n; out->max_ref_span = (int32_t)hs[0] > 0 ? (int32_t)hs[0] : 1;
-	out->tid = P<int32_t>(d.tid); out->pos = P<int32_t>(d.pos); out->flag = P<uint16_t>(d.flag); out->mapq = P<uint8_t>(d.mapq); out->n_cigar = P<uint16_t>(d.n_cigar);
-	out->l_qseq = P<int32_t>(d.l_qseq); out->mtid = P<int32_t>(d.mtid); out->mpos = P<int32_t>(d.mpos); out->isize = P<int32_t>(d.isize); out->cigar_off = P<uint32_t>(d.cigar_off);
-	out->cigar = P<uint32_t>(d.cigar); out->xc = P<uint8_t>(d.xc); out->seq_off = P<uint64_t>(d.seq_off); out->seqqual = P<uint8_t>(d.seqqual);
-	out->cigar_ends = P<uint8_t>(d.ends);
-	out->n_cigar_total = (int64_t)hs[4]; out->seqqual_bytes = (int64_t)seq_total;
+	d.cols.fill(out, n, (int64_t)cigar_total, (int64_t)seq_total);
+	out->max_ref_span = (int32_t)hs[0] > 0 ? (int32_t)hs[0] : 1;
 	{ // the tid column as runs (atomics gave them no order: sorted by record index); more than the list holds: not handed out
 		const uint32_t nr = hs[11];
 		d.tid_runs.clear();
@@ -467,29 +458,5 @@ int ssv_bamdec_last(ssv_ctx *c, ssv_bamdec_info *info)
 {
 	if (!c || !c->bd || !info) return SSV_E_ARG;
 	*info = c->bd->info;
-	return SSV_OK;
-}
-
-// test/debug helper: a device batch as a host batch (arrays owned by the context, valid until the next call)
-int ssv_batch_to_host(ssv_ctx *c, const ssv_batch_t *dev, ssv_batch_t *host)
-{
-	if (!c || !dev || !host || dev->mem != SSV_MEM_DEVICE) return SSV_E_ARG;
-	const size_t n = (size_t)dev->n;
-	const size_t sz[15] = {n * 4, n * 4, n * 2, n, n * 2, n * 4, n * 4, n * 4, n * 4, n * 4, (size_t)dev->n_cigar_total * 4, n, n * 8, (size_t)dev->seqqual_bytes, n};
-	const void *src[15] = {dev->tid, dev->pos, dev->flag, dev->mapq, dev->n_cigar, dev->l_qseq, dev->mtid, dev->mpos, dev->isize, dev->cigar_off, dev->cigar, dev->xc, dev->seq_off, dev->seqqual, dev->cigar_ends};
-	size_t off[16]; off[0] = 0;
-	for (int k = 0; k < 15; ++k) off[k + 1] = off[k] + ((sz[k] + 63) & ~(size_t)63);
-	CHECK(ensure_host(c, c->h_batch, off[15] + 64));
-	uint8_t *base = P<uint8_t>(c->h_batch);
-	for (int k = 0; k < 15; ++k) if (sz[k] && src[k]) HIPCHECK(c, hipMemcpyAsync(base + off[k], src[k], sz[k], hipMemcpyDeviceToHost, c->st));
-	HIPCHECK(c, hipStreamSynchronize(c->st));
-	*host = *dev;
-	host->mem = SSV_MEM_HOST;
-	host->tid = (const int32_t *)(base + off[0]); host->pos = (const int32_t *)(base + off[1]); host->flag = (const uint16_t *)(base + off[2]); host->mapq = base + off[3];
-	host->n_cigar = (const uint16_t *)(base + off[4]); host->l_qseq = (const int32_t *)(base + off[5]); host->mtid = (const int32_t *)(base + off[6]); host->mpos = (const int32_t *)(base + off[7]);
-	host->isize = (const int32_t *)(base + off[8]); host->cigar_off = (const uint32_t *)(base + off[9]); host->cigar = (const uint32_t *)(base + off[10]);
-	host->xc = dev->xc ? base + off[11] : nullptr; host->seq_off = (const uint64_t *)(base + off[12]); host->seqqual = base + off[13];
-	host->cigar_ends = dev->cigar_ends ? base + off[14] : nullptr;
-	host->rec = nullptr; // (the lines stay on the device: the host batch is the classic columns)
 	return SSV_OK;
 }

@@ -19,6 +19,7 @@
 // makes the result independent of the speculation.
 #pragma once
 
+#include "batch_columns.h"
 #include "common.h"
 #include "inflate_core.h"
 #include "resolve_wave.h"
@@ -505,12 +506,8 @@ __global__ __launch_bounds__(BLOCK) void k_list_records(const uint8_t *__restric
 
 // ---- records -> structure of arrays ----------------------------------------------------------------------------------------------
 
+// what only this decoder writes, beside the columns both decoders share (DecodedCols, batch_columns.h)
 struct RecColumns {
-	int32_t *tid, *pos, *l_qseq, *mtid, *mpos, *isize;
-	uint16_t *flag, *n_cigar;
-	uint8_t *mapq, *xc;
-	uint8_t *ends;        // first | last << 4 CIGAR operation codes (ssv_batch_t.cigar_ends)
-	uint32_t *seq_bytes;  // bytes of packed bases + qualities to ship (0 when not shipped)
 	uint32_t *raw_bytes;  // 4 + block_size for UNMAP|MUNMAP records (else 0)
 	uint2 *stash;         // the first two CIGAR operations (k_record_cigars copies from here: most records have no more, and it need not touch the stream again)
 	int32_t *max_span;    // one int: largest reference span (atomicMax)
@@ -518,7 +515,7 @@ struct RecColumns {
 };
 
 // one record's fixed fields -> columns; returns its reference span.  rp = the record (its block_size word), in the stream or in a staged copy of it
-__device__ __forceinline__ int record_fields_of(const uint8_t *rp, int64_t i, int keep_all_seq, const RecColumns &c)
+__device__ __forceinline__ int record_fields_of(const uint8_t *rp, int64_t i, int keep_all_seq, const DecodedCols &c, const RecColumns &x)
 {
 	int span = 1;
 	const uint8_t *r = rp + 4;
@@ -531,7 +528,7 @@ __device__ __forceinline__ int record_fields_of(const uint8_t *rp, int64_t i, in
 	bool soft = false;
 	uint32_t ends = 0xffu;
 	uint2 first2 = make_uint2(0u, 0u);
-	if (l_seq < 0 || need > bs) { *c.bad = 1; c.seq_bytes[i] = 0; c.raw_bytes[i] = 0; c.n_cigar[i] = 0; }
+	if (l_seq < 0 || need > bs) { *x.bad = 1; c.seq_bytes[i] = 0; x.raw_bytes[i] = 0; c.n_cigar[i] = 0; }
 	else {
 		int s = 0;
 		for (uint32_t k = 0; k < ncig; ++k) {
@@ -546,10 +543,10 @@ __device__ __forceinline__ int record_fields_of(const uint8_t *rp, int64_t i, in
 		}
 		if (s > span) span = s;
 		c.seq_bytes[i] = (soft || keep_all_seq) ? (uint32_t)(((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq) : 0u;
-		c.raw_bytes[i] = (flag & (F_UNMAP | F_MUNMAP)) ? 4u + bs : 0u;
+		x.raw_bytes[i] = (flag & (F_UNMAP | F_MUNMAP)) ? 4u + bs : 0u;
 	}
-	c.ends[i] = (uint8_t)ends;
-	c.stash[i] = first2;
+	c.cigar_ends[i] = (uint8_t)ends;
+	x.stash[i] = first2;
 	c.xc[i] = soft ? 2 : 0; // 2 = "soft clipped, aux not looked at yet": k_record_seqs turns it into the XC flag
 	return span;
 }
@@ -557,15 +554,15 @@ __device__ __forceinline__ int record_fields_of(const uint8_t *rp, int64_t i, in
 // (Tried: a wavefront copies its 64 records' whole run of the stream into LDS with coalesced 16-byte loads and the lanes parse out of the copy - the stream
 // read once, in order: 3.5 -> 3.7 ms, with every load issued before the first LDS write 5.0 ms.  Lane-by-lane loads already pull each 128-byte line only
 // once - consecutive lanes, consecutive records - so the copy saves no bytes and adds a trip through LDS.)
-__global__ __launch_bounds__(BLOCK) void k_record_fields(const uint8_t *__restrict__ u, const uint64_t *__restrict__ rec_off, int64_t n, int keep_all_seq, RecColumns c)
+__global__ __launch_bounds__(BLOCK) void k_record_fields(const uint8_t *__restrict__ u, const uint64_t *__restrict__ rec_off, int64_t n, int keep_all_seq, DecodedCols c, RecColumns x)
 {
 	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	int span = 1;
-	if (i < n) span = record_fields_of(u + rec_off[i], i, keep_all_seq, c);
+	if (i < n) span = record_fields_of(u + rec_off[i], i, keep_all_seq, c, x);
 	span = wave_max(span);
 	// every wavefront has SOME span > 1, and 300 K atomics on one address are served one after the other (3 of this kernel's 3.5 ms were that): look first
 	// (a load that bypasses the CU's cache, or a stale small value would keep this CU's atomics coming), raise only what is not yet as large
-	if (lane_id() == 0 && span > 1 && span > __hip_atomic_load(c.max_span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(c.max_span, span);
+	if (lane_id() == 0 && span > 1 && span > __hip_atomic_load(x.max_span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(x.max_span, span);
 }
 
 // bam_aux_get(b, "XC") + bam_aux2i (clip_reads.cpp:126-127): integer value of the XC tag != 0

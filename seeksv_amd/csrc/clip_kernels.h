@@ -12,6 +12,7 @@
 // the read's packed bases + qualities where they already lie in HBM.
 #pragma once
 
+#include "batch_columns.h"
 #include "common.h"
 #include "seeksv_hip.h"
 
@@ -29,18 +30,6 @@ struct DevBatch {
 	const uint32_t *cigar;      // all operations (a line holds the first five)
 	const uint8_t *seqqual;
 	int32_t max_ref_span;
-};
-
-// structure-of-arrays source of k_build_rec (batches that come without `rec`)
-struct SoaCols {
-	const int32_t *tid, *pos;
-	const uint16_t *flag;
-	const uint8_t *mapq;
-	const uint16_t *n_cigar;
-	const int32_t *l_qseq, *mtid, *mpos, *isize;
-	const uint32_t *cigar_off, *cigar;
-	const uint8_t *xc;
-	const uint64_t *seq_off;
 };
 
 // one ssv_record in registers: four 16-byte loads of one line

@@ -42,6 +42,10 @@ template <typename T> using gptr = const T __attribute__((address_space(1))) *;
 template <typename T> __device__ __forceinline__ gptr<T> as_global(const T *p) { return (gptr<T>)p; }
 template <typename T> __device__ __forceinline__ gptr<T> global_at(uint64_t addr) { return (gptr<T>)(uintptr_t)addr; }
 
+// the read names of a batch on the device: record i's NUL-terminated name starts at base + off[i] + bias (ssv_names_t)
+struct DevNames { const char *base; const uint64_t *off; int64_t bias; };
+__device__ __forceinline__ const char *name_addr(const DevNames &nm, int64_t i) { return nm.base + nm.off[i] + nm.bias; }
+
 constexpr int WAVE = 64;
 constexpr int BLOCK = 256;            // 4 waves per workgroup
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;

@@ -42,7 +42,8 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 {
 	if (!c) return SSV_E_ARG;
 	if (!c->rt || c->rt->phase != ssv_rt_state::SCANNING) { c->err = "ssv_rt_scan before ssv_rt_begin"; return SSV_E_STATE; }
-	if (!b || !nm || (b->n > 0 && (!nm->base || !nm->off)) || (nm->mem != SSV_MEM_HOST && nm->mem != SSV_MEM_DEVICE) || nm->bias < 0) { c->err = "ssv_rt_scan: bad arguments"; return SSV_E_ARG; }
+	if (!b || !nm) { c->err = "ssv_rt_scan: no batch or no names"; return SSV_E_ARG; }
+	CHECK(check_names(c, nm, b->n, "ssv_rt_scan"));
 	ssv_rt_state &R = *c->rt;
 	HIPCHECK(c, hipSetDevice(c->device));
 	DevBatch d;
@@ -56,15 +57,8 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 		HIPCHECK(c, hipGetLastError());
 		d.ends = P<uint8_t>(c->ends_buf);
 	}
-	RtNames names;
-	if (nm->mem == SSV_MEM_DEVICE) names = RtNames{nm->base, nm->off, nm->bias};
-	else {
-		CHECK(ensure(c, R.hnames, (size_t)nm->bytes + 16)); CHECK(ensure(c, R.hoff, (size_t)n * 8 + 16));
-		if (nm->bytes) HIPCHECK(c, hipMemcpyAsync(R.hnames.p, nm->base, (size_t)nm->bytes, hipMemcpyHostToDevice, c->st));
-		HIPCHECK(c, hipMemsetAsync(P<char>(R.hnames) + nm->bytes, 0, 16, c->st)); // (a name without its NUL ends here)
-		HIPCHECK(c, hipMemcpyAsync(R.hoff.p, nm->off, (size_t)n * 8, hipMemcpyHostToDevice, c->st));
-		names = RtNames{P<char>(R.hnames), P<uint64_t>(R.hoff), nm->bias};
-	}
+	DevNames names;
+	CHECK(stage_names(c, nm, n, R.hnames, R.hoff, names));
 	// ---- select: the ends column (and behind a passing pair the flag / mapq of the line) -> ordered compaction ----
 	CHECK(ensure(c, R.keep, (size_t)n * 4 + 16)); CHECK(ensure(c, R.at, (size_t)n * 4 + 16)); CHECK(ensure(c, R.cand, (size_t)n * 4 + 16));
 	CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(n) * 4)); CHECK(ensure(c, c->scan_scratch64, scan_scratch_elems(n) * 8));

@@ -22,9 +22,6 @@ struct RtCand {
 	uint64_t name_off, seq_off, cig_off;
 };
 
-// names of a batch: record i's NUL-terminated name at base + off[i] + bias
-struct RtNames { const char *base; const uint64_t *off; int64_t bias; };
-
 __device__ __forceinline__ bool rt_ends_pass(uint8_t e)
 {
 	if (e == 0xff) return false; // no CIGAR (the reference reads cigar[-1]: skipped here)
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(BLOCK) void k_rt_place(const uint32_t *__restrict__
 }
 
 // per candidate: bytes of its name (with the NUL), packed bases and operations; the 64-bit FNV-1a hash of its name (low hash_bits bits)
-__global__ __launch_bounds__(BLOCK) void k_rt_measure(DevBatch b, RtNames nm, const uint32_t *__restrict__ cand, int64_t m, uint64_t hash_mask,
+__global__ __launch_bounds__(BLOCK) void k_rt_measure(DevBatch b, DevNames nm, const uint32_t *__restrict__ cand, int64_t m, uint64_t hash_mask,
                                                       uint64_t *__restrict__ name_bytes, uint64_t *__restrict__ seq_bytes, uint64_t *__restrict__ cig_ops,
                                                       uint64_t *__restrict__ hash, uint32_t *__restrict__ bad)
 {
@@ -65,7 +62,7 @@ __global__ __launch_bounds__(BLOCK) void k_rt_measure(DevBatch b, RtNames nm, co
 	if (k >= m) return;
 	const int64_t i = cand[k];
 	const RecLine r = rec_load(b.rec, i);
-	const char *p = nm.base + nm.off[i] + nm.bias;
+	const char *p = name_addr(nm, i);
 	uint64_t h = 1469598103934665603ull;
 	uint32_t len = 0;
 	while (len < 255) {
@@ -86,7 +83,7 @@ __global__ __launch_bounds__(BLOCK) void k_rt_measure(DevBatch b, RtNames nm, co
 }
 
 // one wavefront per candidate: its RtCand line and copies of its name, bases and non-clip operations
-__global__ __launch_bounds__(BLOCK) void k_rt_gather(DevBatch b, RtNames nm, const uint32_t *__restrict__ cand, int64_t m, uint64_t rec_base,
+__global__ __launch_bounds__(BLOCK) void k_rt_gather(DevBatch b, DevNames nm, const uint32_t *__restrict__ cand, int64_t m, uint64_t rec_base,
                                                      const uint64_t *__restrict__ name_at, const uint64_t *__restrict__ seq_at, const uint64_t *__restrict__ cig_at,
                                                      RtCand *__restrict__ out, char *__restrict__ names, uint8_t *__restrict__ seqs, uint32_t *__restrict__ cigs)
 {
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(BLOCK) void k_rt_gather(DevBatch b, RtNames nm, con
 	c.ncig = (uint16_t)(cig_at[k + 1] - cig_at[k]);
 	c.pad = 0;
 	if (lane == 0) out[k] = c;
-	const char *pn = nm.base + nm.off[i] + nm.bias;
+	const char *pn = name_addr(nm, i);
 	for (uint32_t j = (uint32_t)lane; j < c.name_len; j += WAVE) names[c.name_off + j] = pn[j];
 	if (lane == 0) names[c.name_off + c.name_len] = 0;
 	const uint32_t sb = (uint32_t)(seq_at[k + 1] - seq_at[k]);

@@ -9,7 +9,8 @@ struct ssv_samdec_state {
 	uint32_t ref_mask = 15;
 	DBuf ref_slots, ref_off, ref_blob;
 	DBuf text, carrybuf, tile_sep, tile_nl, sep, nlidx, small;
-	DBuf tid, pos, l_qseq, mtid, mpos, isize, flag, n_cigar, mapq, xc, ends, seq_bytes, cigar_off, seq_off, name_off, rec, cigar, seqqual;
+	DecodedColumns cols; // the batch handed out
+	DBuf name_off, rec;
 	HBuf h_small;
 	// chunks announced ahead (ssv_samdec_prefetch): on the upload stream into one of two slots, moved behind the carried line by the decode call
 	struct Slot { DBuf buf; const void *host = nullptr; size_t bytes = 0; hipEvent_t up = nullptr, done = nullptr; bool read = false; } slot[2];
@@ -183,21 +184,13 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	}
 	const size_t N = (size_t)n;
 	CHECK(ensure(c, d.sep, (size_t)n_sep * 4 + 16)); CHECK(ensure(c, d.nlidx, N * 4 + 16));
-	CHECK(ensure(c, d.tid, N * 4 + 16)); CHECK(ensure(c, d.pos, N * 4 + 16)); CHECK(ensure(c, d.l_qseq, N * 4 + 16)); CHECK(ensure(c, d.mtid, N * 4 + 16)); CHECK(ensure(c, d.mpos, N * 4 + 16));
-	CHECK(ensure(c, d.isize, N * 4 + 16)); CHECK(ensure(c, d.flag, N * 2 + 16)); CHECK(ensure(c, d.n_cigar, N * 2 + 16)); CHECK(ensure(c, d.mapq, N + 16)); CHECK(ensure(c, d.xc, N + 16));
-	CHECK(ensure(c, d.ends, N + 16)); CHECK(ensure(c, d.seq_bytes, N * 4 + 16)); CHECK(ensure(c, d.cigar_off, N * 4 + 16)); CHECK(ensure(c, d.seq_off, N * 8 + 16));
+	CHECK(d.cols.reserve(c, N, 1.0));
 	CHECK(ensure(c, d.name_off, N * 8 + 16)); CHECK(ensure(c, d.rec, N * sizeof(ssv_record) + 64));
 	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n) * 8 + 64)); CHECK(ensure(c, c->scan_scratch64, (size_t)scan_scratch_elems(n) * 8 + 64));
-	ssv::SamColumns col;
-	col.tid = P<int32_t>(d.tid); col.pos = P<int32_t>(d.pos); col.l_qseq = P<int32_t>(d.l_qseq); col.mtid = P<int32_t>(d.mtid); col.mpos = P<int32_t>(d.mpos); col.isize = P<int32_t>(d.isize);
-	col.flag = P<uint16_t>(d.flag); col.n_cigar = P<uint16_t>(d.n_cigar); col.mapq = P<uint8_t>(d.mapq); col.xc = P<uint8_t>(d.xc); col.ends = P<uint8_t>(d.ends);
-	col.seq_bytes = P<uint32_t>(d.seq_bytes); col.cigar_off = P<uint32_t>(d.cigar_off); col.seq_off = P<uint64_t>(d.seq_off); col.name_off = P<uint64_t>(d.name_off);
-	col.rec = P<ssv_record>(d.rec); col.cigar = nullptr;
 	k_sam_marks<<<(unsigned)n_tiles, BLOCK, 0, st>>>(tx, len, virt_at, P<uint32_t>(d.tile_sep), P<uint32_t>(d.tile_nl), (uint32_t)n, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), errw);
-	k_sam_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col, errw);
+	k_sam_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, d.cols.view(), errw);
 	HIPCHECK(c, hipGetLastError());
-	exclusive_scan<uint16_t, uint32_t>(st, P<uint16_t>(d.n_cigar), P<uint32_t>(d.cigar_off), n, 0u, P<uint32_t>(c->scan_scratch), sm + 4);
-	exclusive_scan<uint32_t, uint64_t>(st, P<uint32_t>(d.seq_bytes), P<uint64_t>(d.seq_off), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 6));
+	d.cols.layout(st, n, P<uint32_t>(c->scan_scratch), P<uint64_t>(c->scan_scratch64), sm + 4, reinterpret_cast<uint64_t *>(sm + 6));
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 16, P<uint32_t>(d.nlidx) + (n - 1), 4, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
@@ -206,14 +199,15 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	const uint32_t cigar_total = hs[4], last_nl_sep = hs[16];
 	uint64_t seq_total;
 	memcpy(&seq_total, hs + 6, 8);
-	CHECK(ensure(c, d.cigar, (size_t)cigar_total * 4 + 64)); CHECK(ensure(c, d.seqqual, (size_t)seq_total + 64));
-	col.cigar = P<uint32_t>(d.cigar);
+	CHECK(d.cols.reserve_variable(c, cigar_total, (size_t)seq_total, 1.0));
+	const ssv::DecodedCols col = d.cols.view();
+	const ssv::SamLineCols lines{P<uint64_t>(d.name_off), P<ssv_record>(d.rec)};
 	ssv::SamRefTable T{P<uint32_t>(d.ref_slots), d.ref_mask, P<uint32_t>(d.ref_off), P<uint8_t>(d.ref_blob)};
 	// where the last finished line ends (k_sam_fields puts NULs over the first tabs of finished lines only: the unfinished one is carried as it is)
 	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 17, P<uint32_t>(d.sep) + last_nl_sep, 4, hipMemcpyDeviceToHost, st));
-	k_sam_fields<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, reinterpret_cast<int32_t *>(sm + 8), errw);
-	k_sam_seqqual<<<(unsigned)std::min<int64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, P<int32_t>(d.l_qseq),
-	                                                                                                                 P<uint64_t>(d.seq_off), P<uint8_t>(d.seqqual), errw);
+	k_sam_fields<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, lines, reinterpret_cast<int32_t *>(sm + 8), errw);
+	k_sam_seqqual<<<(unsigned)std::min<int64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col.l_qseq, col.seq_off,
+	                                                                                                                 col.seqqual, errw);
 	HIPCHECK(c, hipGetLastError());
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
@@ -232,11 +226,9 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	d.info.n_records = n; d.info.lines_consumed = d.lines_done; d.info.carried_bytes = carry;
 	if (last) d.phase = ssv_samdec_state::ENDED;
 	d.have_batch = true;
-	out->n = n; out->max_ref_span = (int32_t)hs[8] > 0 ? (int32_t)hs[8] : 1;
-	out->tid = col.tid; out->pos = col.pos; out->flag = col.flag; out->mapq = col.mapq; out->n_cigar = col.n_cigar; out->l_qseq = col.l_qseq; out->mtid = col.mtid; out->mpos = col.mpos;
-	out->isize = col.isize; out->cigar_off = col.cigar_off; out->cigar = col.cigar; out->xc = col.xc; out->seq_off = col.seq_off; out->seqqual = P<uint8_t>(d.seqqual);
-	out->n_cigar_total = (int64_t)cigar_total; out->seqqual_bytes = (int64_t)seq_total;
-	out->rec = col.rec; out->cigar_ends = col.ends;
+	d.cols.fill(out, n, (int64_t)cigar_total, (int64_t)seq_total);
+	out->max_ref_span = (int32_t)hs[8] > 0 ? (int32_t)hs[8] : 1;
+	out->rec = lines.rec;
 	out->tid_runs = nullptr; out->n_tid_runs = 0;
 	return SSV_OK;
 }

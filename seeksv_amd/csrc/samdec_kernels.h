@@ -9,6 +9,7 @@
 // A line that is not well-formed puts (line << 8 | reason) into one device word by atomic-min: the decode call fails with the smallest line.
 #pragma once
 
+#include "batch_columns.h"
 #include "common.h"
 #include "seeksv_hip.h"
 
@@ -31,14 +32,10 @@ struct SamRefTable {
 	const uint8_t *blob;
 };
 
-struct SamColumns {
-	int32_t *tid, *pos, *l_qseq, *mtid, *mpos, *isize;
-	uint16_t *flag, *n_cigar;
-	uint8_t *mapq, *xc, *ends;
-	uint32_t *seq_bytes, *cigar_off;
-	uint64_t *seq_off, *name_off;
+// what only this decoder writes, beside the columns both decoders share (DecodedCols, batch_columns.h)
+struct SamLineCols {
+	uint64_t *name_off; // where the record's name starts in the text (ssv_samdec_names)
 	ssv_record *rec;
-	uint32_t *cigar;
 };
 
 // 0x80 in every byte of v that equals c
@@ -162,7 +159,7 @@ __device__ __forceinline__ uint32_t sam_shape(const uint8_t *__restrict__ text, 
 	return SAM_OK;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_sam_sizes(const uint8_t *__restrict__ text, const uint32_t *__restrict__ sep, const uint32_t *__restrict__ nlidx, int64_t n, SamColumns c,
+__global__ __launch_bounds__(BLOCK) void k_sam_sizes(const uint8_t *__restrict__ text, const uint32_t *__restrict__ sep, const uint32_t *__restrict__ nlidx, int64_t n, DecodedCols c,
                                                     unsigned long long *__restrict__ err)
 {
 	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -228,7 +225,7 @@ __device__ __forceinline__ int sam_cigar_code(uint32_t ch)
 	}
 }
 
-__global__ __launch_bounds__(BLOCK) void k_sam_fields(uint8_t *__restrict__ text, const uint32_t *__restrict__ sep, const uint32_t *__restrict__ nlidx, int64_t n, SamRefTable T, SamColumns c,
+__global__ __launch_bounds__(BLOCK) void k_sam_fields(uint8_t *__restrict__ text, const uint32_t *__restrict__ sep, const uint32_t *__restrict__ nlidx, int64_t n, SamRefTable T, DecodedCols c, SamLineCols x,
                                                      int32_t *__restrict__ max_span, unsigned long long *__restrict__ err)
 {
 	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -323,9 +320,9 @@ __global__ __launch_bounds__(BLOCK) void k_sam_fields(uint8_t *__restrict__ text
 			} else mine = ((unsigned long long)i << 8) | e;
 		}
 		c.tid[i] = tid; c.pos[i] = pos; c.mtid[i] = mtid; c.mpos[i] = mpos; c.isize[i] = isize;
-		c.flag[i] = (uint16_t)flag; c.mapq[i] = (uint8_t)mapq; c.xc[i] = (uint8_t)xc; c.ends[i] = (uint8_t)ends;
-		c.name_off[i] = L.start;
-		uint4 *p = reinterpret_cast<uint4 *>(c.rec + i);
+		c.flag[i] = (uint16_t)flag; c.mapq[i] = (uint8_t)mapq; c.xc[i] = (uint8_t)xc; c.cigar_ends[i] = (uint8_t)ends;
+		x.name_off[i] = L.start;
+		uint4 *p = reinterpret_cast<uint4 *>(x.rec + i);
 		p[0] = make_uint4((uint32_t)tid, (uint32_t)pos, flag | (mapq << 16) | (xc << 24), nc);
 		p[1] = make_uint4(lq, (uint32_t)mtid, (uint32_t)mpos, (uint32_t)isize);
 		p[2] = make_uint4(coff, h[0], h[1], h[2]);

@@ -27,6 +27,7 @@
 #include <memory>
 #include <vector>
 
+#include "batch_columns.h"
 #include "bamdec_kernels.h"
 #include "realign_kernels.h"
 #include "clip_kernels.h"
@@ -191,7 +192,7 @@ struct ssv_ctx { // (created and deleted below the stage files only: the state s
 	// staging of host batches, and the record lines built for batches that come without them
 	// host batches are copied into one of three staging sets: 0 and 1 take the batches announced with ssv_batch_prefetch (copied on st_h2d while
 	// the kernels of the batch before run on st), 2 the ones that come unannounced (copied on st itself)
-	struct StageSet { DBuf col[15], rec; hipEvent_t ready = nullptr; } ss[3];
+	struct StageSet { DBuf col[COL_COUNT], rec; hipEvent_t ready = nullptr; } ss[3];
 	struct Prefetched { ssv_batch_t b; int set; };
 	std::deque<Prefetched> pf;
 	uint64_t pf_count = 0;
@@ -203,7 +204,7 @@ struct ssv_ctx { // (created and deleted below the stage files only: the state s
 	HBuf h_counters, h_totals;
 	DBuf stage; int64_t stage_cap = 0; // the scans' staging of candidates (getclip, getsv)
 	DBuf ends_buf, ghist;              // cigar_ends built from the lines (getclip, getsv -F); radix histograms (getclip, getsv -F)
-	HBuf h_batch;                      // ssv_bamdec_batch_to_host
+	HBuf h_batch;                      // ssv_batch_to_host
 
 	hipStream_t st_copy = nullptr;
 	hipEvent_t ev_packed = nullptr;
@@ -544,6 +545,72 @@ int arena_alloc(ssv_ctx *c, Arena &a, size_t bytes, void **out)
 template <typename T> T *P(DBuf &b) { return reinterpret_cast<T *>(b.p); }
 template <typename T> T *P(HBuf &b) { return reinterpret_cast<T *>(b.p); }
 
+// a buffer's size when the call sizes everything for a chunk `grow` times as large as the one at hand (ssv_bamdec_expect; 1: as it is)
+inline size_t grown(size_t bytes, double grow) { return grow > 1.0 ? (size_t)((double)bytes * grow) + 64 : bytes; }
+
+// The device buffers of the columns both decoders write (ssv_bamdec_decode, ssv_samdec_decode): one per column of the table, and seq_bytes.
+struct DecodedColumns {
+	DBuf col[COL_COUNT], seq_bytes;
+	int reserve(ssv_ctx *c, size_t n, double grow) // the per-record columns
+	{
+		for (int k = 0; k < COL_COUNT; ++k) if (kBatchCols[k].len == LEN_N) CHECK(ensure(c, col[k], grown(n * kBatchCols[k].elem + 16, grow)));
+		return ensure(c, seq_bytes, grown(n * 4 + 16, grow));
+	}
+	int reserve_variable(ssv_ctx *c, size_t cigar_total, size_t seq_total, double grow) // the operations, the bases + qualities: once layout()'s totals are known
+	{
+		CHECK(ensure(c, col[COL_cigar], grown(cigar_total * 4 + 64, grow)));
+		return ensure(c, col[COL_seqqual], grown(seq_total + 64, grow));
+	}
+	DecodedCols view()
+	{
+		DecodedCols v;
+#define X(member, ...) v.member = static_cast<decltype(v.member)>(col[COL_##member].p);
+		SSV_BATCH_COLUMNS(X)
+#undef X
+		v.seq_bytes = P<uint32_t>(seq_bytes);
+		return v;
+	}
+	// n_cigar -> cigar_off, seq_bytes -> seq_off; the totals go to device memory of the caller's, read back with the rest of its small block
+	void layout(hipStream_t st, int64_t n, uint32_t *scratch32, uint64_t *scratch64, uint32_t *cigar_total, uint64_t *seq_total)
+	{
+		const DecodedCols v = view();
+		exclusive_scan<uint16_t, uint32_t>(st, v.n_cigar, v.cigar_off, n, 0u, scratch32, cigar_total);
+		exclusive_scan<uint32_t, uint64_t>(st, v.seq_bytes, v.seq_off, n, 0ull, scratch64, seq_total);
+	}
+	void fill(ssv_batch_t *out, int64_t n, int64_t cigar_total, int64_t seq_total) // the batch handed out (max_ref_span, rec, tid_runs: the caller's)
+	{
+		out->n = n; out->n_cigar_total = cigar_total; out->seqqual_bytes = seq_total;
+		for (int k = 0; k < COL_COUNT; ++k) col_set(*out, k, col[k].p);
+	}
+};
+
+// The one set of rules for an ssv_names_t argument (`what`: the entry point, for the message): a batch with records needs its names, and names that are
+// given say where they lie.
+int check_names(ssv_ctx *c, const ssv_names_t *nm, int64_t n, const char *what)
+{
+	const char *bad = nullptr;
+	if (n > 0 && (!nm || !nm->base || !nm->off)) bad = "a batch with records needs their names";
+	else if (nm && nm->mem != SSV_MEM_HOST && nm->mem != SSV_MEM_DEVICE) bad = "bad names.mem";
+	else if (nm && nm->bias < 0) bad = "names.bias below 0";
+	else if (nm && nm->mem == SSV_MEM_HOST && nm->bytes < 0) bad = "names.bytes below 0";
+	if (!bad) return SSV_OK;
+	c->err = std::string(what) + ": " + bad;
+	return SSV_E_ARG;
+}
+
+// The names of a batch of n > 0 records where the kernels read them: device names in place; host names copied into `blob` and `off` on c->st, 16 zero
+// bytes behind the blob (a name without its NUL ends there).
+int stage_names(ssv_ctx *c, const ssv_names_t *nm, int64_t n, DBuf &blob, DBuf &off, DevNames &out)
+{
+	if (nm->mem == SSV_MEM_DEVICE) { out = DevNames{nm->base, nm->off, nm->bias}; return SSV_OK; }
+	CHECK(ensure(c, blob, (size_t)nm->bytes + 16)); CHECK(ensure(c, off, (size_t)n * 8 + 16));
+	if (nm->bytes) HIPCHECK(c, hipMemcpyAsync(blob.p, nm->base, (size_t)nm->bytes, hipMemcpyHostToDevice, c->st));
+	HIPCHECK(c, hipMemsetAsync(P<char>(blob) + nm->bytes, 0, 16, c->st));
+	HIPCHECK(c, hipMemcpyAsync(off.p, nm->off, (size_t)n * 8, hipMemcpyHostToDevice, c->st));
+	out = DevNames{P<char>(blob), P<uint64_t>(off), nm->bias};
+	return SSV_OK;
+}
+
 struct ProfScope {
 	ssv_ctx *c;
 	int id;
@@ -603,39 +670,44 @@ static int upload_host_batch(ssv_ctx *c, const ssv_batch_t *b, int set, hipStrea
 {
 	const size_t n = (size_t)b->n;
 	ssv_ctx::StageSet &S = c->ss[set];
-	struct { const void *src; size_t bytes; } f[15] = {
-		{b->tid, n * 4}, {b->pos, n * 4}, {b->rec ? nullptr : b->flag, n * 2}, {b->rec ? nullptr : b->mapq, n}, {b->n_cigar, n * 2}, {b->rec ? nullptr : b->l_qseq, n * 4},
-		{b->rec ? nullptr : b->mtid, n * 4}, {b->rec ? nullptr : b->mpos, n * 4}, {b->rec ? nullptr : b->isize, n * 4}, {b->rec ? nullptr : b->cigar_off, n * 4},
-		{b->cigar, (size_t)b->n_cigar_total * 4}, {b->rec ? nullptr : b->xc, b->xc ? n : 0}, {b->rec ? nullptr : b->seq_off, n * 8}, {b->seqqual, (size_t)b->seqqual_bytes},
-		{b->cigar_ends, n}};
-	for (int k = 0; k < 15; ++k) {
-		if (!f[k].src) continue;
-		CHECK(ensure(c, S.col[k], f[k].bytes + 16));
-		if (f[k].bytes) HIPCHECK(c, hipMemcpyAsync(S.col[k].p, f[k].src, f[k].bytes, hipMemcpyHostToDevice, st));
+	for (int k = 0; k < COL_COUNT; ++k) {
+		const void *src = b->rec && kBatchCols[k].in_rec ? nullptr : col_get(*b, k);
+		if (!src) { if (kBatchCols[k].never_empty) CHECK(ensure(c, S.col[k], 16)); continue; }
+		const size_t bytes = col_bytes(*b, k);
+		CHECK(ensure(c, S.col[k], bytes + 16));
+		if (bytes) HIPCHECK(c, hipMemcpyAsync(S.col[k].p, src, bytes, hipMemcpyHostToDevice, st));
 	}
-	CHECK(ensure(c, S.col[10], 16)); CHECK(ensure(c, S.col[13], 16));
 	CHECK(ensure(c, S.rec, n * sizeof(ssv_record) + 64));
 	if (b->rec && n) HIPCHECK(c, hipMemcpyAsync(S.rec.p, b->rec, n * sizeof(ssv_record), hipMemcpyHostToDevice, st));
 	return SSV_OK;
 }
 
-// the device view of a host batch staged in set `set`
+// k_build_rec's source out of any set of column base pointers: at(COL_x) -> where column x lies
+template <typename At> static SoaCols soa_cols(At at)
+{
+	SoaCols s;
+#define X(member, ...) s.member = static_cast<decltype(s.member)>(at(COL_##member));
+	SSV_BATCH_COLUMNS(X)
+#undef X
+	return s;
+}
+
+// the device view of a host batch staged in set `set` (a column that may be NULL is NULL here when the batch came without it)
 static void staged_view(ssv_ctx *c, const ssv_batch_t *b, int set, DevBatch &d, SoaCols &s)
 {
 	ssv_ctx::StageSet &S = c->ss[set];
-	d.tid = P<int32_t>(S.col[0]); d.pos = P<int32_t>(S.col[1]); d.n_cigar = P<uint16_t>(S.col[4]); d.cigar = P<uint32_t>(S.col[10]); d.seqqual = P<uint8_t>(S.col[13]);
-	d.ends = b->cigar_ends ? P<uint8_t>(S.col[14]) : nullptr;
+	s = soa_cols([&](int k) -> const void * { return kBatchCols[k].nullable && !col_get(*b, k) ? nullptr : S.col[k].p; });
+	d.tid = s.tid; d.pos = s.pos; d.n_cigar = s.n_cigar; d.cigar = s.cigar; d.seqqual = s.seqqual; d.ends = s.cigar_ends;
 	d.rec = P<ssv_record>(S.rec);
-	s.tid = d.tid; s.pos = d.pos; s.flag = P<uint16_t>(S.col[2]); s.mapq = P<uint8_t>(S.col[3]); s.n_cigar = d.n_cigar; s.l_qseq = P<int32_t>(S.col[5]); s.mtid = P<int32_t>(S.col[6]);
-	s.mpos = P<int32_t>(S.col[7]); s.isize = P<int32_t>(S.col[8]); s.cigar_off = P<uint32_t>(S.col[9]); s.cigar = d.cigar; s.xc = b->xc ? P<uint8_t>(S.col[11]) : nullptr;
-	s.seq_off = P<uint64_t>(S.col[12]);
 }
 
 static int check_batch(ssv_ctx *c, const ssv_batch_t *b)
 {
 	if (!b || b->n < 0 || b->n >= (1ll << 31)) { c->err = "bad batch"; return SSV_E_ARG; }
-	const bool has_soa = b->flag && b->mapq && b->l_qseq && b->mtid && b->mpos && b->isize && b->cigar_off && b->seq_off;
-	if (b->n > 0 && (!b->tid || !b->pos || !b->n_cigar || (!b->rec && !has_soa))) { c->err = "batch with null arrays"; return SSV_E_ARG; }
+	bool complete = true; // the per-record columns that must be there: all but the nullable ones, or with `rec` those it does not stand in for
+	for (int k = 0; k < COL_COUNT; ++k)
+		if (kBatchCols[k].len == LEN_N && !kBatchCols[k].nullable && !(b->rec && kBatchCols[k].in_rec) && !col_get(*b, k)) complete = false;
+	if (b->n > 0 && !complete) { c->err = "batch with null arrays"; return SSV_E_ARG; }
 	const int mem = b->mem & ~(int)SSV_MEM_PERSISTENT;
 	if (mem != SSV_MEM_DEVICE && b->mem != SSV_MEM_HOST) { c->err = "bad batch.mem"; return SSV_E_ARG; }
 	return SSV_OK;
@@ -657,8 +729,7 @@ int stage_batch(ssv_ctx *c, const ssv_batch_t *b, DevBatch &d, bool keep_announc
 		if (b->cigar_ends && !aligned16(b->cigar_ends)) { c->err = "device batch arrays must be 16-byte aligned (rec: 64-byte aligned)"; return SSV_E_ARG; }
 		d.tid = b->tid; d.pos = b->pos; d.n_cigar = b->n_cigar; d.cigar = b->cigar; d.seqqual = b->seqqual; d.rec = b->rec; d.ends = b->cigar_ends;
 		if (d.rec || n == 0) return SSV_OK;
-		s.tid = b->tid; s.pos = b->pos; s.flag = b->flag; s.mapq = b->mapq; s.n_cigar = b->n_cigar; s.l_qseq = b->l_qseq; s.mtid = b->mtid; s.mpos = b->mpos; s.isize = b->isize;
-		s.cigar_off = b->cigar_off; s.cigar = b->cigar; s.xc = b->xc; s.seq_off = b->seq_off;
+		s = soa_cols([&](int k) { return col_get(*b, k); });
 		CHECK(ensure(c, c->ss[2].rec, n * sizeof(ssv_record) + 64));
 		rec_dst = P<ssv_record>(c->ss[2].rec);
 	} else {
@@ -789,6 +860,26 @@ int ssv_batch_prefetch_drop(ssv_ctx *c)
 
 const char *ssv_last_error(const ssv_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 void *ssv_stream(ssv_ctx *c) { return c ? (void *)c->st : nullptr; }
+
+// test/debug helper: a device batch as a host batch (arrays owned by the context, valid until the next call)
+int ssv_batch_to_host(ssv_ctx *c, const ssv_batch_t *dev, ssv_batch_t *host)
+{
+	if (!c || !dev || !host || dev->mem != SSV_MEM_DEVICE) return SSV_E_ARG;
+	size_t off[COL_COUNT + 1]; off[0] = 0; // every column 64-byte aligned
+	for (int k = 0; k < COL_COUNT; ++k) off[k + 1] = off[k] + ((col_bytes(*dev, k) + 63) & ~(size_t)63);
+	CHECK(ensure_host(c, c->h_batch, off[COL_COUNT] + 64));
+	uint8_t *base = P<uint8_t>(c->h_batch);
+	for (int k = 0; k < COL_COUNT; ++k) {
+		const void *src = col_get(*dev, k);
+		if (src && col_bytes(*dev, k)) HIPCHECK(c, hipMemcpyAsync(base + off[k], src, col_bytes(*dev, k), hipMemcpyDeviceToHost, c->st));
+	}
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	*host = *dev;
+	host->mem = SSV_MEM_HOST;
+	for (int k = 0; k < COL_COUNT; ++k) col_set(*host, k, kBatchCols[k].nullable && !col_get(*dev, k) ? nullptr : base + off[k]);
+	host->rec = nullptr; // (the lines stay on the device: the host batch is the classic columns)
+	return SSV_OK;
+}
 
 // ---- a batch kept: the decoded records of a file stay in HBM for the passes that follow ----
 int ssv_batch_retain(ssv_ctx *c, const ssv_batch_t *b, ssv_batch_t *out)

@@ -83,3 +83,38 @@ def test_getsv_begin_refuses_unsorted_windows(ctx):
     p = _abi.GetsvParams()
     p.windows = w.ctypes.data; p.n_windows = 2; p.n_targets = 1; p.target_len = lens.ctypes.data; p.times = 4
     assert ctx._lib.ssv_getsv_begin(ctx._h, C.byref(p)) == E_ARG and "sorted" in _err(ctx)
+
+
+@pytest.mark.parametrize("call", ["ssv_rt_scan", "ssv_aln_pack"])
+def test_names_argument_is_checked_the_same_way(ctx, call):
+    """host names with bytes = -1, then mem = 5, then bias = -1: E_ARG with a message from either call that takes an ssv_names_t, and nothing allocated or
+    left half done - the context then runs a normal getclip on the batch"""
+    import sam_text as ST
+    lib, h = ctx._lib, ctx._h
+    path = os.path.join(G.GOLDEN, "getclip", "filters.bam")
+    _, _, batches = host.read_bam(path)
+    assert len(batches) == 1
+    qnames = [r["qname"] for r in ST.read_bam_full(path)[1]]
+    b, keep = _abi.make_batch(batches[0])
+    assert b.n == len(qnames) > 0
+    good, keep_names = ctx._as_names(qnames)
+    out = _abi.AlnCols()
+    if call == "ssv_rt_scan":
+        ctx.rt_begin(1, ["c%d" % k for k in range(int(batches[0]["tid"].max()) + 1)])
+        scan = lambda nm: lib.ssv_rt_scan(h, C.byref(b), C.byref(nm))
+    else:
+        scan = lambda nm: lib.ssv_aln_pack(h, C.byref(b), C.byref(nm), C.byref(out))
+    for field, value in (("bytes", -1), ("mem", 5), ("bias", -1)):
+        nm = _abi.Names(good.mem, 0, good.bias, good.base, good.off, good.bytes)
+        setattr(nm, field, value)
+        assert scan(nm) == E_ARG, field
+        assert call in _err(ctx) and field in _err(ctx), (field, _err(ctx))
+    want = type(ctx)(0)
+    try:
+        ref = want.getclip(batches)
+    finally:
+        want.close()
+    got = ctx.getclip(batches)
+    assert got["n_clusters"] == ref["n_clusters"] > 0
+    for k in ref:
+        assert np.array_equal(got[k], ref[k]), k
