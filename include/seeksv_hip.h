@@ -594,14 +594,30 @@ typedef struct {
 	int32_t n_mismatch;
 	uint8_t reverse;     /* flag 16 */
 	uint8_t mapq;        /* 0 when another locus scores as well, 60 when the runner-up is >= 10 behind */
-	uint8_t pad[2];
+	uint8_t pad[2];      /* pad[0]: SSV_RA_F_* of the query's seed set - written by the sorted index only (the hash index writes 0), also for an unaligned query; pad[1]: 0 */
 } ssv_realign_hit;
+#define SSV_RA_F_MASKED 1   /* a 20-mer of the query occurs more than max_occ times among the indexed positions and gave no seed */
+#define SSV_RA_F_OVERFLOW 2 /* the query has more seeds than candidate slots (192): the rarest were followed, some were left out */
 
 /* Build the index.  ref2bit: base i of the concatenated contigs at bits [2 (i % 32), +2) of word i / 32, A C G T = 0 1 2 3 (the
  * caller decides what N becomes); target_off[n_targets + 1] = first base of every contig, target_off[0] = 0, target_off[n_targets] =
  * n_bases.  SSV_MEM_DEVICE arrays are used in place and need one readable word after the last one.  *n_dropped (optional) = sampled
  * positions that found no slot within the probe limit (low-complexity sequence). */
 int ssv_realign_index(ssv_ctx *ctx, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped);
+/* The same reference as a SORTED index, for references with repeats: the sampled 20-mers sorted, equal ones next to each other with ascending positions;
+ * nothing is dropped and there is no probe limit.  Same arguments, checks and 32-bit sample limit as ssv_realign_index; max_occ in 1..65535 (else
+ * SSV_E_ARG) is bwa mem's -c: a query 20-mer with more occurrences gives no seed (SSV_RA_F_MASKED).  Queries on this index admit their seeds rarest first -
+ * by class ceil(log2(occurrences)), then strand, query offset, reference position - until the 192 candidate slots are full (SSV_RA_F_OVERFLOW when seeds
+ * were left out), and candidates equal in score, strand and diagonal go to the smaller contig id: every field of a hit is a function of the input.
+ * Building either kind of index replaces the other; ssv_realign_query uses the one that was built last; ssv_realign_free frees either. */
+typedef struct {
+	int64_t n_indexed;   /* sampled positions whose 20-mer lies inside one contig */
+	int64_t n_distinct;  /* distinct 20-mers among them */
+	int64_t occ_max;     /* occurrences of the most frequent one */
+	int64_t n_over_cap;  /* distinct 20-mers with more than max_occ occurrences */
+} ssv_realign_index_stats;
+int ssv_realign_index_sorted(ssv_ctx *ctx, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int32_t max_occ,
+                             ssv_realign_index_stats *stats /* may be NULL */);
 /* Align n ASCII sequences (host memory, concatenated; seq_off[n + 1]) -> hits[n] (host).  Queries shorter than 20 or longer than 1024
  * bases come back unaligned. */
 int ssv_realign_query(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits);

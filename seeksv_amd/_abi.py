@@ -321,7 +321,12 @@ def host_lib():
 
 
 REALIGN_HIT = [("tid", "<i4"), ("pos", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"), ("score", "<i4"), ("second", "<i4"), ("n_mismatch", "<i4"),
-               ("reverse", "u1"), ("mapq", "u1"), ("pad", "u1", (2,))]  # ssv_realign_hit
+               ("reverse", "u1"), ("mapq", "u1"), ("pad", "u1", (2,))]  # ssv_realign_hit; pad[:, 0] = RA_F_* (sorted index)
+RA_F_MASKED, RA_F_OVERFLOW = 1, 2
+
+
+class RealignIndexStats(C.Structure):  # ssv_realign_index_stats
+    _fields_ = [("n_indexed", C.c_int64), ("n_distinct", C.c_int64), ("occ_max", C.c_int64), ("n_over_cap", C.c_int64)]
 
 
 def hip_lib():
@@ -375,6 +380,7 @@ def hip_lib():
         lib.ssv_bamdec_last.argtypes = [V, C.POINTER(BamdecInfo)]
         lib.ssv_batch_to_host.argtypes = [V, C.POINTER(Batch), C.POINTER(Batch)]
         lib.ssv_realign_index.argtypes = [V, V, C.c_int32, C.c_int64, V, C.c_int32, C.POINTER(C.c_int64)]
+        lib.ssv_realign_index_sorted.argtypes = [V, V, C.c_int32, C.c_int64, V, C.c_int32, C.c_int32, C.POINTER(RealignIndexStats)]
         lib.ssv_realign_query.argtypes = [V, V, V, C.c_int64, V]
         lib.ssv_realign_free.argtypes = [V]
         lib.ssv_prof_enable.argtypes = [V, C.c_int]

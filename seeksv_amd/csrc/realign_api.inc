@@ -1,7 +1,10 @@
-// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h)
+// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h and realign_sorted_kernels.h)
 
 struct ssv_realign_state {
 	DBuf ref, ctg, table, seqs, offs, hits, dropped;
+	DBuf skeys, svals, sdir; // the sorted index (ssv_realign_index_sorted); a context holds one kind of index at a time
+	bool sorted = false;
+	int32_t dir_bits = 0, max_occ = 0;
 	const uint64_t *ref_p = nullptr; // device pointer used by the kernels (own copy or the caller's resident array)
 	int64_t n_bases = 0;
 	int32_t n_ctg = 0;
@@ -9,14 +12,9 @@ struct ssv_realign_state {
 	bool ready = false;
 };
 
-int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped)
+// the reference and the contig offsets on the device (both kinds of index)
+static int realign_reference(ssv_ctx *c, ssv_realign_state &R, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets)
 {
-	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
-	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
-	HIPCHECK(c, hipSetDevice(c->device));
-	if (!c->ra) c->ra.reset(new ssv_realign_state());
-	ssv_realign_state &R = *c->ra;
-	R.ready = false;
 	const size_t words = (size_t)((n_bases + 31) / 32);
 	if (mem == SSV_MEM_DEVICE) R.ref_p = ref2bit; // resident: used in place; the caller keeps one readable word of slack after it
 	else {
@@ -27,6 +25,24 @@ int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t 
 	}
 	CHECK(ensure(c, R.ctg, (size_t)(n_targets + 1) * 8));
 	HIPCHECK(c, hipMemcpyAsync(R.ctg.p, target_off, (size_t)(n_targets + 1) * 8, hipMemcpyHostToDevice, c->st));
+	R.n_bases = n_bases; R.n_ctg = n_targets;
+	return SSV_OK;
+}
+
+int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped)
+{
+	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
+	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	if (!c->ra) c->ra.reset(new ssv_realign_state());
+	ssv_realign_state &R = *c->ra;
+	R.ready = false;
+	if (R.sorted) { // the hash index replaces a sorted one
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+		for (DBuf *b : {&R.skeys, &R.svals, &R.sdir}) HIPCHECK(c, b->release());
+		R.sorted = false;
+	}
+	CHECK(realign_reference(c, R, ref2bit, mem, n_bases, target_off, n_targets));
 	const int64_t samples = (n_bases + RA_SAMPLE - 1) / RA_SAMPLE;
 	uint64_t slots = 1024;
 	while (slots < (uint64_t)samples * 2) slots <<= 1;
@@ -34,7 +50,7 @@ int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t 
 	HIPCHECK(c, hipMemsetAsync(R.table.p, 0, slots * 4, c->st));
 	CHECK(ensure(c, R.dropped, 8));
 	HIPCHECK(c, hipMemsetAsync(R.dropped.p, 0, 8, c->st));
-	R.n_bases = n_bases; R.n_ctg = n_targets; R.mask = slots - 1;
+	R.mask = slots - 1;
 	RaIndex ix;
 	ix.ref = R.ref_p; ix.n_bases = n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = n_targets; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
 	{
@@ -46,6 +62,60 @@ int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t 
 	HIPCHECK(c, hipMemcpyAsync(&d, R.dropped.p, 8, hipMemcpyDeviceToHost, c->st));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
 	if (n_dropped) *n_dropped = (int64_t)d;
+	R.ready = true;
+	return SSV_OK;
+}
+
+// The sorted index: keys, six passes of the stable radix sort, the directory, the statistics (realign_sorted_kernels.h).  The sort's second pair of
+// buffers, its histograms and the statistics' partial sums are freed when the index stands.
+int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int32_t max_occ, ssv_realign_index_stats *stats)
+{
+	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
+	if (max_occ < 1 || max_occ > 65535) { c->err = "max_occ outside 1..65535"; return SSV_E_ARG; }
+	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	if (!c->ra) c->ra.reset(new ssv_realign_state());
+	ssv_realign_state &R = *c->ra;
+	R.ready = false;
+	if (R.table.p) { // the sorted index replaces a hash index
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+		for (DBuf *b : {&R.table, &R.dropped}) HIPCHECK(c, b->release());
+		R.mask = 0;
+	}
+	R.sorted = true;
+	CHECK(realign_reference(c, R, ref2bit, mem, n_bases, target_off, n_targets));
+	const int64_t samples = (n_bases + RA_SAMPLE - 1) / RA_SAMPLE;
+	int bits = 0;
+	while (bits < 30 && ((int64_t)2 << bits) <= samples) ++bits; // floor(log2(samples)), at most 30
+	const int64_t nt = rs_tiles(samples), n_part = (samples + RAS_STATS_TILE - 1) / RAS_STATS_TILE;
+	DBuf keys2, vals2, ghist, scratch, part;
+	CHECK(ensure(c, R.skeys, (size_t)samples * 8)); CHECK(ensure(c, R.svals, (size_t)samples * 4)); CHECK(ensure(c, R.sdir, (((size_t)1 << bits) + 1) * 4));
+	CHECK(ensure(c, keys2, (size_t)samples * 8)); CHECK(ensure(c, vals2, (size_t)samples * 4));
+	CHECK(ensure(c, ghist, (size_t)256 * nt * 4)); CHECK(ensure(c, scratch, (size_t)scan_scratch_elems(256 * nt) * 4));
+	CHECK(ensure(c, part, (size_t)(n_part + 1) * sizeof(RasStats)));
+	RaIndex ix;
+	ix.ref = R.ref_p; ix.n_bases = n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = n_targets; ix.table = nullptr; ix.mask = 0;
+	uint64_t *keys[2] = {P<uint64_t>(R.skeys), P<uint64_t>(keys2)};
+	uint32_t *vals[2] = {P<uint32_t>(R.svals), P<uint32_t>(vals2)};
+	static_assert(((RAS_KEY_BITS + 7) / 8) % 2 == 0, "an even number of passes: the sorted pairs end in the buffers they started in");
+	uint32_t n_indexed = 0;
+	RasStats st;
+	const uint32_t *dir_end = P<uint32_t>(R.sdir) + ((size_t)1 << bits); // = the number of indexed positions
+	{
+		ProfScope ps(c, P_REALIGN_INDEX, samples);
+		k_ras_keys<<<grid_for(samples, BLOCK), BLOCK, 0, c->st>>>(ix, samples, keys[0], vals[0]);
+		const int cur = radix_sort_pairs(c->st, keys, vals, samples, RAS_KEY_BITS, P<uint32_t>(ghist), P<uint32_t>(scratch));
+		if (cur != 0) { c->err = "sorted index: the sort ended in its second buffer"; return SSV_E_STATE; }
+		k_ras_dir<<<grid_for(((int64_t)1 << bits) + 1, BLOCK), BLOCK, 0, c->st>>>(keys[0], samples, bits, P<uint32_t>(R.sdir));
+		k_ras_stats<<<(unsigned)n_part, BLOCK, 0, c->st>>>(keys[0], dir_end, (uint32_t)max_occ, P<RasStats>(part));
+		k_ras_stats_sum<<<1, BLOCK, 0, c->st>>>(P<RasStats>(part), n_part, P<RasStats>(part) + n_part);
+	}
+	HIPCHECK(c, hipGetLastError());
+	HIPCHECK(c, hipMemcpyAsync(&n_indexed, dir_end, 4, hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipMemcpyAsync(&st, P<RasStats>(part) + n_part, sizeof(st), hipMemcpyDeviceToHost, c->st));
+	HIPCHECK(c, hipStreamSynchronize(c->st));
+	if (stats) { stats->n_indexed = (int64_t)n_indexed; stats->n_distinct = (int64_t)st.n_distinct; stats->occ_max = (int64_t)st.occ_max; stats->n_over_cap = (int64_t)st.n_over_cap; }
+	R.dir_bits = bits; R.max_occ = max_occ;
 	R.ready = true;
 	return SSV_OK;
 }
@@ -62,12 +132,22 @@ int ssv_realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int
 	CHECK(ensure(c, R.seqs, bytes + 16)); CHECK(ensure(c, R.offs, (size_t)(n + 1) * 8)); CHECK(ensure(c, R.hits, (size_t)n * sizeof(RaHit)));
 	HIPCHECK(c, hipMemcpyAsync(R.seqs.p, seqs, bytes, hipMemcpyHostToDevice, c->st));
 	HIPCHECK(c, hipMemcpyAsync(R.offs.p, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->st));
-	RaQueryArgs a;
-	a.ix.ref = R.ref_p; a.ix.n_bases = R.n_bases; a.ix.ctg_off = P<int64_t>(R.ctg); a.ix.n_ctg = R.n_ctg; a.ix.table = P<uint32_t>(R.table); a.ix.mask = R.mask;
-	a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
+	RaIndex ix;
+	ix.ref = R.ref_p; ix.n_bases = R.n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = R.n_ctg; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
 	{
 		ProfScope ps(c, P_REALIGN_QUERY, n);
-		k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		if (R.sorted) {
+			RasQueryArgs a;
+			a.ix = ix;
+			a.sx.keys = P<uint64_t>(R.skeys); a.sx.vals = P<uint32_t>(R.svals); a.sx.dir = P<uint32_t>(R.sdir); a.sx.bits = R.dir_bits; a.sx.max_occ = R.max_occ;
+			a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
+			k_ras_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		} else {
+			RaQueryArgs a;
+			a.ix = ix;
+			a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
+			k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		}
 	}
 	HIPCHECK(c, hipGetLastError());
 	HIPCHECK(c, hipMemcpyAsync(hits, R.hits.p, (size_t)n * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));

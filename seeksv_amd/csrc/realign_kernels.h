@@ -7,7 +7,8 @@
 // (the synthetic genomes of bench / tests): a k-mer index of the reference in HBM, seed look-ups for every k-mer of a query on
 // both strands, ungapped extension with bwa mem's default scores (match 1, mismatch 4, end clipping 5, report >= 30).
 // It does not reproduce bwa's alignments bit for bit (no gapped extension, no chaining, no supplementary records; at most
-// RA_MAX_CAND seed hits per query are followed, probe runs longer than RA_MAX_PROBE are cut).
+// RA_MAX_CAND seed hits per query are followed, probe runs longer than RA_MAX_PROBE are cut).  References with repeats take the second, sorted
+// index of realign_sorted_kernels.h: the same query kernel (k_ra_query_t below) with another seed stage.
 //
 // Index: every SAMPLE-th reference position p whose K-mer lies inside one contig is a slot of an open-addressing table
 // (u32 slot = p / SAMPLE + 1, 0 = empty; linear probing; load <= 1/2); a slot does not hold its key - a look-up checks the K-mer
@@ -114,7 +115,13 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 // penalty (bwa mem's rule); every candidate's score stays in LDS.  5. best locus over the lanes, then the runner-up over ALL scored
 // candidates (a lane scores one candidate per round of 64 and keeps only its best: the lanes' bests alone would miss a runner-up
 // that the winner's lane scored in another round, and a sequence present twice would come back with MAPQ 60) -> hit.
-__global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
+// The kernel is a template over the seed stage, so that the sorted index (realign_sorted_kernels.h: ras_seeds fills the same candidate arrays, rarest seeds
+// first, and sets the hit's flags) shares coding and steps 3-5 with the hash index; SORTED also sends candidates equal in score, strand and diagonal to
+// the smaller contig id, where the hash index leaves them to the order of the lanes.  k_ra_query = k_ra_query_t<false, RaQueryArgs> is the hash index's
+// kernel (a profiler shows the template's name).  (A template KERNEL, not a __device__ body called from two kernels: inlined from a function hipcc compiled
+// the hash path to other code - 52 VGPRs for 60 - that ran slower; this form measures like the kernel before it)
+template <bool SORTED, typename Args>
+__global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 {
 	__shared__ uint8_t s_code[WAVES_PER_BLOCK][2][RA_MAX_Q];
 	__shared__ int64_t s_diag[WAVES_PER_BLOCK][RA_MAX_CAND];
@@ -139,7 +146,10 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	// ---- seeds ----
-	for (int st = 0; st < 2; ++st) {
+	if constexpr (SORTED) { // ras_seeds: realign_sorted_kernels.h, which includes this file and is the only place that instantiates SORTED (found there by argument-dependent look-up)
+		const int filled = ras_seeds(a, w, lane, n, s_code, s_diag, s_ss, s_tid, &out.pad[0]);
+		if (lane == 0) s_n[w] = filled;
+	} else for (int st = 0; st < 2; ++st) {
 		const uint8_t *code = s_code[w][st];
 		for (int o = lane; o + RA_K <= n; o += WAVE) {
 			uint64_t km = 0;
@@ -205,19 +215,21 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 		s_ss[w][c] = (uint16_t)((st << 15) | bs);
 		int mm = 0;
 		for (int i = bb; i < be; ++i) mm += (code[i] < 4 && (uint32_t)code[i] == ra_base_at(ix.ref, d + i)) ? 0 : 1;
-		const bool better = bs > best_score || (bs == best_score && best_tid >= 0 && (st < best_st || (st == best_st && d < best_diag)));
+		const bool better = bs > best_score || (bs == best_score && best_tid >= 0 && (st < best_st || (st == best_st && (d < best_diag || (SORTED && d == best_diag && t < best_tid)))));
 		if (better) { best_score = bs; best_beg = bb; best_end = be; best_mm = mm; best_st = st; best_diag = d; best_tid = t; }
 	}
 	// ---- best locus over the lanes; second best = best score among all candidates that are not the winner's neighbourhood ----
-	int win_score = best_score, win_lane = lane;
+	int win_score = best_score, win_lane = lane, win_t = best_tid; // (win_t: SORTED only)
 	int64_t win_diag = best_diag;
 	int win_st = best_st;
 #pragma unroll
 	for (int dlt = 32; dlt >= 1; dlt >>= 1) {
 		const int os = __shfl_xor(win_score, dlt, 64), ol = __shfl_xor(win_lane, dlt, 64), ost = __shfl_xor(win_st, dlt, 64);
 		const int64_t od = __shfl_xor(win_diag, dlt, 64);
-		const bool take = os > win_score || (os == win_score && os > 0 && (ost < win_st || (ost == win_st && (od < win_diag || (od == win_diag && ol < win_lane)))));
-		if (take) { win_score = os; win_lane = ol; win_diag = od; win_st = ost; }
+		const int ot = SORTED ? __shfl_xor(win_t, dlt, 64) : 0;
+		const bool first = SORTED ? (ot < win_t || (ot == win_t && ol < win_lane)) : ol < win_lane;
+		const bool take = os > win_score || (os == win_score && os > 0 && (ost < win_st || (ost == win_st && (od < win_diag || (od == win_diag && first)))));
+		if (take) { win_score = os; win_lane = ol; win_diag = od; win_st = ost; win_t = ot; }
 	}
 	if (win_score < RA_MIN_SCORE) { if (lane == 0) a.hits[q] = out; return; }
 	const int win_tid = __shfl(best_tid, win_lane, 64);
@@ -241,5 +253,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query(RaQueryArgs a)
 		a.hits[q] = out;
 	}
 }
+
+constexpr auto k_ra_query = k_ra_query_t<false, RaQueryArgs>;
 
 } // namespace ssv

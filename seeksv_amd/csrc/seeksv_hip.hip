@@ -30,6 +30,7 @@
 #include "batch_columns.h"
 #include "bamdec_kernels.h"
 #include "realign_kernels.h"
+#include "realign_sorted_kernels.h"
 #include "clip_kernels.h"
 #include "table3_kernels.h"
 #include "tile_sort.h"

@@ -406,6 +406,15 @@ class Context:
         self._check(self._lib.ssv_realign_index(self._h, ptr, mem, int(off[-1]), off.ctypes.data, len(off) - 1, C.byref(dropped)), "ssv_realign_index")
         return dropped.value
 
+    def realign_index_sorted(self, ref2bit, target_off, max_occ, mem=_abi.MEM_HOST):
+        """the sorted index (references with repeats): query 20-mers with more than max_occ occurrences give no seed.  Arguments as realign_index;
+        -> dict(n_indexed, n_distinct, occ_max, n_over_cap).  realign() then uses this index; its flags are hits["pad"][:, 0] (_abi.RA_F_*)."""
+        off = np.ascontiguousarray(target_off, np.int64)
+        ptr = ref2bit.ctypes.data if isinstance(ref2bit, np.ndarray) else int(ref2bit)
+        st = _abi.RealignIndexStats()
+        self._check(self._lib.ssv_realign_index_sorted(self._h, ptr, mem, int(off[-1]), off.ctypes.data, len(off) - 1, int(max_occ), C.byref(st)), "ssv_realign_index_sorted")
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def realign(self, seqs):
         """list of str -> numpy structured array of ssv_realign_hit"""
         blob = "".join(seqs).encode()

@@ -1859,13 +1859,36 @@ static int cmd_somatic(int argc, char **argv)
 // seeksv realign: prefix.clip.fq.gz -> prefix.clip.bam.  The reference's pipeline runs an external aligner here
 // (README.md:22-34, example/seeksv.sh:3: `bwa mem ref.fa prefix.clip.fq.gz | samtools view -Sb - > prefix.clip.bam`); this is the
 // stand-in for hosts without bwa (ssv_realign_*, include/seeksv_hip.h): one record per clipped sequence, in FASTQ order, the
-// read name is the sequence.  Meant for references that behave like random sequence (synthetic genomes); no gapped alignment.
+// read name is the sequence.  No gapped alignment.  The default (hash) index is meant for references that behave like random sequence (synthetic
+// genomes); -c selects the sorted index, which keeps every copy of a repeat, skips seeds with more occurrences than the cap and follows the rarest first.
 // ---------------------------------------------------------------------------------------------------------------------
 [[noreturn]] static void usage_realign()
 {
 	cerr << "Usage: seeksv realign [options] <reference fasta(.gz)> <input clipped reads (*.clip.fq.gz)> <output clip.bam>\n\n"
+	     << "         -c <int>              skip seeds with more than INT occurrences; selects the sorted index (1..65535; bwa mem's -c, there 500) [hash index, no cap]\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
+}
+
+// -c of `seeksv realign` (and of `seeksv run -a`): 0 = not a cap
+static int parse_max_occ(const char *arg)
+{
+	char *end = nullptr;
+	const long v = strtol(arg, &end, 10);
+	return (end != arg && *end == 0 && v >= 1 && v <= 65535) ? (int)v : 0;
+}
+
+// realign's options, for `seeksv realign` itself and for the words of `seeksv run -a`; *gpu stays as it is without -G.  -> index of the first operand
+static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ)
+{
+	int c;
+	optind = 1;
+	while ((c = getopt(argc, argv, "G:c:")) != -1) {
+		if (c == 'G') *gpu = atoi(optarg);
+		else if (c == 'c') { if (!(*max_occ = parse_max_occ(optarg))) usage_realign(); }
+		else usage_realign();
+	}
+	return optind;
 }
 
 static bool gz_getline(gzFile f, string &line)
@@ -2041,7 +2064,7 @@ struct AlignedRecords {
 	vector<uint32_t> cig_off, cig;
 	vector<uint64_t> seq_off;
 	vector<const char *> qn;
-	int64_t n_aligned = 0;
+	int64_t n_aligned = 0, n_masked = 0, n_over = 0; // (the last two: SSV_RA_F_* of the sorted index)
 	int64_t size() const { return (int64_t)tid.size(); }
 };
 // the sequences through the aligner (ssv_realign_query) and their records appended to `out`
@@ -2083,6 +2106,7 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 			const int L = seqs[(size_t)i].n;
 			const bool al = h.tid >= 0;
 			out.n_aligned += al ? 1 : 0;
+			out.n_masked += (h.pad[0] & SSV_RA_F_MASKED) ? 1 : 0; out.n_over += (h.pad[0] & SSV_RA_F_OVERFLOW) ? 1 : 0;
 			cig_off[i] = co; seq_off[i] = so;
 			ncig[i] = (uint16_t)(al ? 1 + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
 			co += ncig[i]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
@@ -2139,6 +2163,21 @@ static void write_clip_bam(const string &out_bam, const Reference &R, AlignedRec
 	if (ssvh_bam_write_batch_named(out_bam.c_str(), tn.data(), R.lens.data(), (int32_t)R.names.size(), &b, A.qn.data(), 0, 1) != 0) die(string("[seeksv] ") + ssvh_last_error());
 }
 
+// the index `seeksv realign` / `seeksv run` asked for: max_occ == 0 the hash index, else the sorted one with that cap
+static void build_realign_index(ssv_ctx *ctx, const Reference &R, int max_occ, int64_t *dropped)
+{
+	const int rc = max_occ ? ssv_realign_index_sorted(ctx, R.words.data(), SSV_MEM_HOST, R.offs.back(), R.offs.data(), (int32_t)R.names.size(), max_occ, nullptr)
+	                       : ssv_realign_index(ctx, R.words.data(), SSV_MEM_HOST, R.offs.back(), R.offs.data(), (int32_t)R.names.size(), dropped);
+	if (rc != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
+}
+
+static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ)
+{
+	string t = "[seeksv realign] " + to_string(A.size()) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
+	if (!max_occ) return t + (dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string());
+	return t + (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
+}
+
 static void resident_alignments(seeksv::AlnRecords &R)
 {
 	const AlignedRecords &A = *g_resident.aln.rec;
@@ -2148,11 +2187,8 @@ static void resident_alignments(seeksv::AlnRecords &R)
 
 static int cmd_realign(int argc, char **argv)
 {
-	int gpu = 0, c;
-	while ((c = getopt(argc, argv, "G:")) != -1) {
-		if (c == 'G') gpu = atoi(optarg); else usage_realign();
-	}
-	if (argc - optind != 3) usage_realign();
+	int gpu = 0, max_occ = 0;
+	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ) != 3) usage_realign();
 	const string fasta = argv[optind], fq = argv[optind + 1], out_bam = argv[optind + 2];
 	PhaseTimer pt;
 	Reference R;
@@ -2184,11 +2220,10 @@ static int cmd_realign(int argc, char **argv)
 			seqs.push_back(l2); quals.push_back(l4);
 		}
 	}
-	const int64_t n = (int64_t)seqs.size();
 	pt.lap("read fastq");
 	ssv_ctx *ctx = acquire_ctx(gpu);
 	int64_t dropped = 0;
-	if (ssv_realign_index(ctx, R.words.data(), SSV_MEM_HOST, R.offs.back(), R.offs.data(), (int32_t)R.names.size(), &dropped) != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
+	build_realign_index(ctx, R, max_occ, &dropped);
 	pt.lap("index");
 	AlignedRecords A;
 	align_lines(ctx, seqs, quals, A);
@@ -2199,7 +2234,7 @@ static int cmd_realign(int argc, char **argv)
 	setenv("SSV_BGZF_LEVEL", "-1", 0);
 	write_clip_bam(out_bam, R, A);
 	pt.lap("write bam");
-	cerr << "[seeksv realign] " << n << " clipped sequences, " << A.n_aligned << " aligned" << (dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string()) << endl;
+	cerr << realign_summary(A, dropped, max_occ) << endl;
 	ssv_realign_free(ctx);
 	release_ctx(ctx);
 	return 0;
@@ -2218,6 +2253,7 @@ struct RunAligner {
 	Reference R;
 	AlignedRecords A;
 	int64_t dropped = 0;
+	int max_occ = 0; // -a "-c INT": the sorted index
 	double t_index = 0, t_align = 0, t_wait_ref = 0;
 	void start(int device, const string &fasta)
 	{
@@ -2229,7 +2265,7 @@ struct RunAligner {
 			read_reference(fasta, R);
 			t_wait_ref = std::chrono::duration<double>(now() - t0).count();
 			t0 = now();
-			if (ssv_realign_index(ctx, R.words.data(), SSV_MEM_HOST, R.offs.back(), R.offs.data(), (int32_t)R.names.size(), &dropped) != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
+			build_realign_index(ctx, R, max_occ, &dropped);
 			t_index = std::chrono::duration<double>(now() - t0).count();
 			for (;;) {
 				vector<ResidentBam::Piece *> pass;
@@ -2283,6 +2319,7 @@ struct RunAligner {
 	     << "records stay in HBM for the getsv passes (80 bytes a record).\n\n"
 	     << "Options: -c <string>           options handed to getclip, e.g. -c \"-q 5 -s\"\n"
 	     << "         -v <string>           options handed to getsv, e.g. -v \"-b 5 -L 100\"\n"
+	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500\" (the GPU is chosen by -G here)\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -2298,17 +2335,29 @@ static vector<string> split_words(const string &t)
 static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0;
-	string clip_opts, sv_opts;
-	while ((c = getopt(argc, argv, "c:v:G:")) >= 0) {
+	string clip_opts, sv_opts, aln_opts;
+	while ((c = getopt(argc, argv, "c:v:a:G:")) >= 0) {
 		switch (c) {
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
+		case 'a': aln_opts = optarg; break;
 		case 'G': device = atoi(optarg); break;
 		default: usage_run();
 		}
 	}
 	if (argc != optind + 3) usage_run();
 	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
+	int max_occ = 0;
+	{ // realign's options, parsed as `seeksv realign` parses them; the GPU is run's own -G
+		vector<string> w = {"realign"};
+		for (auto &x : split_words(aln_opts)) w.push_back(x);
+		vector<char *> av;
+		for (auto &x : w) av.push_back(const_cast<char *>(x.c_str()));
+		av.push_back(nullptr);
+		int aln_gpu = -1;
+		if (parse_realign_options((int)w.size(), av.data(), &aln_gpu, &max_occ) != (int)w.size()) usage_realign();
+		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
+	}
 	PhaseTimer pt;
 	g_resident.ctx = acquire_ctx(device);
 	g_resident.path = bam;
@@ -2317,6 +2366,7 @@ static int cmd_run(int argc, char **argv)
 	g_preread.path = fasta; g_preread.offs.assign(1, 0);
 	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
 	RunAligner &aligner = *new RunAligner; // (never destroyed: die() may exit while its thread runs)
+	aligner.max_occ = max_occ;
 	aligner.start(device, fasta);
 	g_resident.on_pass = [&aligner](const vector<ResidentBam::Piece *> &pass) { aligner.submit(pass); };
 	auto call = [&](int (*fn)(int, char **), vector<string> words) {
@@ -2342,7 +2392,7 @@ static int cmd_run(int argc, char **argv)
 		g_resident.aln.bam_path = prefix + ".clip.bam"; g_resident.aln.rec = &aligner.A; g_resident.aln.names = aligner.R.names;
 		// (written under a temporary name and renamed when it is whole: a run that dies in getsv must not leave half a clip.bam where `seeksv getsv` would find it)
 		g_resident.bam_writer = std::thread([&aligner] { write_clip_bam(g_resident.aln.bam_path + ".tmp", aligner.R, aligner.A); });
-		cerr << "[seeksv realign] " << aligner.A.size() << " clipped sequences, " << aligner.A.n_aligned << " aligned" << (aligner.dropped ? ", " + to_string(aligner.dropped) + " repetitive index positions dropped" : string()) << endl;
+		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ) << endl;
 		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
 		a = {"getsv"};
 		for (auto &w : split_words(sv_opts)) a.push_back(w);

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """The GPU re-aligner (ssv_realign_*) at the size of the bench workload: index of the whole synthetic genome (generated in
 HBM), then queries cut from it - half of them real placements (both strands, 0.5 % substitutions), half random sequence like the bulk of
-a sample's soft clips.  usage: python tools/realign_bench.py [genome_frac] [n_queries] [query_len]"""
+a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [genome_frac] [n_queries] [query_len]
+--index both builds and queries the two kinds of index in one process, alternating (hash, sorted, hash, sorted, ...), R times each: one JSON line
+with a list of rounds per kind.  Index bytes are computed from the sizes the library allocates, not measured."""
+import argparse
 import json
 import os
 import sys
@@ -15,10 +18,29 @@ from seeksv_amd import _abi, synth  # noqa: E402
 from seeksv_amd.device import Context  # noqa: E402
 
 
+def index_bytes(kind, samples):
+    """(bytes the index keeps, bytes allocated while it is built) for ceil(n_bases / 4) sampled positions"""
+    if kind == "hash":
+        slots = 1024
+        while slots < 2 * samples:
+            slots <<= 1
+        return 4 * slots, 4 * slots
+    bits = min(30, max(0, int(samples).bit_length() - 1))
+    kept = 12 * samples + 4 * ((1 << bits) + 1)
+    tiles = (samples + 2047) // 2048
+    return kept, kept + 12 * samples + 4 * 256 * tiles
+
+
 def main():
-    frac = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
-    nq = int(sys.argv[2]) if len(sys.argv) > 2 else 2_000_000
-    qlen = int(sys.argv[3]) if len(sys.argv) > 3 else 60
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--index", choices=["hash", "sorted", "both"], default="hash")
+    ap.add_argument("--max-occ", type=int, default=500)
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("genome_frac", nargs="?", type=float, default=1.0)
+    ap.add_argument("n_queries", nargs="?", type=int, default=2_000_000)
+    ap.add_argument("query_len", nargs="?", type=int, default=60)
+    args = ap.parse_args()
+    frac, nq, qlen = args.genome_frac, args.n_queries, args.query_len
     import torch
     w = synth.Workload(genome_frac=frac, depth=1, n_sv=0)
     t = time.perf_counter()
@@ -27,9 +49,6 @@ def main():
     t_ref = time.perf_counter() - t
     ctx = Context(0)
     ctx.prof_enable(1)
-    t = time.perf_counter()
-    dropped = ctx.realign_index(words.data_ptr(), off, _abi.MEM_DEVICE)
-    t_index = time.perf_counter() - t
     # queries
     rng = np.random.RandomState(11)
     G = int(off[-1])
@@ -50,22 +69,40 @@ def main():
     lut = np.frombuffer(b"ACGT", np.uint8)
     text = lut[allc].tobytes().decode()
     seqs = [text[i * qlen:(i + 1) * qlen] for i in range(nq)]
-    t = time.perf_counter()
-    hits = ctx.realign(seqs)
-    t_query = time.perf_counter() - t
-    prof = ctx.prof_all()
     is_real = order < n_real
     exp_tid = np.full(nq, -1)
     exp_tid[is_real] = tid[order[is_real]]
     exp_pos = np.full(nq, -1, np.int64)
     exp_pos[is_real] = (start - off[tid])[order[is_real]]
-    ok_real = int(((hits["tid"] == exp_tid) & (hits["pos"] - hits["q_beg"] == exp_pos) & (hits["mapq"] > 0))[is_real].sum())
-    junk_unaligned = int((hits["tid"][~is_real] == -1).sum())
-    out = {"genome_bases": G, "reference_2bit_s": round(t_ref, 3), "index_wall_s": round(t_index, 3), "index_kernel_ms": round(prof["realign_index"]["total_ms"], 2),
-           "index_positions_per_s": round(G / 4 / (prof["realign_index"]["total_ms"] * 1e-3)), "index_dropped": dropped, "table_GB": round(4 * (1 << int(np.ceil(np.log2(G / 4 * 2)))) / 1e9, 2),
-           "queries": nq, "query_len": qlen, "query_wall_s": round(t_query, 3), "query_kernel_ms": round(prof["realign_query"]["total_ms"], 2),
-           "queries_per_s_kernel": round(nq / (prof["realign_query"]["total_ms"] * 1e-3)), "real_placed_correctly": ok_real, "real": int(is_real.sum()),
-           "junk_unaligned": junk_unaligned, "junk": int((~is_real).sum())}
+    samples = (G + 3) // 4
+
+    def one(kind):
+        ctx.prof_reset()
+        t = time.perf_counter()
+        if kind == "hash":
+            built = {"index_dropped": ctx.realign_index(words.data_ptr(), off, _abi.MEM_DEVICE)}
+        else:
+            built = {"index_stats": ctx.realign_index_sorted(words.data_ptr(), off, args.max_occ, _abi.MEM_DEVICE), "max_occ": args.max_occ}
+        t_index = time.perf_counter() - t
+        t = time.perf_counter()
+        hits = ctx.realign(seqs)
+        t_query = time.perf_counter() - t
+        prof = ctx.prof_all()
+        ok_real = int(((hits["tid"] == exp_tid) & (hits["pos"] - hits["q_beg"] == exp_pos) & (hits["mapq"] > 0))[is_real].sum())
+        kept, peak = index_bytes(kind, samples)
+        flags = hits["pad"][:, 0]
+        return dict(built, index_wall_s=round(t_index, 3), index_kernel_ms=round(prof["realign_index"]["total_ms"], 2),
+                    index_positions_per_s=round(samples / (prof["realign_index"]["total_ms"] * 1e-3)), index_GB=round(kept / 1e9, 2), index_build_GB=round(peak / 1e9, 2),
+                    query_wall_s=round(t_query, 3), query_kernel_ms=round(prof["realign_query"]["total_ms"], 2),
+                    queries_per_s_kernel=round(nq / (prof["realign_query"]["total_ms"] * 1e-3)), real_placed_correctly=ok_real,
+                    junk_unaligned=int((hits["tid"][~is_real] == -1).sum()), masked=int((flags & 1).astype(bool).sum()), over_limit=int((flags & 2).astype(bool).sum()))
+
+    kinds = ["hash", "sorted"] if args.index == "both" else [args.index]
+    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int((~is_real).sum()),
+           "rounds": {k: [] for k in kinds}}
+    for _ in range(args.rounds):
+        for k in kinds:
+            out["rounds"][k].append(one(k))
     print(json.dumps(out))
 
 
