@@ -257,7 +257,7 @@ static int cluster_sort(ssv_ctx *c, bool fmt3, int *cur)
 	if (EL > 1) k_check_sorted<<<grid_for(EL, BLOCK), BLOCK, 0, c->st>>>(P<uint64_t>(C.key_l), EL, &dc->l_unsorted);
 	if (EL > 0) k_key_max<<<(unsigned)std::min<int64_t>(512, grid_for(EL, BLOCK)), BLOCK, 0, c->st>>>(P<uint64_t>(C.key_l), EL, &dc->max_key);
 	if (ER > 0) k_key_max<<<(unsigned)std::min<int64_t>(512, grid_for(ER, BLOCK)), BLOCK, 0, c->st>>>(P<uint64_t>(C.key_r[0]), ER, &dc->max_key);
-	// the '3' list is sorted up to small displacements: one windowed rank pass, checked (tile_sort.h); SSV_RADIX_ONLY=1 skips the attempt
+	// the '3' list is sorted up to small displacements: one windowed rank pass, checked (tile_sort.h); where the check fails (r_unsorted) the radix sort below takes over - the attempt is always made, there is no switch for it
 	if (ER > 0) { CHECK(ensure(c, C.key_r[1], ER * 8)); CHECK(ensure(c, C.val_r[1], ER * 4)); }
 	if (ER > 0) HIPCHECK(c, sort_nearly_sorted(c->st, P<uint64_t>(C.key_r[0]), P<uint32_t>(C.val_r[0]), P<uint64_t>(C.key_r[1]), P<uint32_t>(C.val_r[1]), ER, &dc->r_unsorted));
 	if (fmt3) {

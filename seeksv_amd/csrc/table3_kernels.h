@@ -368,6 +368,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack3_stream(PackArgs p, Pack3Args q,
 			}
 		}
 		uint32_t seen_lo = 0, seen_hi = 0; // TRACK: phred 0..63 as a bit set in registers (anything higher goes straight to LDS)
+		                                   // (a read without qualities - 0xff bytes - shows no value: 255 is no letter of the alphabet)
 		uint32_t miss = 0;                 // OR of the table look-ups: 0xff marks a value outside the alphabet
 		if constexpr (W == 0) { // grouped qualities, group by group out of the staged bytes (this kernel is the direct one's stand-in for alphabets with a phred value >= 64 and the TRACK launch)
 			const int B = p.qual_bits, K = p.qual_group;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack3_stream(PackArgs p, Pack3Args q,
 				uint64_t acc = 0;
 				for (int g = g0; B * g < 32 * t + 32 && K * g < n; ++g)
 					acc |= (uint64_t)qual_group_code(s_lut, K, (uint32_t)p.qual_radix, K * g, n, miss, [&](int i) { return (uint32_t)qbytes[i]; },
-					                                 [&](uint32_t ph) { if (TRACK) { if (ph < 32) seen_lo |= 1u << ph; else if (ph < 64) seen_hi |= 1u << (ph - 32); else atomicOr(&s_seen[ph >> 5], 1u << (ph & 31)); } }) << (B * (g - g0));
+					                                 [&](uint32_t ph) { if (TRACK && !qmiss) { if (ph < 32) seen_lo |= 1u << ph; else if (ph < 64) seen_hi |= 1u << (ph - 32); else atomicOr(&s_seen[ph >> 5], 1u << (ph & 31)); } }) << (B * (g - g0));
 				d[nDb + t] = qmiss ? 0u : (uint32_t)(acc >> off);
 			}
 		} else
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void k_pack3_stream(PackArgs p, Pack3Args q,
 					const uint32_t idx = s_lut[ph];
 					acc |= (uint64_t)(idx & ((1u << W) - 1u)) << (jq * W);
 					miss |= jq < rem ? idx : 0u;
-					if (TRACK && jq < rem) { if (ph < 32) seen_lo |= 1u << ph; else if (ph < 64) seen_hi |= 1u << (ph - 32); else atomicOr(&s_seen[ph >> 5], 1u << (ph & 31)); }
+					if (TRACK && !qmiss && jq < rem) { if (ph < 32) seen_lo |= 1u << ph; else if (ph < 64) seen_hi |= 1u << (ph - 32); else atomicOr(&s_seen[ph >> 5], 1u << (ph & 31)); }
 				}
 				if (rem < CNT) acc &= (1ull << (W * rem)) - 1ull;
 				v = qmiss ? 0u : (uint32_t)(acc >> off); // no qualities: the row prints "*", the stream stays zero
