@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
+                             v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
                              v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
                              v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
                              v9: ssv_table_block_bytes(left_len, right_len) lost the parameters of the removed formats; ssv_bamdec_info.unmapped_raw stays valid for one more decode.
@@ -621,6 +622,19 @@ int ssv_realign_index_sorted(ssv_ctx *ctx, const uint64_t *ref2bit, int32_t mem,
 /* Align n ASCII sequences (host memory, concatenated; seq_off[n + 1]) -> hits[n] (host).  Queries shorter than 20 or longer than 1024
  * bases come back unaligned. */
 int ssv_realign_query(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits);
+/* The same with one insertion or deletion per alignment (`seeksv realign -g`).  The first stage keeps candidates that score 20 or more (second still
+ * counts those at 30 or more only), then the winner - and only the winner - is tried with one gap of 1..16 bases on either side of its segment
+ * (bwa mem's scores: a gap of L costs 6 + L): the winner's segment keeps one end and becomes one piece, the other piece is the best segment on the
+ * neighbouring diagonal that starts (ends) at the gap, extended to the query's end by the rule of the ungapped stage.  The gapped alignment replaces
+ * the ungapped one when it scores strictly more: pos, q_beg, q_end, score, n_mismatch (inserted bases are not counted) and mapq (from the new score
+ * and the unchanged second) are updated, tid, reverse, second and pad[0] stay.  Of equal gapped alignments: the leftmost gap, then the shorter gap,
+ * a deletion before an insertion.  A hit below 30 after this is unaligned in every field but pad[0].  Gaps longer than 16 bases, a second gap and
+ * the runner-up are not looked at.  Works on the index that was built last; arguments and errors as ssv_realign_query, gaps[n] (host) is required. */
+typedef struct {
+	int32_t q_at;        /* query base (in the hit's orientation) behind the gap's left edge */
+	int32_t len;         /* > 0: deletion of len reference bases before query base q_at; < 0: query bases [q_at, q_at - len) are inserted; 0: none */
+} ssv_realign_gap;
+int ssv_realign_query_gapped(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps);
 int ssv_realign_free(ssv_ctx *ctx);
 
 /* ---- getsv -F: junctions from read-through split alignments: replaces FindJunction (process_bwasw.cpp:5-227, seeksv.cpp:221-225) -----------

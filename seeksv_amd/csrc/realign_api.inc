@@ -1,7 +1,7 @@
-// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h and realign_sorted_kernels.h)
+// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h and realign_gap_kernels.h)
 
 struct ssv_realign_state {
-	DBuf ref, ctg, table, seqs, offs, hits, dropped;
+	DBuf ref, ctg, table, seqs, offs, hits, gaps, dropped;
 	DBuf skeys, svals, sdir; // the sorted index (ssv_realign_index_sorted); a context holds one kind of index at a time
 	bool sorted = false;
 	int32_t dir_bits = 0, max_occ = 0;
@@ -120,39 +120,68 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 	return SSV_OK;
 }
 
-int ssv_realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits)
+// the query kernel of the index that stands - its instantiation with the candidate floor at RA_K when `floor` - over the n sequences in R.seqs / R.offs -> R.hits
+static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor)
 {
-	if (!c || n < 0 || (n > 0 && (!seqs || !seq_off || !hits))) return SSV_E_ARG;
-	if (!c->ra || !c->ra->ready) { if (c) c->err = "ssv_realign_query before ssv_realign_index"; return SSV_E_STATE; }
+	RaIndex ix;
+	ix.ref = R.ref_p; ix.n_bases = R.n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = R.n_ctg; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
+	ProfScope ps(c, P_REALIGN_QUERY, n);
+	if (R.sorted) {
+		RasQueryArgs a;
+		a.ix = ix;
+		a.sx.keys = P<uint64_t>(R.skeys); a.sx.vals = P<uint32_t>(R.svals); a.sx.dir = P<uint32_t>(R.sdir); a.sx.bits = R.dir_bits; a.sx.max_occ = R.max_occ;
+		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
+		if (floor) k_ras_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		else k_ras_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+	} else {
+		RaQueryArgs a;
+		a.ix = ix;
+		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
+		if (floor) k_ra_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		else k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+	}
+}
+
+// ssv_realign_query (gaps == nullptr) and ssv_realign_query_gapped; `who` names the caller in the error text
+static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps, bool gapped, const char *who)
+{
+	if (!c || n < 0 || (n > 0 && (!seqs || !seq_off || !hits || (gapped && !gaps)))) return SSV_E_ARG;
+	if (!c->ra || !c->ra->ready) { c->err = std::string(who) + " before ssv_realign_index"; return SSV_E_STATE; }
 	if (n == 0) return SSV_OK;
 	static_assert(sizeof(RaHit) == sizeof(ssv_realign_hit), "hit layout");
+	static_assert(sizeof(RaGap) == sizeof(ssv_realign_gap), "gap layout");
 	HIPCHECK(c, hipSetDevice(c->device));
 	ssv_realign_state &R = *c->ra;
 	const uint64_t bytes = seq_off[n];
 	CHECK(ensure(c, R.seqs, bytes + 16)); CHECK(ensure(c, R.offs, (size_t)(n + 1) * 8)); CHECK(ensure(c, R.hits, (size_t)n * sizeof(RaHit)));
+	if (gapped) CHECK(ensure(c, R.gaps, (size_t)n * sizeof(RaGap)));
 	HIPCHECK(c, hipMemcpyAsync(R.seqs.p, seqs, bytes, hipMemcpyHostToDevice, c->st));
 	HIPCHECK(c, hipMemcpyAsync(R.offs.p, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->st));
-	RaIndex ix;
-	ix.ref = R.ref_p; ix.n_bases = R.n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = R.n_ctg; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
-	{
-		ProfScope ps(c, P_REALIGN_QUERY, n);
-		if (R.sorted) {
-			RasQueryArgs a;
-			a.ix = ix;
-			a.sx.keys = P<uint64_t>(R.skeys); a.sx.vals = P<uint32_t>(R.svals); a.sx.dir = P<uint32_t>(R.sdir); a.sx.bits = R.dir_bits; a.sx.max_occ = R.max_occ;
-			a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-			k_ras_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-		} else {
-			RaQueryArgs a;
-			a.ix = ix;
-			a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-			k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-		}
-	}
+	realign_launch_query(c, R, n, gapped);
 	HIPCHECK(c, hipGetLastError());
+	if (gapped) {
+		RaGapArgs g;
+		g.ref = R.ref_p; g.ctg_off = P<int64_t>(R.ctg); g.seqs = P<char>(R.seqs); g.seq_off = P<uint64_t>(R.offs); g.n = n; g.hits = P<RaHit>(R.hits); g.gaps = P<RaGap>(R.gaps);
+		{
+			ProfScope ps(c, P_REALIGN_GAP, n);
+			k_ra_gap<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(g);
+		}
+		HIPCHECK(c, hipGetLastError());
+		HIPCHECK(c, hipMemcpyAsync(gaps, R.gaps.p, (size_t)n * sizeof(RaGap), hipMemcpyDeviceToHost, c->st));
+	}
 	HIPCHECK(c, hipMemcpyAsync(hits, R.hits.p, (size_t)n * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
 	return SSV_OK;
+}
+
+int ssv_realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits)
+{
+	return realign_query(c, seqs, seq_off, n, hits, nullptr, false, "ssv_realign_query");
+}
+
+int ssv_realign_query_gapped(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps)
+{
+	return realign_query(c, seqs, seq_off, n, hits, gaps, true, "ssv_realign_query_gapped");
 }
 
 int ssv_realign_free(ssv_ctx *c)

@@ -6,7 +6,7 @@
 // getsv.h:445-527).  This is a stand-in for that step on hosts without bwa, for references that behave like random sequence
 // (the synthetic genomes of bench / tests): a k-mer index of the reference in HBM, seed look-ups for every k-mer of a query on
 // both strands, ungapped extension with bwa mem's default scores (match 1, mismatch 4, end clipping 5, report >= 30).
-// It does not reproduce bwa's alignments bit for bit (no gapped extension, no chaining, no supplementary records; at most
+// It does not reproduce bwa's alignments bit for bit (one gap per alignment at the most, and only on request: realign_gap_kernels.h; no chaining, no supplementary records; at most
 // RA_MAX_CAND seed hits per query are followed, probe runs longer than RA_MAX_PROBE are cut).  References with repeats take the second, sorted
 // index of realign_sorted_kernels.h: the same query kernel (k_ra_query_t below) with another seed stage.
 //
@@ -120,7 +120,10 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 // the smaller contig id, where the hash index leaves them to the order of the lanes.  k_ra_query = k_ra_query_t<false, RaQueryArgs> is the hash index's
 // kernel (a profiler shows the template's name).  (A template KERNEL, not a __device__ body called from two kernels: inlined from a function hipcc compiled
 // the hash path to other code - 52 VGPRs for 60 - that ran slower; this form measures like the kernel before it)
-template <bool SORTED, typename Args>
+// FLOOR is the score a candidate needs to be kept and a winner to be reported: RA_MIN_SCORE, or RA_K for the gapped query (realign_gap_kernels.h: k_ra_gap
+// refines the winner and applies RA_MIN_SCORE to what it leaves; `second` counts candidates at RA_MIN_SCORE or more only).  At the default every
+// FLOOR test is the one the kernel had before the parameter.
+template <bool SORTED, typename Args, int FLOOR = RA_MIN_SCORE>
 __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 {
 	__shared__ uint8_t s_code[WAVES_PER_BLOCK][2][RA_MAX_Q];
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 			run += eq ? RA_MATCH : -RA_MISMATCH;
 			if (run > bs) { bs = run; bb = run_beg; be = i + 1; }
 		}
-		if (bs < RA_MIN_SCORE) continue;
+		if (bs < FLOOR) continue;
 		// extension to the query's ends (only possible when the end lies inside the contig)
 		if (bb > i_lo || be < i_hi) {
 			int sc = 0;
@@ -231,7 +234,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		const bool take = os > win_score || (os == win_score && os > 0 && (ost < win_st || (ost == win_st && (od < win_diag || (od == win_diag && first)))));
 		if (take) { win_score = os; win_lane = ol; win_diag = od; win_st = ost; win_t = ot; }
 	}
-	if (win_score < RA_MIN_SCORE) { if (lane == 0) a.hits[q] = out; return; }
+	if (win_score < FLOOR) { if (lane == 0) a.hits[q] = out; return; }
 	const int win_tid = __shfl(best_tid, win_lane, 64);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		const int sc = s_ss[w][c] & 0x7fff;
 		const int64_t d = s_diag[w][c];
 		const bool same_locus = (s_ss[w][c] >> 15) == win_st && s_tid[w][c] == win_tid && (d - win_diag <= 32 && win_diag - d <= 32);
-		if (sc > second && !same_locus) second = sc;
+		if (sc > second && !same_locus && (FLOOR == RA_MIN_SCORE || sc >= RA_MIN_SCORE)) second = sc;
 	}
 	second = wave_max(second);
 	if (lane == win_lane) {
@@ -255,5 +258,6 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 }
 
 constexpr auto k_ra_query = k_ra_query_t<false, RaQueryArgs>;
+constexpr auto k_ra_query_floor = k_ra_query_t<false, RaQueryArgs, RA_K>; // the gapped query's first stage
 
 } // namespace ssv

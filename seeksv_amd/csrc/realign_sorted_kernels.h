@@ -22,7 +22,7 @@
 //               run's first entry up again and copies its positions, which already ascend.  Admission stops at RA_MAX_CAND slots; seeds left out: flag
 //               SSV_RA_F_OVERFLOW.  No LDS atomic orders anything: every field of every hit is a function of the input.
 //   ties        candidates equal in score, strand and diagonal go to the smaller contig id.
-// Still not bwa: no gapped extension, no chaining, no supplementary records, one record per query.
+// Still not bwa: one gap per alignment at the most (realign_gap_kernels.h), no chaining, no supplementary records, one record per query.
 #pragma once
 
 #include "common.h"
@@ -239,5 +239,6 @@ __device__ __forceinline__ int ras_seeds(const RasQueryArgs &a, int w, int lane,
 }
 
 constexpr auto k_ras_query = k_ra_query_t<true, RasQueryArgs>;
+constexpr auto k_ras_query_floor = k_ra_query_t<true, RasQueryArgs, RA_K>; // the gapped query's first stage
 
 } // namespace ssv

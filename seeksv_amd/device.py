@@ -415,14 +415,20 @@ class Context:
         self._check(self._lib.ssv_realign_index_sorted(self._h, ptr, mem, int(off[-1]), off.ctypes.data, len(off) - 1, int(max_occ), C.byref(st)), "ssv_realign_index_sorted")
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
-    def realign(self, seqs):
-        """list of str -> numpy structured array of ssv_realign_hit"""
+    def realign(self, seqs, gapped=False):
+        """list of str -> numpy structured array of ssv_realign_hit; gapped: one insertion or deletion per alignment (ssv_realign_query_gapped)
+        -> (hits, structured array of ssv_realign_gap)"""
         blob = "".join(seqs).encode()
         off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.uint64)
         hits = np.zeros(len(seqs), dtype=np.dtype(_abi.REALIGN_HIT))
+        if not gapped:
+            if len(seqs):
+                self._check(self._lib.ssv_realign_query(self._h, C.c_char_p(blob), off.ctypes.data, len(seqs), hits.ctypes.data), "ssv_realign_query")
+            return hits
+        gaps = np.zeros(len(seqs), dtype=np.dtype(_abi.REALIGN_GAP))
         if len(seqs):
-            self._check(self._lib.ssv_realign_query(self._h, C.c_char_p(blob), off.ctypes.data, len(seqs), hits.ctypes.data), "ssv_realign_query")
-        return hits
+            self._check(self._lib.ssv_realign_query_gapped(self._h, C.c_char_p(blob), off.ctypes.data, len(seqs), hits.ctypes.data, gaps.ctypes.data), "ssv_realign_query_gapped")
+        return hits, gaps
 
     # ---- measurement ----
     def prof_enable(self, mode=1):

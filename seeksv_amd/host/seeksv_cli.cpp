@@ -1859,13 +1859,14 @@ static int cmd_somatic(int argc, char **argv)
 // seeksv realign: prefix.clip.fq.gz -> prefix.clip.bam.  The reference's pipeline runs an external aligner here
 // (README.md:22-34, example/seeksv.sh:3: `bwa mem ref.fa prefix.clip.fq.gz | samtools view -Sb - > prefix.clip.bam`); this is the
 // stand-in for hosts without bwa (ssv_realign_*, include/seeksv_hip.h): one record per clipped sequence, in FASTQ order, the
-// read name is the sequence.  No gapped alignment.  The default (hash) index is meant for references that behave like random sequence (synthetic
+// read name is the sequence.  No gapped alignment unless -g asks for it (one insertion or deletion of up to 16 bases per record).  The default (hash) index is meant for references that behave like random sequence (synthetic
 // genomes); -c selects the sorted index, which keeps every copy of a repeat, skips seeds with more occurrences than the cap and follows the rarest first.
 // ---------------------------------------------------------------------------------------------------------------------
 [[noreturn]] static void usage_realign()
 {
 	cerr << "Usage: seeksv realign [options] <reference fasta(.gz)> <input clipped reads (*.clip.fq.gz)> <output clip.bam>\n\n"
 	     << "         -c <int>              skip seeds with more than INT occurrences; selects the sorted index (1..65535; bwa mem's -c, there 500) [hash index, no cap]\n"
+	     << "         -g                    allow one insertion or deletion of 1..16 bases per alignment (M, I / D, M; gap open 6, extend 1) [ungapped]\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -1879,12 +1880,13 @@ static int parse_max_occ(const char *arg)
 }
 
 // realign's options, for `seeksv realign` itself and for the words of `seeksv run -a`; *gpu stays as it is without -G.  -> index of the first operand
-static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ)
+static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped)
 {
 	int c;
 	optind = 1;
-	while ((c = getopt(argc, argv, "G:c:")) != -1) {
+	while ((c = getopt(argc, argv, "G:c:g")) != -1) {
 		if (c == 'G') *gpu = atoi(optarg);
+		else if (c == 'g') *gapped = true;
 		else if (c == 'c') { if (!(*max_occ = parse_max_occ(optarg))) usage_realign(); }
 		else usage_realign();
 	}
@@ -2064,11 +2066,11 @@ struct AlignedRecords {
 	vector<uint32_t> cig_off, cig;
 	vector<uint64_t> seq_off;
 	vector<const char *> qn;
-	int64_t n_aligned = 0, n_masked = 0, n_over = 0; // (the last two: SSV_RA_F_* of the sorted index)
+	int64_t n_aligned = 0, n_masked = 0, n_over = 0, n_gapped = 0; // (n_masked, n_over: SSV_RA_F_* of the sorted index; n_gapped: records with an I / D, -g)
 	int64_t size() const { return (int64_t)tid.size(); }
 };
-// the sequences through the aligner (ssv_realign_query) and their records appended to `out`
-static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out)
+// the sequences through the aligner (ssv_realign_query, or ssv_realign_query_gapped when `gapped`) and their records appended to `out`
+static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out, bool gapped)
 {
 	const int64_t n = (int64_t)seqs.size();
 	if (!n) return;
@@ -2082,7 +2084,9 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 		for (const Line &q : seqs) { blob.append(q.p, (size_t)q.n); soff.push_back(blob.size()); }
 	}
 	vector<ssv_realign_hit> hits((size_t)n);
-	if (ssv_realign_query(ctx, blob.data(), soff.data(), n, hits.data()) != SSV_OK) die(string("[seeksv] realign query: ") + ssv_last_error(ctx));
+	vector<ssv_realign_gap> gaps((size_t)n, ssv_realign_gap{0, 0}); // (all zero without -g)
+	const int rc = gapped ? ssv_realign_query_gapped(ctx, blob.data(), soff.data(), n, hits.data(), gaps.data()) : ssv_realign_query(ctx, blob.data(), soff.data(), n, hits.data());
+	if (rc != SSV_OK) die(string("[seeksv] realign query: ") + ssv_last_error(ctx));
 	const size_t at = (size_t)out.size();
 	for (auto *v : {&out.tid, &out.pos, &out.lq}) v->resize(at + (size_t)n);
 	out.mtid.resize(at + (size_t)n, -1); out.mpos.resize(at + (size_t)n, -1); out.isz.resize(at + (size_t)n, 0);
@@ -2108,7 +2112,9 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 			out.n_aligned += al ? 1 : 0;
 			out.n_masked += (h.pad[0] & SSV_RA_F_MASKED) ? 1 : 0; out.n_over += (h.pad[0] & SSV_RA_F_OVERFLOW) ? 1 : 0;
 			cig_off[i] = co; seq_off[i] = so;
-			ncig[i] = (uint16_t)(al ? 1 + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
+			const bool gap = al && gaps[(size_t)i].len != 0;
+			out.n_gapped += gap ? 1 : 0;
+			ncig[i] = (uint16_t)(al ? 1 + (gap ? 2 : 0) + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
 			co += ncig[i]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
 		}
 		out.cig.resize(co, 0);
@@ -2130,7 +2136,14 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 				if (al) {
 					uint32_t *c = cig + cig_off[i];
 					if (h.q_beg > 0) *c++ = ((uint32_t)h.q_beg << 4) | 4u;
-					*c++ = ((uint32_t)(h.q_end - h.q_beg) << 4) | 0u;
+					const ssv_realign_gap &g = gaps[(size_t)i];
+					if (g.len == 0) *c++ = ((uint32_t)(h.q_end - h.q_beg) << 4) | 0u;
+					else { // M, D / I, M: the hit's coordinates are those of its own orientation, which is the record's
+						const int32_t j = g.len > 0 ? g.q_at : g.q_at - g.len;
+						*c++ = ((uint32_t)(g.q_at - h.q_beg) << 4) | 0u;
+						*c++ = g.len > 0 ? (((uint32_t)g.len << 4) | 2u) : (((uint32_t)-g.len << 4) | 1u);
+						*c++ = ((uint32_t)(h.q_end - j) << 4) | 0u;
+					}
 					if (h.q_end < L) *c++ = ((uint32_t)(L - h.q_end) << 4) | 4u;
 				}
 				uint8_t *sp = seqqual + seq_off[i], *qp = sp + ((size_t)L + 1) / 2;
@@ -2171,9 +2184,10 @@ static void build_realign_index(ssv_ctx *ctx, const Reference &R, int max_occ, i
 	if (rc != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
 }
 
-static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ)
+static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped)
 {
 	string t = "[seeksv realign] " + to_string(A.size()) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
+	if (gapped) t += ", " + to_string(A.n_gapped) + " with a gap";
 	if (!max_occ) return t + (dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string());
 	return t + (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
 }
@@ -2188,7 +2202,8 @@ static void resident_alignments(seeksv::AlnRecords &R)
 static int cmd_realign(int argc, char **argv)
 {
 	int gpu = 0, max_occ = 0;
-	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ) != 3) usage_realign();
+	bool gapped = false;
+	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped) != 3) usage_realign();
 	const string fasta = argv[optind], fq = argv[optind + 1], out_bam = argv[optind + 2];
 	PhaseTimer pt;
 	Reference R;
@@ -2226,7 +2241,7 @@ static int cmd_realign(int argc, char **argv)
 	build_realign_index(ctx, R, max_occ, &dropped);
 	pt.lap("index");
 	AlignedRecords A;
-	align_lines(ctx, seqs, quals, A);
+	align_lines(ctx, seqs, quals, A, gapped);
 	pt.lap("align");
 	A.seqqual.resize(A.seqqual.size() + 16, 0);
 	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
@@ -2234,7 +2249,7 @@ static int cmd_realign(int argc, char **argv)
 	setenv("SSV_BGZF_LEVEL", "-1", 0);
 	write_clip_bam(out_bam, R, A);
 	pt.lap("write bam");
-	cerr << realign_summary(A, dropped, max_occ) << endl;
+	cerr << realign_summary(A, dropped, max_occ, gapped) << endl;
 	ssv_realign_free(ctx);
 	release_ctx(ctx);
 	return 0;
@@ -2254,6 +2269,7 @@ struct RunAligner {
 	AlignedRecords A;
 	int64_t dropped = 0;
 	int max_occ = 0; // -a "-c INT": the sorted index
+	bool gapped = false; // -a "-g"
 	double t_index = 0, t_align = 0, t_wait_ref = 0;
 	void start(int device, const string &fasta)
 	{
@@ -2285,7 +2301,7 @@ struct RunAligner {
 						seqs.push_back(Line{base + r.seq_off, (int)r.seq_len}); quals.push_back(Line{base + r.qual_off, (int)r.qual_len});
 					}
 				}
-				align_lines(ctx, seqs, quals, A);
+				align_lines(ctx, seqs, quals, A, gapped);
 				t_align += std::chrono::duration<double>(now() - t0).count();
 			}
 			A.seqqual.resize(A.seqqual.size() + 16, 0);
@@ -2319,7 +2335,7 @@ struct RunAligner {
 	     << "records stay in HBM for the getsv passes (80 bytes a record).\n\n"
 	     << "Options: -c <string>           options handed to getclip, e.g. -c \"-q 5 -s\"\n"
 	     << "         -v <string>           options handed to getsv, e.g. -v \"-b 5 -L 100\"\n"
-	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500\" (the GPU is chosen by -G here)\n"
+	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500 -g\" (the GPU is chosen by -G here)\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -2348,14 +2364,15 @@ static int cmd_run(int argc, char **argv)
 	if (argc != optind + 3) usage_run();
 	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
 	int max_occ = 0;
+	bool gapped = false;
+	vector<string> aln_words = {"realign"}; // (lives while getopt is used below: behind a flag without an argument - "-g" - getopt keeps a pointer into the word it read last)
 	{ // realign's options, parsed as `seeksv realign` parses them; the GPU is run's own -G
-		vector<string> w = {"realign"};
-		for (auto &x : split_words(aln_opts)) w.push_back(x);
+		for (auto &x : split_words(aln_opts)) aln_words.push_back(x);
 		vector<char *> av;
-		for (auto &x : w) av.push_back(const_cast<char *>(x.c_str()));
+		for (auto &x : aln_words) av.push_back(const_cast<char *>(x.c_str()));
 		av.push_back(nullptr);
 		int aln_gpu = -1;
-		if (parse_realign_options((int)w.size(), av.data(), &aln_gpu, &max_occ) != (int)w.size()) usage_realign();
+		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped) != (int)aln_words.size()) usage_realign();
 		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
 	}
 	PhaseTimer pt;
@@ -2366,7 +2383,7 @@ static int cmd_run(int argc, char **argv)
 	g_preread.path = fasta; g_preread.offs.assign(1, 0);
 	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
 	RunAligner &aligner = *new RunAligner; // (never destroyed: die() may exit while its thread runs)
-	aligner.max_occ = max_occ;
+	aligner.max_occ = max_occ; aligner.gapped = gapped;
 	aligner.start(device, fasta);
 	g_resident.on_pass = [&aligner](const vector<ResidentBam::Piece *> &pass) { aligner.submit(pass); };
 	auto call = [&](int (*fn)(int, char **), vector<string> words) {
@@ -2392,7 +2409,7 @@ static int cmd_run(int argc, char **argv)
 		g_resident.aln.bam_path = prefix + ".clip.bam"; g_resident.aln.rec = &aligner.A; g_resident.aln.names = aligner.R.names;
 		// (written under a temporary name and renamed when it is whole: a run that dies in getsv must not leave half a clip.bam where `seeksv getsv` would find it)
 		g_resident.bam_writer = std::thread([&aligner] { write_clip_bam(g_resident.aln.bam_path + ".tmp", aligner.R, aligner.A); });
-		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ) << endl;
+		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped) << endl;
 		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
 		a = {"getsv"};
 		for (auto &w : split_words(sv_opts)) a.push_back(w);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The GPU re-aligner (ssv_realign_*) at the size of the bench workload: index of the whole synthetic genome (generated in
 HBM), then queries cut from it - half of them real placements (both strands, 0.5 % substitutions), half random sequence like the bulk of
-a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [genome_frac] [n_queries] [query_len]
+a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [genome_frac] [n_queries] [query_len]
+--gapped: half of the random queries give way to a third class, real placements that carry one insertion or deletion of 1-3 bases at least 12 bases
+from either end; every round then runs the set through ssv_realign_query and through ssv_realign_query_gapped (`seeksv realign -g`) and reports both.
 --index both builds and queries the two kinds of index in one process, alternating (hash, sorted, hash, sorted, ...), R times each: one JSON line
 with a list of rounds per kind.  Index bytes are computed from the sizes the library allocates, not measured."""
 import argparse
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--index", choices=["hash", "sorted", "both"], default="hash")
     ap.add_argument("--max-occ", type=int, default=500)
     ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--gapped", action="store_true")
     ap.add_argument("genome_frac", nargs="?", type=float, default=1.0)
     ap.add_argument("n_queries", nargs="?", type=int, default=2_000_000)
     ap.add_argument("query_len", nargs="?", type=int, default=60)
@@ -63,6 +66,25 @@ def main():
     rev = rng.random_sample(n_real) < 0.5
     codes[rev] = (3 - codes[rev])[:, ::-1]
     junk = rng.randint(0, 4, (nq - n_real, qlen)).astype(np.uint8)
+    n_gap = (nq - n_real) // 2 if args.gapped else 0
+    if n_gap:   # the third class takes the place of the first n_gap random queries (a generator of its own: the other two classes stay what they are without --gapped)
+        g = np.random.RandomState(12)
+        gtid = g.randint(0, len(off) - 1, n_gap)
+        gstart = (off[gtid] + (g.random_sample(n_gap) * (np.diff(off)[gtid] - qlen - 3)).astype(np.int64)).astype(np.int64)
+        glen = g.randint(1, 4, n_gap)
+        gins = g.random_sample(n_gap) < 0.5
+        gat = 12 + (g.random_sample(n_gap) * (qlen - 24 - glen + 1)).astype(np.int64)   # the gap (and an insertion's bases) lie in [12, qlen - 12)
+        col = np.arange(qlen)[None, :]
+        behind = col >= (gat + np.where(gins, glen, 0))[:, None]
+        gidx = gstart[:, None] + col + np.where(behind, np.where(gins, -glen, glen)[:, None], 0)
+        gcodes = ((wh[gidx >> 5] >> ((gidx & 31) * 2).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)
+        inserted = gins[:, None] & (col >= gat[:, None]) & ~behind
+        gcodes = np.where(inserted, g.randint(0, 4, gcodes.shape), gcodes).astype(np.uint8)
+        gsub = g.random_sample(gcodes.shape) < 0.005
+        gcodes = np.where(gsub, (gcodes + 1 + g.randint(0, 3, gcodes.shape)) & 3, gcodes).astype(np.uint8)
+        grev = g.random_sample(n_gap) < 0.5
+        gcodes[grev] = (3 - gcodes[grev])[:, ::-1]
+        junk[:n_gap] = gcodes
     allc = np.concatenate([codes, junk])
     order = rng.permutation(nq)
     allc = allc[order]
@@ -74,6 +96,13 @@ def main():
     exp_tid[is_real] = tid[order[is_real]]
     exp_pos = np.full(nq, -1, np.int64)
     exp_pos[is_real] = (start - off[tid])[order[is_real]]
+    is_gap = (order >= n_real) & (order < n_real + n_gap)
+    exp_len = np.zeros(nq, np.int64)
+    if n_gap:
+        exp_tid[is_gap] = gtid[order[is_gap] - n_real]
+        exp_pos[is_gap] = (gstart - off[gtid])[order[is_gap] - n_real]
+        exp_len[is_gap] = np.where(gins, -glen, glen)[order[is_gap] - n_real]
+    is_junk = ~is_real & ~is_gap
     samples = (G + 3) // 4
 
     def one(kind):
@@ -91,14 +120,30 @@ def main():
         ok_real = int(((hits["tid"] == exp_tid) & (hits["pos"] - hits["q_beg"] == exp_pos) & (hits["mapq"] > 0))[is_real].sum())
         kept, peak = index_bytes(kind, samples)
         flags = hits["pad"][:, 0]
-        return dict(built, index_wall_s=round(t_index, 3), index_kernel_ms=round(prof["realign_index"]["total_ms"], 2),
-                    index_positions_per_s=round(samples / (prof["realign_index"]["total_ms"] * 1e-3)), index_GB=round(kept / 1e9, 2), index_build_GB=round(peak / 1e9, 2),
-                    query_wall_s=round(t_query, 3), query_kernel_ms=round(prof["realign_query"]["total_ms"], 2),
-                    queries_per_s_kernel=round(nq / (prof["realign_query"]["total_ms"] * 1e-3)), real_placed_correctly=ok_real,
-                    junk_unaligned=int((hits["tid"][~is_real] == -1).sum()), masked=int((flags & 1).astype(bool).sum()), over_limit=int((flags & 2).astype(bool).sum()))
+        out = dict(built, index_wall_s=round(t_index, 3), index_kernel_ms=round(prof["realign_index"]["total_ms"], 2),
+                   index_positions_per_s=round(samples / (prof["realign_index"]["total_ms"] * 1e-3)), index_GB=round(kept / 1e9, 2), index_build_GB=round(peak / 1e9, 2),
+                   query_wall_s=round(t_query, 3), query_kernel_ms=round(prof["realign_query"]["total_ms"], 2),
+                   queries_per_s_kernel=round(nq / (prof["realign_query"]["total_ms"] * 1e-3)), real_placed_correctly=ok_real,
+                   junk_unaligned=int((hits["tid"][is_junk] == -1).sum()), masked=int((flags & 1).astype(bool).sum()), over_limit=int((flags & 2).astype(bool).sum()))
+        if args.gapped:   # the same queries once more, with gaps
+            at_locus = (hits["tid"] == exp_tid) & (hits["mapq"] > 0)
+            out["ungapped_gap_class_at_its_contig"] = int(at_locus[is_gap].sum())
+            ctx.prof_reset()
+            t = time.perf_counter()
+            hits, gaps = ctx.realign(seqs, gapped=True)
+            t_query = time.perf_counter() - t
+            prof = ctx.prof_all()
+            q_ms, g_ms = prof["realign_query"]["total_ms"], prof["realign_gap"]["total_ms"]
+            placed = (hits["tid"] == exp_tid) & (hits["pos"] - hits["q_beg"] == exp_pos) & (hits["mapq"] > 0)
+            out["gapped"] = dict(query_wall_s=round(t_query, 3), query_kernel_ms=round(q_ms, 2), gap_kernel_ms=round(g_ms, 2), queries_per_s_kernels=round(nq / ((q_ms + g_ms) * 1e-3)),
+                                 real_placed_correctly=int((placed & (gaps["len"] == 0))[is_real].sum()), real_with_a_gap=int((gaps["len"] != 0)[is_real].sum()),
+                                 junk_unaligned=int((hits["tid"][is_junk] == -1).sum()),
+                                 planted_gap_found=int((placed & (gaps["len"] == exp_len))[is_gap].sum()), gap_class_with_another_gap=int(((gaps["len"] != 0) & ~(placed & (gaps["len"] == exp_len)))[is_gap].sum()),
+                                 gap_class_without_gap=int((gaps["len"] == 0)[is_gap].sum()))
+        return out
 
     kinds = ["hash", "sorted"] if args.index == "both" else [args.index]
-    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int((~is_real).sum()),
+    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int(is_junk.sum()), "with_planted_gap": int(is_gap.sum()),
            "rounds": {k: [] for k in kinds}}
     for _ in range(args.rounds):
         for k in kinds:
