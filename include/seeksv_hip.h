@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
+                             v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
                              v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
                              v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
                              v9 (additive, same version): ssv_rt_begin / ssv_rt_scan / ssv_rt_finish (getsv -F), ssv_names_t, ssv_bamdec_names.
@@ -585,7 +586,8 @@ const char *ssv_prof_names(void);
  * like random sequence (the synthetic genomes of bench.py / tests).  getsv consumes of each clip.bam record: flag & {4, 16, 256},
  * MAPQ == 0 or not, tid, pos, the CIGAR with its S ends, the read name = the sequence (getsv.cpp:25-71, getsv.h:445-527).
  * K-mer index of the reference in HBM + seed look-ups on both strands + ungapped extension with bwa mem's default scores
- * (match 1, mismatch 4, end clipping 5, minimum 30).  NOT bit-identical to bwa: no gaps, no chaining, one record per query. */
+ * (match 1, mismatch 4, end clipping 5, minimum 30).  NOT bit-identical to bwa: no gaps unless asked for (one), no chaining, no
+ * supplementary records, one record per query unless its other loci are asked for (ssv_realign_query_alts: up to 1 + 16). */
 typedef struct {
 	int32_t tid;         /* -1: unaligned (flag 4) */
 	int32_t pos;         /* 0-based reference position of the aligned segment's first base */
@@ -599,6 +601,7 @@ typedef struct {
 } ssv_realign_hit;
 #define SSV_RA_F_MASKED 1   /* a 20-mer of the query occurs more than max_occ times among the indexed positions and gave no seed */
 #define SSV_RA_F_OVERFLOW 2 /* the query has more seeds than candidate slots (192): the rarest were followed, some were left out */
+#define SSV_RA_F_ALT_CUT 4  /* ssv_realign_query_alts only: more loci qualified as alternates than max_alt */
 
 /* Build the index.  ref2bit: base i of the concatenated contigs at bits [2 (i % 32), +2) of word i / 32, A C G T = 0 1 2 3 (the
  * caller decides what N becomes); target_off[n_targets + 1] = first base of every contig, target_off[0] = 0, target_off[n_targets] =
@@ -635,6 +638,24 @@ typedef struct {
 	int32_t len;         /* > 0: deletion of len reference bases before query base q_at; < 0: query bases [q_at, q_at - len) are inserted; 0: none */
 } ssv_realign_gap;
 int ssv_realign_query_gapped(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps);
+/* ssv_realign_query (gapped == 0) or ssv_realign_query_gapped (gapped != 0) + the query's OTHER loci (`seeksv realign -S`), as bwa mem -a users feed them to
+ * getsv: secondary records that still make junctions.  hits[n] (and gaps[n]) are bit for bit those of the plain calls apart from SSV_RA_F_ALT_CUT.
+ * Rule: the candidates and their scores are those of the query's first stage on the index that was built last; best = the primary's score there (in gapped
+ * mode: before the refinement).  A candidate is an alternate locus when its score is >= 30 and 5 * score >= 4 * best (bwa mem's XA ratio 0.8) and it is not
+ * the locus - same strand, same contig, diagonals at most 32 apart: the window of `second` - of the primary or of an alternate chosen before it.  They are
+ * chosen greedily by score (descending), strand (forward first), diagonal (ascending), contig id (ascending); at most max_alt (1..16) are kept, and when
+ * more loci qualified the primary's pad[0] gets SSV_RA_F_ALT_CUT.  An alternate's hit: tid, pos, q_beg, q_end, score, n_mismatch, reverse of its own
+ * diagonal by the primary's rule (best segment inside the seed's contig + end extension), second = best, mapq = 0, pad[0] = the primary's, pad[1] = 0.
+ * An unaligned, too short or too long query has none.  Limits: alternates are not gap-refined (with `gapped` they come from the first stage, need 30 or more
+ * there, and a primary that the refinement leaves unaligned has none); at most 16; on the hash index a query with more than 192 seeds keeps the candidates
+ * it happened to keep (as its primary does), and a primary tied in score, strand and diagonal between two contigs is the lanes' choice there, the other
+ * contig's candidate then being an alternate (the sorted index decides both); split sequences still get no supplementary records.
+ * alt_off[n + 1] (host): query i's alternates are alts[alt_off[i] .. alt_off[i + 1]), in the rule's order; alts (host) needs room for n * max_alt hits,
+ * alt_off[n] are written.  Errors as the other query calls; SSV_E_ARG also for max_alt outside 1..16, a NULL alt_off or alts, gapped without gaps.
+ * n == 0: SSV_OK and alt_off[0] = 0. */
+int ssv_realign_query_alts(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, int32_t max_alt, int32_t gapped,
+                           ssv_realign_hit *hits, ssv_realign_gap *gaps /* required iff gapped */,
+                           int64_t *alt_off /* n + 1 */, ssv_realign_hit *alts /* room for n * max_alt; alt_off[n] are written */);
 int ssv_realign_free(ssv_ctx *ctx);
 
 /* ---- getsv -F: junctions from read-through split alignments: replaces FindJunction (process_bwasw.cpp:5-227, seeksv.cpp:221-225) -----------

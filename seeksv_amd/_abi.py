@@ -323,6 +323,7 @@ def host_lib():
 REALIGN_HIT = [("tid", "<i4"), ("pos", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"), ("score", "<i4"), ("second", "<i4"), ("n_mismatch", "<i4"),
                ("reverse", "u1"), ("mapq", "u1"), ("pad", "u1", (2,))]  # ssv_realign_hit; pad[:, 0] = RA_F_* (sorted index)
 RA_F_MASKED, RA_F_OVERFLOW = 1, 2
+RA_F_ALT_CUT = 4  # ssv_realign_query_alts: more loci qualified than max_alt
 REALIGN_GAP = [("q_at", "<i4"), ("len", "<i4")]  # ssv_realign_gap
 
 
@@ -384,6 +385,7 @@ def hip_lib():
         lib.ssv_realign_index_sorted.argtypes = [V, V, C.c_int32, C.c_int64, V, C.c_int32, C.c_int32, C.POINTER(RealignIndexStats)]
         lib.ssv_realign_query.argtypes = [V, V, V, C.c_int64, V]
         lib.ssv_realign_query_gapped.argtypes = [V, V, V, C.c_int64, V, V]
+        lib.ssv_realign_query_alts.argtypes = [V, V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V]
         lib.ssv_realign_free.argtypes = [V]
         lib.ssv_prof_enable.argtypes = [V, C.c_int]
         lib.ssv_prof_reset.argtypes = [V]

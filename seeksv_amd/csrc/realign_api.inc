@@ -1,7 +1,8 @@
-// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h and realign_gap_kernels.h)
+// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h, realign_gap_kernels.h and realign_alts_kernels.h)
 
 struct ssv_realign_state {
 	DBuf ref, ctg, table, seqs, offs, hits, gaps, dropped;
+	DBuf alts, alt_n, alt_off, alt_sums, alt_dense; // ssv_realign_query_alts: strided hits and counts, their scan, the dense list
 	DBuf skeys, svals, sdir; // the sorted index (ssv_realign_index_sorted); a context holds one kind of index at a time
 	bool sorted = false;
 	int32_t dir_bits = 0, max_occ = 0;
@@ -120,8 +121,9 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 	return SSV_OK;
 }
 
-// the query kernel of the index that stands - its instantiation with the candidate floor at RA_K when `floor` - over the n sequences in R.seqs / R.offs -> R.hits
-static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor)
+// the query kernel of the index that stands - its instantiation with the candidate floor at RA_K when `floor` - over the n sequences in R.seqs / R.offs -> R.hits;
+// max_alt > 0: the instantiation that goes on to the alternates -> R.alts (max_alt per query), R.alt_n
+static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor, int32_t max_alt = 0)
 {
 	RaIndex ix;
 	ix.ref = R.ref_p; ix.n_bases = R.n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = R.n_ctg; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
@@ -131,23 +133,36 @@ static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bo
 		a.ix = ix;
 		a.sx.keys = P<uint64_t>(R.skeys); a.sx.vals = P<uint32_t>(R.svals); a.sx.dir = P<uint32_t>(R.sdir); a.sx.bits = R.dir_bits; a.sx.max_occ = R.max_occ;
 		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-		if (floor) k_ras_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		if (max_alt > 0) {
+			RaAltArgs<RasQueryArgs> x;
+			static_cast<RasQueryArgs &>(x) = a;
+			x.alts = P<RaHit>(R.alts); x.alt_n = P<int32_t>(R.alt_n); x.max_alt = max_alt;
+			if (floor) k_ras_query_floor_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
+			else k_ras_query_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
+		} else if (floor) k_ras_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
 		else k_ras_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
 	} else {
 		RaQueryArgs a;
 		a.ix = ix;
 		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-		if (floor) k_ra_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+		if (max_alt > 0) {
+			RaAltArgs<RaQueryArgs> x;
+			static_cast<RaQueryArgs &>(x) = a;
+			x.alts = P<RaHit>(R.alts); x.alt_n = P<int32_t>(R.alt_n); x.max_alt = max_alt;
+			if (floor) k_ra_query_floor_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
+			else k_ra_query_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
+		} else if (floor) k_ra_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
 		else k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
 	}
 }
 
-// ssv_realign_query (gaps == nullptr) and ssv_realign_query_gapped; `who` names the caller in the error text
-static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps, bool gapped, const char *who)
+// ssv_realign_query (gaps == nullptr), ssv_realign_query_gapped and - max_alt > 0 - ssv_realign_query_alts; `who` names the caller in the error text
+static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps, bool gapped, const char *who,
+                         int32_t max_alt = 0, int64_t *alt_off = nullptr, ssv_realign_hit *alts = nullptr)
 {
 	if (!c || n < 0 || (n > 0 && (!seqs || !seq_off || !hits || (gapped && !gaps)))) return SSV_E_ARG;
 	if (!c->ra || !c->ra->ready) { c->err = std::string(who) + " before ssv_realign_index"; return SSV_E_STATE; }
-	if (n == 0) return SSV_OK;
+	if (n == 0) { if (alt_off) alt_off[0] = 0; return SSV_OK; }
 	static_assert(sizeof(RaHit) == sizeof(ssv_realign_hit), "hit layout");
 	static_assert(sizeof(RaGap) == sizeof(ssv_realign_gap), "gap layout");
 	HIPCHECK(c, hipSetDevice(c->device));
@@ -155,9 +170,13 @@ static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, 
 	const uint64_t bytes = seq_off[n];
 	CHECK(ensure(c, R.seqs, bytes + 16)); CHECK(ensure(c, R.offs, (size_t)(n + 1) * 8)); CHECK(ensure(c, R.hits, (size_t)n * sizeof(RaHit)));
 	if (gapped) CHECK(ensure(c, R.gaps, (size_t)n * sizeof(RaGap)));
+	if (max_alt > 0) {
+		CHECK(ensure(c, R.alts, (size_t)n * (size_t)max_alt * sizeof(RaHit))); CHECK(ensure(c, R.alt_n, (size_t)n * 4)); CHECK(ensure(c, R.alt_off, (size_t)(n + 1) * 8));
+		CHECK(ensure(c, R.alt_sums, (size_t)scan_scratch_elems(n) * 8));
+	}
 	HIPCHECK(c, hipMemcpyAsync(R.seqs.p, seqs, bytes, hipMemcpyHostToDevice, c->st));
 	HIPCHECK(c, hipMemcpyAsync(R.offs.p, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->st));
-	realign_launch_query(c, R, n, gapped);
+	realign_launch_query(c, R, n, gapped, max_alt);
 	HIPCHECK(c, hipGetLastError());
 	if (gapped) {
 		RaGapArgs g;
@@ -169,8 +188,28 @@ static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, 
 		HIPCHECK(c, hipGetLastError());
 		HIPCHECK(c, hipMemcpyAsync(gaps, R.gaps.p, (size_t)n * sizeof(RaGap), hipMemcpyDeviceToHost, c->st));
 	}
+	if (max_alt > 0) { // counts -> offsets; the dense list's size is known on the host before it is gathered
+		{
+			ProfScope ps(c, P_REALIGN_ALTS, n);
+			exclusive_scan<int32_t, int64_t>(c->st, P<int32_t>(R.alt_n), P<int64_t>(R.alt_off), n, (int64_t)0, P<int64_t>(R.alt_sums), P<int64_t>(R.alt_off) + n);
+		}
+		HIPCHECK(c, hipGetLastError());
+		HIPCHECK(c, hipMemcpyAsync(alt_off, R.alt_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->st));
+	}
 	HIPCHECK(c, hipMemcpyAsync(hits, R.hits.p, (size_t)n * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
+	if (max_alt > 0 && alt_off[n] > 0) {
+		const int64_t total = alt_off[n];
+		if (total > n * (int64_t)max_alt) { c->err = std::string(who) + ": more alternates than slots"; return SSV_E_STATE; }
+		CHECK(ensure(c, R.alt_dense, (size_t)total * sizeof(RaHit)));
+		{
+			ProfScope ps(c, P_REALIGN_ALTS, total);
+			k_ra_alt_compact<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<RaHit>(R.alts), P<int32_t>(R.alt_n), P<int64_t>(R.alt_off), n, max_alt, P<RaHit>(R.alt_dense));
+		}
+		HIPCHECK(c, hipGetLastError());
+		HIPCHECK(c, hipMemcpyAsync(alts, R.alt_dense.p, (size_t)total * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+	}
 	return SSV_OK;
 }
 
@@ -182,6 +221,13 @@ int ssv_realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int
 int ssv_realign_query_gapped(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps)
 {
 	return realign_query(c, seqs, seq_off, n, hits, gaps, true, "ssv_realign_query_gapped");
+}
+
+int ssv_realign_query_alts(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, int32_t max_alt, int32_t gapped, ssv_realign_hit *hits, ssv_realign_gap *gaps,
+                           int64_t *alt_off, ssv_realign_hit *alts)
+{
+	if (max_alt < 1 || max_alt > RA_MAX_ALT || !alt_off || !alts || (gapped && !gaps)) return SSV_E_ARG;
+	return realign_query(c, seqs, seq_off, n, hits, gapped ? gaps : nullptr, gapped != 0, "ssv_realign_query_alts", max_alt, alt_off, alts);
 }
 
 int ssv_realign_free(ssv_ctx *c)

@@ -6,7 +6,7 @@
 // getsv.h:445-527).  This is a stand-in for that step on hosts without bwa, for references that behave like random sequence
 // (the synthetic genomes of bench / tests): a k-mer index of the reference in HBM, seed look-ups for every k-mer of a query on
 // both strands, ungapped extension with bwa mem's default scores (match 1, mismatch 4, end clipping 5, report >= 30).
-// It does not reproduce bwa's alignments bit for bit (one gap per alignment at the most, and only on request: realign_gap_kernels.h; no chaining, no supplementary records; at most
+// It does not reproduce bwa's alignments bit for bit (one gap per alignment at the most, and only on request: realign_gap_kernels.h; other loci as secondary hits only on request: realign_alts_kernels.h; no chaining, no supplementary records; at most
 // RA_MAX_CAND seed hits per query are followed, probe runs longer than RA_MAX_PROBE are cut).  References with repeats take the second, sorted
 // index of realign_sorted_kernels.h: the same query kernel (k_ra_query_t below) with another seed stage.
 //
@@ -123,7 +123,9 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 // FLOOR is the score a candidate needs to be kept and a winner to be reported: RA_MIN_SCORE, or RA_K for the gapped query (realign_gap_kernels.h: k_ra_gap
 // refines the winner and applies RA_MIN_SCORE to what it leaves; `second` counts candidates at RA_MIN_SCORE or more only).  At the default every
 // FLOOR test is the one the kernel had before the parameter.
-template <bool SORTED, typename Args, int FLOOR = RA_MIN_SCORE>
+// ALTS: the query's other loci behind the winner (realign_alts_kernels.h: ra_alts, found like ras_seeds; Args is then RaAltArgs<...>, whose alt_n[q] every
+// query writes).  Off - the default - nothing of it is compiled: the four instantiations from before the parameter keep their code and resources.
+template <bool SORTED, typename Args, int FLOOR = RA_MIN_SCORE, bool ALTS = false>
 __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 {
 	__shared__ uint8_t s_code[WAVES_PER_BLOCK][2][RA_MAX_Q];
@@ -139,7 +141,10 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 	const int n = (int)(a.seq_off[q + 1] - o0);
 	RaHit out;
 	out.tid = -1; out.pos = -1; out.q_beg = 0; out.q_end = 0; out.score = 0; out.second = 0; out.n_mismatch = 0; out.reverse = 0; out.mapq = 0; out.pad[0] = out.pad[1] = 0;
-	if (n < RA_K || n > RA_MAX_Q) { if (lane == 0) a.hits[q] = out; return; }
+	if (n < RA_K || n > RA_MAX_Q) {
+		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; }
+		return;
+	}
 	for (int i = lane; i < n; i += WAVE) {
 		const uint32_t c = ra_code(a.seqs[o0 + i]);
 		s_code[w][0][i] = (uint8_t)c;
@@ -234,7 +239,10 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		const bool take = os > win_score || (os == win_score && os > 0 && (ost < win_st || (ost == win_st && (od < win_diag || (od == win_diag && first)))));
 		if (take) { win_score = os; win_lane = ol; win_diag = od; win_st = ost; win_t = ot; }
 	}
-	if (win_score < FLOOR) { if (lane == 0) a.hits[q] = out; return; }
+	if (win_score < FLOOR) {
+		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; }
+		return;
+	}
 	const int win_tid = __shfl(best_tid, win_lane, 64);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
@@ -255,6 +263,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		out.mapq = (uint8_t)(second >= best_score ? 0 : (gap >= 10 ? 60 : (gap * 6 > 1 ? gap * 6 : 1)));
 		a.hits[q] = out;
 	}
+	if constexpr (ALTS) ra_alts(a, w, lane, n, m, q, s_code, s_diag, s_ss, s_tid, win_st, win_tid, win_diag, win_score, win_lane, (uint32_t)out.pad[0]);
 }
 
 constexpr auto k_ra_query = k_ra_query_t<false, RaQueryArgs>;

@@ -430,6 +430,20 @@ class Context:
             self._check(self._lib.ssv_realign_query_gapped(self._h, C.c_char_p(blob), off.ctypes.data, len(seqs), hits.ctypes.data, gaps.ctypes.data), "ssv_realign_query_gapped")
         return hits, gaps
 
+    def realign_alts(self, seqs, max_alt, gapped=False):
+        """realign() + every query's other loci (ssv_realign_query_alts, max_alt in 1..16) -> (hits, gaps or None, alt_off, alts): query i's alternates
+        are alts[alt_off[i]:alt_off[i + 1]], in the rule's order; hits["pad"][:, 0] & _abi.RA_F_ALT_CUT where more loci qualified than max_alt"""
+        n = len(seqs)
+        blob = "".join(seqs).encode()
+        off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.uint64)
+        hits = np.zeros(n, dtype=np.dtype(_abi.REALIGN_HIT))
+        gaps = np.zeros(n, dtype=np.dtype(_abi.REALIGN_GAP)) if gapped else None
+        alt_off = np.full(n + 1, -1, dtype=np.int64)
+        alts = np.zeros(max(n * max(int(max_alt), 0), 1), dtype=np.dtype(_abi.REALIGN_HIT))
+        self._check(self._lib.ssv_realign_query_alts(self._h, C.c_char_p(blob), off.ctypes.data, n, int(max_alt), 1 if gapped else 0, hits.ctypes.data,
+                                                     gaps.ctypes.data if gapped else None, alt_off.ctypes.data, alts.ctypes.data), "ssv_realign_query_alts")
+        return hits, gaps, alt_off, alts[:int(alt_off[n])].copy()
+
     # ---- measurement ----
     def prof_enable(self, mode=1):
         self._check(self._lib.ssv_prof_enable(self._h, mode), "ssv_prof_enable")

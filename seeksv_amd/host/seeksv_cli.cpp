@@ -1858,7 +1858,7 @@ static int cmd_somatic(int argc, char **argv)
 // ---------------------------------------------------------------------------------------------------------------------
 // seeksv realign: prefix.clip.fq.gz -> prefix.clip.bam.  The reference's pipeline runs an external aligner here
 // (README.md:22-34, example/seeksv.sh:3: `bwa mem ref.fa prefix.clip.fq.gz | samtools view -Sb - > prefix.clip.bam`); this is the
-// stand-in for hosts without bwa (ssv_realign_*, include/seeksv_hip.h): one record per clipped sequence, in FASTQ order, the
+// stand-in for hosts without bwa (ssv_realign_*, include/seeksv_hip.h): one record per clipped sequence (with -S: followed by up to INT secondary records of its other loci), in FASTQ order, the
 // read name is the sequence.  No gapped alignment unless -g asks for it (one insertion or deletion of up to 16 bases per record).  The default (hash) index is meant for references that behave like random sequence (synthetic
 // genomes); -c selects the sorted index, which keeps every copy of a repeat, skips seeds with more occurrences than the cap and follows the rarest first.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1867,6 +1867,7 @@ static int cmd_somatic(int argc, char **argv)
 	cerr << "Usage: seeksv realign [options] <reference fasta(.gz)> <input clipped reads (*.clip.fq.gz)> <output clip.bam>\n\n"
 	     << "         -c <int>              skip seeds with more than INT occurrences; selects the sorted index (1..65535; bwa mem's -c, there 500) [hash index, no cap]\n"
 	     << "         -g                    allow one insertion or deletion of 1..16 bases per alignment (M, I / D, M; gap open 6, extend 1) [ungapped]\n"
+	     << "         -S <int>              also write up to INT other loci of a sequence as secondary records (flag 256, MAPQ 0; 1..16; score >= 30 and >= 0.8 x the primary's) [none]\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -1880,13 +1881,19 @@ static int parse_max_occ(const char *arg)
 }
 
 // realign's options, for `seeksv realign` itself and for the words of `seeksv run -a`; *gpu stays as it is without -G.  -> index of the first operand
-static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped)
+static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped, int *max_alt)
 {
 	int c;
 	optind = 1;
-	while ((c = getopt(argc, argv, "G:c:g")) != -1) {
+	while ((c = getopt(argc, argv, "G:c:gS:")) != -1) {
 		if (c == 'G') *gpu = atoi(optarg);
 		else if (c == 'g') *gapped = true;
+		else if (c == 'S') { // 0 = no secondary records
+			char *end = nullptr;
+			const long v = strtol(optarg, &end, 10);
+			if (end == optarg || *end != 0 || v < 1 || v > 16) usage_realign();
+			*max_alt = (int)v;
+		}
 		else if (c == 'c') { if (!(*max_occ = parse_max_occ(optarg))) usage_realign(); }
 		else usage_realign();
 	}
@@ -2067,13 +2074,25 @@ struct AlignedRecords {
 	vector<uint64_t> seq_off;
 	vector<const char *> qn;
 	int64_t n_aligned = 0, n_masked = 0, n_over = 0, n_gapped = 0; // (n_masked, n_over: SSV_RA_F_* of the sorted index; n_gapped: records with an I / D, -g)
+	int64_t n_secondary = 0, n_with_alt = 0, n_cut = 0; // -S: secondary records, sequences that have any, sequences with SSV_RA_F_ALT_CUT
 	int64_t size() const { return (int64_t)tid.size(); }
 };
-// the sequences through the aligner (ssv_realign_query, or ssv_realign_query_gapped when `gapped`) and their records appended to `out`
-static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out, bool gapped)
+// the sequences through the aligner (ssv_realign_query, or ssv_realign_query_gapped when `gapped`) and their records appended to `out`; max_alt > 0
+// (ssv_realign_query_alts): behind a sequence's record its alternates in the rule's order, as secondary records
+static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out, bool gapped, int max_alt)
 {
 	const int64_t n = (int64_t)seqs.size();
 	if (!n) return;
+	if (max_alt > 0) { // the alternates' lists are sized for the worst case, n * max_alt hits here and on the device: a file's sequences go a piece at a time
+		static const int64_t piece = [] { const char *e = getenv("SSV_REALIGN_ALT_PIECE"); const long long v = e ? atoll(e) : 0; return v > 0 ? (int64_t)v : (int64_t)1 << 20; }();
+		if (n > piece) {
+			for (int64_t b = 0; b < n; b += piece) {
+				const int64_t e = std::min(n, b + piece);
+				align_lines(ctx, vector<Line>(seqs.begin() + b, seqs.begin() + e), vector<Line>(quals.begin() + b, quals.begin() + e), out, gapped, max_alt);
+			}
+			return;
+		}
+	}
 	string blob;
 	vector<uint64_t> soff(1, 0);
 	{
@@ -2085,12 +2104,17 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 	}
 	vector<ssv_realign_hit> hits((size_t)n);
 	vector<ssv_realign_gap> gaps((size_t)n, ssv_realign_gap{0, 0}); // (all zero without -g)
-	const int rc = gapped ? ssv_realign_query_gapped(ctx, blob.data(), soff.data(), n, hits.data(), gaps.data()) : ssv_realign_query(ctx, blob.data(), soff.data(), n, hits.data());
+	vector<int64_t> alt_off((size_t)n + 1, 0); // (all zero without -S: sequence i is row i)
+	vector<ssv_realign_hit> alts(max_alt > 0 ? (size_t)n * (size_t)max_alt : 0);
+	const int rc = max_alt > 0 ? ssv_realign_query_alts(ctx, blob.data(), soff.data(), n, max_alt, gapped ? 1 : 0, hits.data(), gaps.data(), alt_off.data(), alts.data())
+	               : gapped    ? ssv_realign_query_gapped(ctx, blob.data(), soff.data(), n, hits.data(), gaps.data())
+	                           : ssv_realign_query(ctx, blob.data(), soff.data(), n, hits.data());
 	if (rc != SSV_OK) die(string("[seeksv] realign query: ") + ssv_last_error(ctx));
 	const size_t at = (size_t)out.size();
-	for (auto *v : {&out.tid, &out.pos, &out.lq}) v->resize(at + (size_t)n);
-	out.mtid.resize(at + (size_t)n, -1); out.mpos.resize(at + (size_t)n, -1); out.isz.resize(at + (size_t)n, 0);
-	out.flag.resize(at + (size_t)n); out.ncig.resize(at + (size_t)n); out.mapq.resize(at + (size_t)n); out.cig_off.resize(at + (size_t)n); out.seq_off.resize(at + (size_t)n); out.qn.resize(at + (size_t)n);
+	const size_t rows = (size_t)(n + alt_off[(size_t)n]); // sequence i: rows i + alt_off[i] (its own record) .. i + 1 + alt_off[i + 1]
+	for (auto *v : {&out.tid, &out.pos, &out.lq}) v->resize(at + rows);
+	out.mtid.resize(at + rows, -1); out.mpos.resize(at + rows, -1); out.isz.resize(at + rows, 0);
+	out.flag.resize(at + rows); out.ncig.resize(at + rows); out.mapq.resize(at + rows); out.cig_off.resize(at + rows); out.seq_off.resize(at + rows); out.qn.resize(at + rows);
 	int32_t *tid = out.tid.data() + at, *pos = out.pos.data() + at, *lq = out.lq.data() + at;
 	uint16_t *flag = out.flag.data() + at, *ncig = out.ncig.data() + at;
 	uint8_t *mapq = out.mapq.data() + at;
@@ -2111,11 +2135,19 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 			const bool al = h.tid >= 0;
 			out.n_aligned += al ? 1 : 0;
 			out.n_masked += (h.pad[0] & SSV_RA_F_MASKED) ? 1 : 0; out.n_over += (h.pad[0] & SSV_RA_F_OVERFLOW) ? 1 : 0;
-			cig_off[i] = co; seq_off[i] = so;
+			const int64_t row = i + alt_off[(size_t)i], n_alt = alt_off[(size_t)i + 1] - alt_off[(size_t)i];
+			cig_off[row] = co; seq_off[row] = so;
 			const bool gap = al && gaps[(size_t)i].len != 0;
 			out.n_gapped += gap ? 1 : 0;
-			ncig[i] = (uint16_t)(al ? 1 + (gap ? 2 : 0) + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
-			co += ncig[i]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
+			ncig[row] = (uint16_t)(al ? 1 + (gap ? 2 : 0) + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
+			co += ncig[row]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
+			out.n_secondary += n_alt; out.n_with_alt += n_alt ? 1 : 0; out.n_cut += (h.pad[0] & SSV_RA_F_ALT_CUT) ? 1 : 0;
+			for (int64_t r = 1; r <= n_alt; ++r) { // the alternates: S M S
+				const ssv_realign_hit &x = alts[(size_t)(alt_off[(size_t)i] + r - 1)];
+				cig_off[row + r] = co; seq_off[row + r] = so;
+				ncig[row + r] = (uint16_t)(1 + (x.q_beg > 0 ? 1 : 0) + (x.q_end < L ? 1 : 0));
+				co += ncig[row + r]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
+			}
 		}
 		out.cig.resize(co, 0);
 		out.seqqual.resize(so, 0);
@@ -2125,18 +2157,19 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 	{
 		const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ssv::effective_cpus(), 64, n / 4096}));
 		auto fill = [&](int w) {
-			for (int64_t i = n * w / nt, e = n * (w + 1) / nt; i < e; ++i) {
-				const ssv_realign_hit &h = hits[(size_t)i];
-				const char *s = seqs[(size_t)i].p, *q = quals[(size_t)i].p;
-				const int L = seqs[(size_t)i].n;
-				const bool al = h.tid >= 0, rev = al && h.reverse, has_q = quals[(size_t)i].n == L;
+			for (int64_t qi = n * w / nt, e = n * (w + 1) / nt; qi < e; ++qi)
+			for (int64_t i = qi + alt_off[(size_t)qi], r = 0, last = qi + alt_off[(size_t)qi + 1]; i <= last; ++i, ++r) { // row i: the sequence's own record (r == 0), then its alternates
+				const ssv_realign_hit &h = r ? alts[(size_t)(alt_off[(size_t)qi] + r - 1)] : hits[(size_t)qi];
+				const char *s = seqs[(size_t)qi].p, *q = quals[(size_t)qi].p;
+				const int L = seqs[(size_t)qi].n;
+				const bool al = h.tid >= 0, rev = al && h.reverse, has_q = quals[(size_t)qi].n == L;
 				qn[i] = s;
 				tid[i] = al ? h.tid : -1; pos[i] = al ? h.pos : -1; lq[i] = L;
-				flag[i] = (uint16_t)(al ? (rev ? 16 : 0) : 4); mapq[i] = al ? h.mapq : 0;
+				flag[i] = (uint16_t)((al ? (rev ? 16 : 0) : 4) | (r ? 256 : 0)); mapq[i] = al ? h.mapq : 0;
 				if (al) {
 					uint32_t *c = cig + cig_off[i];
 					if (h.q_beg > 0) *c++ = ((uint32_t)h.q_beg << 4) | 4u;
-					const ssv_realign_gap &g = gaps[(size_t)i];
+					const ssv_realign_gap &g = r ? ssv_realign_gap{0, 0} : gaps[(size_t)qi];
 					if (g.len == 0) *c++ = ((uint32_t)(h.q_end - h.q_beg) << 4) | 0u;
 					else { // M, D / I, M: the hit's coordinates are those of its own orientation, which is the record's
 						const int32_t j = g.len > 0 ? g.q_at : g.q_at - g.len;
@@ -2184,12 +2217,14 @@ static void build_realign_index(ssv_ctx *ctx, const Reference &R, int max_occ, i
 	if (rc != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
 }
 
-static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped)
+static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped, int max_alt)
 {
-	string t = "[seeksv realign] " + to_string(A.size()) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
+	string t = "[seeksv realign] " + to_string(A.size() - A.n_secondary) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
 	if (gapped) t += ", " + to_string(A.n_gapped) + " with a gap";
-	if (!max_occ) return t + (dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string());
-	return t + (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
+	if (!max_occ) t += dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string();
+	else t += (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
+	if (max_alt) t += ", " + to_string(A.n_secondary) + " secondary records for " + to_string(A.n_with_alt) + " sequences (" + to_string(A.n_cut) + " cut at -S)";
+	return t;
 }
 
 static void resident_alignments(seeksv::AlnRecords &R)
@@ -2201,9 +2236,9 @@ static void resident_alignments(seeksv::AlnRecords &R)
 
 static int cmd_realign(int argc, char **argv)
 {
-	int gpu = 0, max_occ = 0;
+	int gpu = 0, max_occ = 0, max_alt = 0;
 	bool gapped = false;
-	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped) != 3) usage_realign();
+	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped, &max_alt) != 3) usage_realign();
 	const string fasta = argv[optind], fq = argv[optind + 1], out_bam = argv[optind + 2];
 	PhaseTimer pt;
 	Reference R;
@@ -2241,7 +2276,7 @@ static int cmd_realign(int argc, char **argv)
 	build_realign_index(ctx, R, max_occ, &dropped);
 	pt.lap("index");
 	AlignedRecords A;
-	align_lines(ctx, seqs, quals, A, gapped);
+	align_lines(ctx, seqs, quals, A, gapped, max_alt);
 	pt.lap("align");
 	A.seqqual.resize(A.seqqual.size() + 16, 0);
 	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
@@ -2249,7 +2284,7 @@ static int cmd_realign(int argc, char **argv)
 	setenv("SSV_BGZF_LEVEL", "-1", 0);
 	write_clip_bam(out_bam, R, A);
 	pt.lap("write bam");
-	cerr << realign_summary(A, dropped, max_occ, gapped) << endl;
+	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt) << endl;
 	ssv_realign_free(ctx);
 	release_ctx(ctx);
 	return 0;
@@ -2270,6 +2305,7 @@ struct RunAligner {
 	int64_t dropped = 0;
 	int max_occ = 0; // -a "-c INT": the sorted index
 	bool gapped = false; // -a "-g"
+	int max_alt = 0; // -a "-S INT": secondary records
 	double t_index = 0, t_align = 0, t_wait_ref = 0;
 	void start(int device, const string &fasta)
 	{
@@ -2301,7 +2337,7 @@ struct RunAligner {
 						seqs.push_back(Line{base + r.seq_off, (int)r.seq_len}); quals.push_back(Line{base + r.qual_off, (int)r.qual_len});
 					}
 				}
-				align_lines(ctx, seqs, quals, A, gapped);
+				align_lines(ctx, seqs, quals, A, gapped, max_alt);
 				t_align += std::chrono::duration<double>(now() - t0).count();
 			}
 			A.seqqual.resize(A.seqqual.size() + 16, 0);
@@ -2335,7 +2371,7 @@ struct RunAligner {
 	     << "records stay in HBM for the getsv passes (80 bytes a record).\n\n"
 	     << "Options: -c <string>           options handed to getclip, e.g. -c \"-q 5 -s\"\n"
 	     << "         -v <string>           options handed to getsv, e.g. -v \"-b 5 -L 100\"\n"
-	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500 -g\" (the GPU is chosen by -G here)\n"
+	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500 -g -S 8\" (the GPU is chosen by -G here)\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -2365,6 +2401,7 @@ static int cmd_run(int argc, char **argv)
 	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
 	int max_occ = 0;
 	bool gapped = false;
+	int max_alt = 0;
 	vector<string> aln_words = {"realign"}; // (lives while getopt is used below: behind a flag without an argument - "-g" - getopt keeps a pointer into the word it read last)
 	{ // realign's options, parsed as `seeksv realign` parses them; the GPU is run's own -G
 		for (auto &x : split_words(aln_opts)) aln_words.push_back(x);
@@ -2372,7 +2409,7 @@ static int cmd_run(int argc, char **argv)
 		for (auto &x : aln_words) av.push_back(const_cast<char *>(x.c_str()));
 		av.push_back(nullptr);
 		int aln_gpu = -1;
-		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped) != (int)aln_words.size()) usage_realign();
+		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped, &max_alt) != (int)aln_words.size()) usage_realign();
 		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
 	}
 	PhaseTimer pt;
@@ -2383,7 +2420,7 @@ static int cmd_run(int argc, char **argv)
 	g_preread.path = fasta; g_preread.offs.assign(1, 0);
 	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
 	RunAligner &aligner = *new RunAligner; // (never destroyed: die() may exit while its thread runs)
-	aligner.max_occ = max_occ; aligner.gapped = gapped;
+	aligner.max_occ = max_occ; aligner.gapped = gapped; aligner.max_alt = max_alt;
 	aligner.start(device, fasta);
 	g_resident.on_pass = [&aligner](const vector<ResidentBam::Piece *> &pass) { aligner.submit(pass); };
 	auto call = [&](int (*fn)(int, char **), vector<string> words) {
@@ -2409,7 +2446,7 @@ static int cmd_run(int argc, char **argv)
 		g_resident.aln.bam_path = prefix + ".clip.bam"; g_resident.aln.rec = &aligner.A; g_resident.aln.names = aligner.R.names;
 		// (written under a temporary name and renamed when it is whole: a run that dies in getsv must not leave half a clip.bam where `seeksv getsv` would find it)
 		g_resident.bam_writer = std::thread([&aligner] { write_clip_bam(g_resident.aln.bam_path + ".tmp", aligner.R, aligner.A); });
-		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped) << endl;
+		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
 		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
 		a = {"getsv"};
 		for (auto &w : split_words(sv_opts)) a.push_back(w);

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """The GPU re-aligner (ssv_realign_*) at the size of the bench workload: index of the whole synthetic genome (generated in
 HBM), then queries cut from it - half of them real placements (both strands, 0.5 % substitutions), half random sequence like the bulk of
-a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [genome_frac] [n_queries] [query_len]
+a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [--alts K [--family N]] [genome_frac] [n_queries] [query_len]
 --gapped: half of the random queries give way to a third class, real placements that carry one insertion or deletion of 1-3 bases at least 12 bases
 from either end; every round then runs the set through ssv_realign_query and through ssv_realign_query_gapped (`seeksv realign -g`) and reports both.
+--alts K: every round also runs the set through ssv_realign_query_alts with max_alt K (`seeksv realign -S K`) and reports the query kernel, the scan and
+k_ra_alt_compact ("realign_alts"), the number of alternates, and whether the primaries are the plain call's.  --family N (with --alts) first plants N elements of
+64 bases in 5 copies each into the reference (word-aligned 2-bit copies on the device, before any index is built) and gives N of the random queries' places to a
+fourth class: 60 bases of such an element; reported: how many come back with all five copies (primary + 4 alternates).
 --index both builds and queries the two kinds of index in one process, alternating (hash, sorted, hash, sorted, ...), R times each: one JSON line
 with a list of rounds per kind.  Index bytes are computed from the sizes the library allocates, not measured."""
 import argparse
@@ -39,17 +43,35 @@ def main():
     ap.add_argument("--max-occ", type=int, default=500)
     ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--gapped", action="store_true")
+    ap.add_argument("--alts", type=int, default=0)
+    ap.add_argument("--family", type=int, default=0)
     ap.add_argument("genome_frac", nargs="?", type=float, default=1.0)
     ap.add_argument("n_queries", nargs="?", type=int, default=2_000_000)
     ap.add_argument("query_len", nargs="?", type=int, default=60)
     args = ap.parse_args()
     frac, nq, qlen = args.genome_frac, args.n_queries, args.query_len
+    if args.family and (not args.alts or qlen > 60):
+        ap.error("--family needs --alts and queries of at most 60 bases")
     import torch
     w = synth.Workload(genome_frac=frac, depth=1, n_sv=0)
     t = time.perf_counter()
     words, off = w.reference_2bit(0)
     torch.cuda.synchronize()
     t_ref = time.perf_counter() - t
+    fam_words = None
+    if args.family:   # N x 5 distinct two-word places inside one contig each; place 0 of a family is copied over the other four
+        f = np.random.RandomState(13)
+        cand = np.unique(f.randint(0, (int(off[-1]) >> 5) // 4 - 1, 8 * args.family * 5)) * 4
+        inside = np.searchsorted(off, cand * 32, side="right") == np.searchsorted(off, cand * 32 + 63, side="right")
+        cand = f.permutation(cand[inside])[:args.family * 5]
+        assert len(cand) == args.family * 5, "too few places for the families"
+        fam_words = cand.reshape(args.family, 5)
+        src = torch.as_tensor(fam_words[:, 0], device=words.device)
+        for k in range(1, 5):
+            dst = torch.as_tensor(fam_words[:, k], device=words.device)
+            words[dst] = words[src]
+            words[dst + 1] = words[src + 1]
+        torch.cuda.synchronize()
     ctx = Context(0)
     ctx.prof_enable(1)
     # queries
@@ -85,6 +107,15 @@ def main():
         grev = g.random_sample(n_gap) < 0.5
         gcodes[grev] = (3 - gcodes[grev])[:, ::-1]
         junk[:n_gap] = gcodes
+    n_fam = args.family
+    if n_fam:   # the fourth class, behind the third: bases 2..2 + qlen of a family's element, either strand
+        f = np.random.RandomState(14)
+        fidx = (fam_words[:, 0] * 32 + 2)[:, None] + np.arange(qlen)[None, :]
+        fcodes = ((wh[fidx >> 5] >> ((fidx & 31) * 2).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)
+        frev = f.random_sample(n_fam) < 0.5
+        fcodes[frev] = (3 - fcodes[frev])[:, ::-1]
+        assert n_gap + n_fam <= len(junk)
+        junk[n_gap:n_gap + n_fam] = fcodes
     allc = np.concatenate([codes, junk])
     order = rng.permutation(nq)
     allc = allc[order]
@@ -102,7 +133,9 @@ def main():
         exp_tid[is_gap] = gtid[order[is_gap] - n_real]
         exp_pos[is_gap] = (gstart - off[gtid])[order[is_gap] - n_real]
         exp_len[is_gap] = np.where(gins, -glen, glen)[order[is_gap] - n_real]
-    is_junk = ~is_real & ~is_gap
+    is_fam = (order >= n_real + n_gap) & (order < n_real + n_gap + n_fam)
+    fam_of = order[is_fam] - n_real - n_gap
+    is_junk = ~is_real & ~is_gap & ~is_fam
     samples = (G + 3) // 4
 
     def one(kind):
@@ -125,6 +158,35 @@ def main():
                    query_wall_s=round(t_query, 3), query_kernel_ms=round(prof["realign_query"]["total_ms"], 2),
                    queries_per_s_kernel=round(nq / (prof["realign_query"]["total_ms"] * 1e-3)), real_placed_correctly=ok_real,
                    junk_unaligned=int((hits["tid"][is_junk] == -1).sum()), masked=int((flags & 1).astype(bool).sum()), over_limit=int((flags & 2).astype(bool).sum()))
+        plain = hits
+        if args.alts:   # the same queries once more, with their other loci
+            ctx.prof_reset()
+            t = time.perf_counter()
+            h2, _, aoff, alts = ctx.realign_alts(seqs, args.alts)
+            t_query = time.perf_counter() - t
+            prof = ctx.prof_all()
+            q_ms, a_ms = prof["realign_query"]["total_ms"], prof["realign_alts"]["total_ms"]
+            cut = (h2["pad"][:, 0] & _abi.RA_F_ALT_CUT) != 0
+            h2["pad"][:, 0] &= ~np.uint8(_abi.RA_F_ALT_CUT)
+            n_alt = np.diff(aoff)
+            out["alts"] = dict(max_alt=args.alts, query_wall_s=round(t_query, 3), query_kernel_ms=round(q_ms, 2), scan_compact_kernel_ms=round(a_ms, 3),
+                               scan_compact_launches=int(prof["realign_alts"]["launches"]),
+                               queries_per_s_kernels=round(nq / ((q_ms + a_ms) * 1e-3)), alternates=int(aoff[-1]), queries_with_alternates=int((n_alt > 0).sum()),
+                               cut=int(cut.sum()), primaries_equal_plain=bool(h2.tobytes() == plain.tobytes()),
+                               real_with_alternates=int((n_alt > 0)[is_real].sum()), junk_with_alternates=int((n_alt > 0)[is_junk].sum()))
+            if n_fam:   # primary + 4 alternates = the five planted places (the diagonal of a 60-base query is its copy's base 2 on either strand)
+                want = np.sort(fam_words[fam_of] * 32 + 2, axis=1)
+                qi = np.flatnonzero(is_fam)
+                full = n_alt[qi] == 4
+                got = np.full((len(qi), 5), -1, np.int64)
+                got[:, 0] = off[np.maximum(h2["tid"][qi], 0)] + h2["pos"][qi] - h2["q_beg"][qi]
+                for k in range(4):
+                    a = alts[np.where(full, aoff[qi] + k, 0)] if len(alts) else None
+                    if a is not None:
+                        got[:, 1 + k] = np.where(full, off[np.maximum(a["tid"], 0)] + a["pos"] - a["q_beg"], -1)
+                out["alts"].update(family_queries=int(len(qi)), family_with_four_alternates=int(full.sum()),
+                                   family_all_five_copies_back=int((np.sort(got, axis=1) == want).all(axis=1).sum()),
+                                   family_primary_mapq0=int((h2["mapq"][qi] == 0).sum()))
         if args.gapped:   # the same queries once more, with gaps
             at_locus = (hits["tid"] == exp_tid) & (hits["mapq"] > 0)
             out["ungapped_gap_class_at_its_contig"] = int(at_locus[is_gap].sum())
@@ -143,7 +205,7 @@ def main():
         return out
 
     kinds = ["hash", "sorted"] if args.index == "both" else [args.index]
-    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int(is_junk.sum()), "with_planted_gap": int(is_gap.sum()),
+    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int(is_junk.sum()), "with_planted_gap": int(is_gap.sum()), "from_a_planted_family": int(is_fam.sum()),
            "rounds": {k: [] for k in kinds}}
     for _ in range(args.rounds):
         for k in kinds:
