@@ -379,8 +379,8 @@ int ssv_getsv_scan(ssv_ctx *ctx, const ssv_batch_t *b);
  * Range-partitioned runs (one GPU per run of records): the reference's pileup keeps at most ~8000 reads alive (bam_plp_push), a rule that
  * depends on the records BEFORE a rank's first one.  Right after ssv_getsv_begin a rank replays the last records before its range through
  * the pileup's bookkeeping only (nothing of them is counted: they belong to the rank before).  *sufficient = 0: the replayed batch itself
- * begins inside a > 8000x stack (or is shorter than 16,384 records without starting at the file's first record - the caller knows): call
- * ssv_getsv_begin again and replay a longer run.  At WGS depths the first 24,576 records before the range always suffice.
+ * begins inside a > 8000x stack, or is shorter than 16,384 records and so too short to tell (a batch that starts at the file's first record
+ * is exact whatever the answer: the caller knows that case): call ssv_getsv_begin again and replay a longer run.  At WGS depths the first 24,576 records before the range always suffice.
  */
 int ssv_getsv_prime(ssv_ctx *ctx, const ssv_batch_t *b, int32_t *sufficient);
 /*
@@ -390,7 +390,8 @@ int ssv_getsv_prime(ssv_ctx *ctx, const ssv_batch_t *b, int32_t *sufficient);
  * point_depth[n_points]    = depth at (tid, beg) (bam2depth.cpp:123-124); 0 outside every window
  * max_depth                = largest per-column depth inside the windows.  The depths follow libbam 0.1.16's pileup, which keeps at
  *                            most ~8000 reads alive: a read that is not the first at its start position is dropped when 2 + (accepted
- *                            reads of the contig ending at or after that start) > 8000 (bam_plp_push); batches must arrive in file order
+ *                            reads of the contig ending at or after that start, a read without M/D/N operation only while it is the
+ *                            first read at the current start) > 8000 (bam_plp_push); batches must arrive in file order
  */
 int ssv_getsv_finish(ssv_ctx *ctx, int32_t *counts,
                      const ssv_interval *ranges, int64_t n_ranges, uint64_t *range_sum,

@@ -574,8 +574,12 @@ static int64_t find_window(const ssv_interval *w, int64_t n, int32_t tid, int32_
  * The pileup's read cap (bam_plp_push of samtools 0.1.16: `iter->tid == b->core.tid && iter->pos == b->core.pos &&
  * iter->mp->cnt > iter->maxcnt` with maxcnt = 8000 and two nodes of the pool always allocated): a read that starts where the
  * previous accepted read of its contig started - i.e. not the first read at its start - is dropped when
- * 2 + (accepted reads of the contig whose bam_calend end is >= the start) > 8000.  The first read at a new start is always taken.
- * Pinned by tests/golden/getsv/deep*.  (Reads without any M/D/N operation are not counted as live here.) */
+ * 2 + (live reads) > 8000.  The first read at a new start is always taken.  Live reads: bam_plp_push keeps the node of a taken read iff
+ * `end > iter->pos || tid > iter->tid` (end = bam_calend), and the pileup frees it once it has emitted column end - 1.  iter->pos is the
+ * start of the read taken before (tid 0, pos 0 before the file's first read): when the first read of a new start is pushed it is still the
+ * previous start.  So every taken read whose end is >= the current start is live - and so is, until the start changes, a read without
+ * any M/D/N operation (end == start) that is the FIRST read at its start; such a read that is not the first at its start is not kept.
+ * Pinned by tests/golden/getsv/deep* and tests/golden/pileup_cap/reference.json. */
 #define ORC_PLP_MAXCNT 8000
 #define ORC_RING_BITS 22
 int orc_depth(const ssv_batch_t *batches, int n_batches, const ssv_interval *windows, int64_t n_windows,
@@ -603,14 +607,18 @@ int orc_depth(const ssv_batch_t *batches, int n_batches, const ssv_interval *win
 			{
 				int64_t p0 = b->pos[i], end = p0;
 				for (int k = 0; k < n; ++k) { int op = (int)(cig[k] & 15); if (op == C_M || op == C_D || op == C_N) end += (int64_t)(cig[k] >> 4); }
+				int first = 0; /* the first read at a new start */
 				if (b->tid[i] != plp_tid) { memset(ring, 0, ((size_t)ring_mask + 1) * sizeof(int32_t)); live = 0; plp_tid = b->tid[i]; plp_pos = -1; }
 				if (p0 != plp_pos) {
+					first = 1;
 					/* columns before p0 have been emitted: nodes with end <= p0 - 1 are gone */
 					if (plp_pos >= 0 && p0 - plp_pos <= ring_mask) { for (int64_t e = plp_pos; e < p0; ++e) { live -= ring[e & ring_mask]; ring[e & ring_mask] = 0; } }
 					else if (plp_pos >= 0) { memset(ring, 0, ((size_t)ring_mask + 1) * sizeof(int32_t)); live = 0; }
 					plp_pos = p0;
 				} else if (2 + live > ORC_PLP_MAXCNT) continue; /* dropped by bam_plp_push */
-				if (end > p0) { ring[end & ring_mask]++; live++; }
+				/* `end > iter->pos || tid > iter->tid`: for the first read at a start iter->pos is the previous start (< p0 <= end), or
+				 * the contig is new; only at (tid 0, pos 0), where the iterator begins, neither holds for a read without a span */
+				if (end > p0 || (first && (b->tid[i] != 0 || p0 != 0))) { ring[end & ring_mask]++; live++; }
 			}
 			int32_t col = b->pos[i] + 1; /* 1-based */
 			{

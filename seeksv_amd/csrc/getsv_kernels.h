@@ -934,9 +934,11 @@ __global__ void k_point_depth(const int32_t *__restrict__ win_tid, const int32_t
 // ---------------------------------------------------------------------------------------------------------------------
 // The read cap of the reference's pileup (libbam 0.1.16, bam_plp_push: `iter->tid == b->core.tid && iter->pos == b->core.pos &&
 // iter->mp->cnt > iter->maxcnt`, maxcnt = 8000, two pool nodes always allocated).  In file order, among the reads that pass the depth
-// filter: a read that is not the first at its start position is dropped when 2 + L > 8000, L = accepted reads of the contig whose
-// bam_calend end (M, D, N) is >= the start.  Pinned by the real reference on tests/golden/getsv/deep.*.  The rule is sequential, but it
-// can only bind where >= 7,998 earlier records start within one read span of a record ("deep" records: impossible below ~5,000x), so:
+// filter: a read that is not the first at its start position is dropped when 2 + L > 8000, L = live reads: the accepted reads of the
+// contig whose bam_calend end (M, D, N) is >= the start, and - until the start changes - an accepted read without any M / D / N operation
+// that was the first read at its start (bam_plp_push keeps a node iff `end > iter->pos || tid > iter->tid`, and iter->pos is still the
+// previous start when the first read of a new start arrives; a spanless read that is not the first at its start is not kept).  Pinned by
+// the real reference on tests/golden/getsv/deep.* and tests/golden/pileup_cap/reference.json.  The rule is sequential, but it can only bind where >= 7,998 earlier records start within one read span of a record ("deep" records: impossible below ~5,000x), so:
 //   * the streaming pass raises a flag when a wavefront's records of a tile start within one span (necessary for an interior deep record);
 //   * k_cap_mark then marks the 4096-record tiles that contain deep records (the first and last two tiles of a batch are always looked at:
 //     their look-back windows reach into the previous batch, whose last 8192 records are kept as (tid, pos, end, pass) in a tail buffer);
@@ -1073,7 +1075,8 @@ __global__ __launch_bounds__(WAVE) void k_cap_sweep(CapArgs c)
 					exempt = 1;
 				}
 				// in file order: a read is taken while 2 + live <= CAP_MAXCNT (bam_plp_push); every taken read with a reference span adds one
-				// to live.  Reads without any M / D / N operation (end == pos) do not: if the group holds one, decide it read by read.
+				// to live.  A read without any M / D / N operation (end == pos) does so only as the first read at its start (`end > iter->pos
+				// || tid > iter->tid`, below): if the group holds one, decide it read by read.
 				const bool in_grp = (grp >> lane) & 1ull;
 				const bool spanless = __any(in_grp && end <= pos);
 				if (!spanless) {
@@ -1096,8 +1099,11 @@ __global__ __launch_bounds__(WAVE) void k_cap_sweep(CapArgs c)
 						g &= g - 1;
 						const int q_end = __shfl(end, q, WAVE);
 						const bool accept = first || !(2 + live > CAP_MAXCNT);
+						// libbam keeps the node iff `end > iter->pos || tid > iter->tid`: for the first read at a start iter->pos is the previous
+						// start (< r_pos <= end) or the contig is new - only at (tid 0, pos 0), where the iterator begins, neither holds
+						const bool kept = q_end > r_pos || (first && (r_tid | r_pos) != 0);
 						first = false;
-						if (accept) { if (q_end > r_pos) { if (lane == q) ring[q_end & mask] += 1; ++live; } }
+						if (accept) { if (kept) { if (lane == q) ring[q_end & mask] += 1; ++live; } }
 						else if (lane == q) dropped |= 1ull << lane;
 						__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 					}
