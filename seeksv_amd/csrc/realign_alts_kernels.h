@@ -14,7 +14,7 @@
 //              the k-th choice, every lane clears the slots of the chosen locus.  A query without a qualifying candidate - nearly all of them - leaves
 //              after one pass over its slots and one ballot.
 //   walk       only a candidate's score outlived the scoring (s_ss); lanes 0 .. k - 1 walk one chosen diagonal each again, side by side: one more walk of
-//              the query, not k (ra_alt_walk: the scoring loop of k_ra_query_t word for word).
+//              the query, not k (ra_alt_walk: a copy of k_ra_query_t's step 4, see there).
 //   output     strided: alts[q * max_alt + r] and alt_n[q].  Most queries have none, so the host call scans the counts (scan.h) and k_ra_alt_compact gathers the
 //              hits into one dense array: alt_off[n + 1] and alt_off[n] hits cross PCIe.
 //   gapped     the alternates are the first stage's (floor RA_K) and need RA_MIN_SCORE there.  A winner that the refinement (k_ra_gap) leaves unaligned scored
@@ -58,6 +58,8 @@ __device__ __forceinline__ bool ra_alt_before(const uint16_t *ss, const int64_t 
 }
 
 // the query (codes of the candidate's orientation, n bases) along diagonal d inside contig t, as k_ra_query_t scores it -> score, segment, mismatches
+// (A copy of that kernel's walk without its two early exits - a chosen candidate passed them.  One function for both moved the default kernels from
+// 60 / 72 VGPRs to 52-54 / 66 whether the floor was a template or a plain parameter and the results references, pointers or a struct: DESIGN.md 10e.)
 __device__ __forceinline__ void ra_alt_walk(const RaIndex &ix, const uint8_t *code, int n, int64_t d, int t, int *score, int *q_beg, int *q_end, int *n_mm)
 {
 	const int64_t c_lo = ix.ctg_off[t], c_hi = ix.ctg_off[t + 1];
@@ -103,9 +105,7 @@ __device__ __forceinline__ void ra_alts(const RaAltArgs<Base> &a, int w, int lan
 		const int c = j * WAVE + lane;
 		if (c >= m) continue;
 		const int sc = ss[c] & 0x7fff;
-		const int64_t d = diag[c];
-		const bool same_locus = (ss[c] >> 15) == win_st && tid[c] == win_tid && (d - win_diag <= 32 && win_diag - d <= 32);
-		if (sc >= RA_MIN_SCORE && RA_ALT_NUM * sc >= RA_ALT_DEN * best && !same_locus) alive |= 1u << j;
+		if (sc >= RA_MIN_SCORE && RA_ALT_NUM * sc >= RA_ALT_DEN * best && !ra_same_locus(ss[c] >> 15, tid[c], diag[c], win_st, win_tid, win_diag)) alive |= 1u << j;
 	}
 	int k = 0, mine = -1;
 	while (k < a.max_alt && __ballot(alive != 0) != 0ull) { // (wave-uniform)
@@ -127,8 +127,7 @@ __device__ __forceinline__ void ra_alts(const RaAltArgs<Base> &a, int w, int lan
 		for (int j = 0; j < SLOTS; ++j) {
 			const int c = j * WAVE + lane;
 			if (!((alive >> j) & 1u)) continue;
-			const int64_t d = diag[c];
-			if ((ss[c] >> 15) == p_st && tid[c] == p_tid && (d - p_diag <= 32 && p_diag - d <= 32)) alive &= ~(1u << j);
+			if (ra_same_locus(ss[c] >> 15, tid[c], diag[c], p_st, p_tid, p_diag)) alive &= ~(1u << j);
 		}
 		++k;
 	}

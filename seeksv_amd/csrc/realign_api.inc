@@ -11,6 +11,8 @@ struct ssv_realign_state {
 	int32_t n_ctg = 0;
 	uint64_t mask = 0;
 	bool ready = false;
+	// what the kernels know of the reference; table and mask are null and 0 while the sorted index stands
+	RaIndex index() { return RaIndex{ref_p, n_bases, P<int64_t>(ctg), n_ctg, P<uint32_t>(table), mask}; }
 };
 
 // the reference and the contig offsets on the device (both kinds of index)
@@ -30,20 +32,30 @@ static int realign_reference(ssv_ctx *c, ssv_realign_state &R, const uint64_t *r
 	return SSV_OK;
 }
 
-int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped)
+// What both index calls begin with: the arguments, the context's state, the other kind of index gone (a context holds one kind at a time; whichever
+// buffers of the five are held are the other kind's), the reference on the device.  max_occ counts for the sorted index only.
+static int realign_index_begin(ssv_ctx *c, bool sorted, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int32_t max_occ = 1)
 {
 	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
+	if (sorted && (max_occ < 1 || max_occ > 65535)) { c->err = "max_occ outside 1..65535"; return SSV_E_ARG; }
 	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
 	HIPCHECK(c, hipSetDevice(c->device));
 	if (!c->ra) c->ra.reset(new ssv_realign_state());
 	ssv_realign_state &R = *c->ra;
 	R.ready = false;
-	if (R.sorted) { // the hash index replaces a sorted one
+	if (sorted ? R.table.p != nullptr : R.sorted) {
 		HIPCHECK(c, hipStreamSynchronize(c->st));
-		for (DBuf *b : {&R.skeys, &R.svals, &R.sdir}) HIPCHECK(c, b->release());
-		R.sorted = false;
+		for (DBuf *b : {&R.table, &R.dropped, &R.skeys, &R.svals, &R.sdir}) HIPCHECK(c, b->release());
+		R.mask = 0;
 	}
-	CHECK(realign_reference(c, R, ref2bit, mem, n_bases, target_off, n_targets));
+	R.sorted = sorted;
+	return realign_reference(c, R, ref2bit, mem, n_bases, target_off, n_targets);
+}
+
+int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int64_t *n_dropped)
+{
+	CHECK(realign_index_begin(c, false, ref2bit, mem, n_bases, target_off, n_targets));
+	ssv_realign_state &R = *c->ra;
 	const int64_t samples = (n_bases + RA_SAMPLE - 1) / RA_SAMPLE;
 	uint64_t slots = 1024;
 	while (slots < (uint64_t)samples * 2) slots <<= 1;
@@ -52,11 +64,9 @@ int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t 
 	CHECK(ensure(c, R.dropped, 8));
 	HIPCHECK(c, hipMemsetAsync(R.dropped.p, 0, 8, c->st));
 	R.mask = slots - 1;
-	RaIndex ix;
-	ix.ref = R.ref_p; ix.n_bases = n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = n_targets; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
 	{
 		ProfScope ps(c, P_REALIGN_INDEX, samples);
-		k_ra_build<<<grid_for(samples, BLOCK), BLOCK, 0, c->st>>>(ix, reinterpret_cast<unsigned long long *>(R.dropped.p));
+		k_ra_build<<<grid_for(samples, BLOCK), BLOCK, 0, c->st>>>(R.index(), reinterpret_cast<unsigned long long *>(R.dropped.p));
 	}
 	HIPCHECK(c, hipGetLastError());
 	unsigned long long d = 0;
@@ -71,20 +81,8 @@ int ssv_realign_index(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t 
 // buffers, its histograms and the statistics' partial sums are freed when the index stands.
 int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, int64_t n_bases, const int64_t *target_off, int32_t n_targets, int32_t max_occ, ssv_realign_index_stats *stats)
 {
-	if (!c || !ref2bit || !target_off || n_targets <= 0 || n_bases <= 0 || target_off[0] != 0 || target_off[n_targets] != n_bases) return SSV_E_ARG;
-	if (max_occ < 1 || max_occ > 65535) { c->err = "max_occ outside 1..65535"; return SSV_E_ARG; }
-	if (n_bases / RA_SAMPLE >= (int64_t)0xfffffffe) { c->err = "reference too long for the re-aligner's 32-bit slots"; return SSV_E_RANGE; }
-	HIPCHECK(c, hipSetDevice(c->device));
-	if (!c->ra) c->ra.reset(new ssv_realign_state());
+	CHECK(realign_index_begin(c, true, ref2bit, mem, n_bases, target_off, n_targets, max_occ));
 	ssv_realign_state &R = *c->ra;
-	R.ready = false;
-	if (R.table.p) { // the sorted index replaces a hash index
-		HIPCHECK(c, hipStreamSynchronize(c->st));
-		for (DBuf *b : {&R.table, &R.dropped}) HIPCHECK(c, b->release());
-		R.mask = 0;
-	}
-	R.sorted = true;
-	CHECK(realign_reference(c, R, ref2bit, mem, n_bases, target_off, n_targets));
 	const int64_t samples = (n_bases + RA_SAMPLE - 1) / RA_SAMPLE;
 	int bits = 0;
 	while (bits < 30 && ((int64_t)2 << bits) <= samples) ++bits; // floor(log2(samples)), at most 30
@@ -94,8 +92,6 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 	CHECK(ensure(c, keys2, (size_t)samples * 8)); CHECK(ensure(c, vals2, (size_t)samples * 4));
 	CHECK(ensure(c, ghist, (size_t)256 * nt * 4)); CHECK(ensure(c, scratch, (size_t)scan_scratch_elems(256 * nt) * 4));
 	CHECK(ensure(c, part, (size_t)(n_part + 1) * sizeof(RasStats)));
-	RaIndex ix;
-	ix.ref = R.ref_p; ix.n_bases = n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = n_targets; ix.table = nullptr; ix.mask = 0;
 	uint64_t *keys[2] = {P<uint64_t>(R.skeys), P<uint64_t>(keys2)};
 	uint32_t *vals[2] = {P<uint32_t>(R.svals), P<uint32_t>(vals2)};
 	static_assert(((RAS_KEY_BITS + 7) / 8) % 2 == 0, "an even number of passes: the sorted pairs end in the buffers they started in");
@@ -104,7 +100,7 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 	const uint32_t *dir_end = P<uint32_t>(R.sdir) + ((size_t)1 << bits); // = the number of indexed positions
 	{
 		ProfScope ps(c, P_REALIGN_INDEX, samples);
-		k_ras_keys<<<grid_for(samples, BLOCK), BLOCK, 0, c->st>>>(ix, samples, keys[0], vals[0]);
+		k_ras_keys<<<grid_for(samples, BLOCK), BLOCK, 0, c->st>>>(R.index(), samples, keys[0], vals[0]);
 		const int cur = radix_sort_pairs(c->st, keys, vals, samples, RAS_KEY_BITS, P<uint32_t>(ghist), P<uint32_t>(scratch));
 		if (cur != 0) { c->err = "sorted index: the sort ended in its second buffer"; return SSV_E_STATE; }
 		k_ras_dir<<<grid_for(((int64_t)1 << bits) + 1, BLOCK), BLOCK, 0, c->st>>>(keys[0], samples, bits, P<uint32_t>(R.sdir));
@@ -121,39 +117,28 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 	return SSV_OK;
 }
 
-// the query kernel of the index that stands - its instantiation with the candidate floor at RA_K when `floor` - over the n sequences in R.seqs / R.offs -> R.hits;
-// max_alt > 0: the instantiation that goes on to the alternates -> R.alts (max_alt per query), R.alt_n
+// One instantiation of the query kernel over the n sequences in R.seqs / R.offs -> R.hits: the arguments every one takes, inside the sorted index's
+// and the alternates' layers where the instantiation has them (-> R.alts, max_alt per query, and R.alt_n)
+extern "C++" template <bool SORTED, int FLOOR, bool ALTS> // (this file is included inside extern "C")
+static void realign_launch_as(ssv_ctx *c, ssv_realign_state &R, int64_t n, int32_t max_alt)
+{
+	using Query = std::conditional_t<SORTED, RasQueryArgs, RaQueryArgs>;
+	using Args = std::conditional_t<ALTS, RaAltArgs<Query>, Query>;
+	Args a;
+	static_cast<RaQueryArgs &>(a) = RaQueryArgs{R.index(), P<char>(R.seqs), P<uint64_t>(R.offs), n, P<RaHit>(R.hits)};
+	if constexpr (SORTED) a.sx = RasIndex{P<uint64_t>(R.skeys), P<uint32_t>(R.svals), P<uint32_t>(R.sdir), R.dir_bits, R.max_occ};
+	if constexpr (ALTS) { a.alts = P<RaHit>(R.alts); a.alt_n = P<int32_t>(R.alt_n); a.max_alt = max_alt; }
+	k_ra_query_t<SORTED, Args, FLOOR, ALTS><<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+}
+
+// the query kernel of the index that stands - with the candidate floor at RA_K when `floor`, going on to the alternates when max_alt > 0
 static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor, int32_t max_alt = 0)
 {
-	RaIndex ix;
-	ix.ref = R.ref_p; ix.n_bases = R.n_bases; ix.ctg_off = P<int64_t>(R.ctg); ix.n_ctg = R.n_ctg; ix.table = P<uint32_t>(R.table); ix.mask = R.mask;
+	static constexpr decltype(&realign_launch_as<false, RA_MIN_SCORE, false>) launch[2][2][2] = { // [sorted][floor][alts]: k_ra_query, k_ra_query_alts, k_ra_query_floor, ... k_ras_query_floor_alts
+		{{realign_launch_as<false, RA_MIN_SCORE, false>, realign_launch_as<false, RA_MIN_SCORE, true>}, {realign_launch_as<false, RA_K, false>, realign_launch_as<false, RA_K, true>}},
+		{{realign_launch_as<true, RA_MIN_SCORE, false>, realign_launch_as<true, RA_MIN_SCORE, true>}, {realign_launch_as<true, RA_K, false>, realign_launch_as<true, RA_K, true>}}};
 	ProfScope ps(c, P_REALIGN_QUERY, n);
-	if (R.sorted) {
-		RasQueryArgs a;
-		a.ix = ix;
-		a.sx.keys = P<uint64_t>(R.skeys); a.sx.vals = P<uint32_t>(R.svals); a.sx.dir = P<uint32_t>(R.sdir); a.sx.bits = R.dir_bits; a.sx.max_occ = R.max_occ;
-		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-		if (max_alt > 0) {
-			RaAltArgs<RasQueryArgs> x;
-			static_cast<RasQueryArgs &>(x) = a;
-			x.alts = P<RaHit>(R.alts); x.alt_n = P<int32_t>(R.alt_n); x.max_alt = max_alt;
-			if (floor) k_ras_query_floor_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
-			else k_ras_query_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
-		} else if (floor) k_ras_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-		else k_ras_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-	} else {
-		RaQueryArgs a;
-		a.ix = ix;
-		a.seqs = P<char>(R.seqs); a.seq_off = P<uint64_t>(R.offs); a.n = n; a.hits = P<RaHit>(R.hits);
-		if (max_alt > 0) {
-			RaAltArgs<RaQueryArgs> x;
-			static_cast<RaQueryArgs &>(x) = a;
-			x.alts = P<RaHit>(R.alts); x.alt_n = P<int32_t>(R.alt_n); x.max_alt = max_alt;
-			if (floor) k_ra_query_floor_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
-			else k_ra_query_alts<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(x);
-		} else if (floor) k_ra_query_floor<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-		else k_ra_query<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
-	}
+	launch[R.sorted][floor][max_alt > 0](c, R, n, max_alt);
 }
 
 // ssv_realign_query (gaps == nullptr), ssv_realign_query_gapped and - max_alt > 0 - ssv_realign_query_alts; `who` names the caller in the error text

@@ -59,10 +59,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_gap(RaGapArgs a)
 	const int n = (int)(a.seq_off[q + 1] - o0); // RA_K..RA_MAX_Q: the query kernel aligned it
 	uint8_t *code = s_code[w];
 	int16_t *pre = s_pre[w];
-	for (int i = lane; i < n; i += WAVE) {
-		const uint32_t c = ra_code(a.seqs[o0 + i]);
-		if (h.reverse) code[n - 1 - i] = (uint8_t)(c < 4 ? 3 - c : 4); else code[i] = (uint8_t)c;
-	}
+	ra_codes(a.seqs + o0, n, lane, h.reverse ? RA_REV : RA_FWD, code, code); // the hit's orientation only
 	const int64_t c_lo = a.ctg_off[h.tid], c_hi = a.ctg_off[h.tid + 1];
 	const int64_t d = c_lo + h.pos - h.q_beg;
 	const int qb = h.q_beg, qe = h.q_end;
@@ -120,8 +117,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_gap(RaGapArgs a)
 	constexpr int BIAS = 1 << 14; // J > -BIAS: two pieces of at most RA_MAX_Q bases at -4 and the gap
 	const int key = wave_max(best_j == INT32_MIN ? 0 : (((best_j + BIAS) << 6) | (WAVE - 1 - lane)));
 	const int win_j = (key >> 6) - BIAS, win_lane = WAVE - 1 - (key & (WAVE - 1));
-	RaHit none;
-	none.tid = -1; none.pos = -1; none.q_beg = 0; none.q_end = 0; none.score = 0; none.second = 0; none.n_mismatch = 0; none.reverse = 0; none.mapq = 0; none.pad[0] = h.pad[0]; none.pad[1] = 0;
+	const RaHit none = ra_unaligned(h.pad[0]);
 	if (key == 0 || win_j <= h.score) { // no gap pays
 		if (lane == 0) {
 			if (h.score < RA_MIN_SCORE) a.hits[q] = none;
@@ -156,8 +152,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_gap(RaGapArgs a)
 	for (int i = j; i < e; ++i) mm += code[i] == ra_base_at(a.ref, dr + i) ? 0 : 1;
 	h.pos = (int32_t)(dl + b - c_lo);
 	h.q_beg = b; h.q_end = e; h.score = win_j; h.n_mismatch = mm;
-	const int lead = win_j - h.second;
-	h.mapq = (uint8_t)(h.second >= win_j ? 0 : (lead >= 10 ? 60 : (lead * 6 > 1 ? lead * 6 : 1)));
+	h.mapq = ra_mapq(win_j, h.second);
 	a.hits[q] = h;
 	a.gaps[q] = RaGap{k, g};
 }

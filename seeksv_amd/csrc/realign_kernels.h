@@ -108,6 +108,42 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 	}
 }
 
+// the codes of a query's n bases, written by the lanes of one wavefront: forward to fwd[0, n) when `want` has RA_FWD, reverse complement to rev[0, n) when it has RA_REV
+constexpr int RA_FWD = 1, RA_REV = 2;
+__device__ __forceinline__ void ra_codes(const char *seq, int n, int lane, int want, uint8_t *fwd, uint8_t *rev)
+{
+	for (int i = lane; i < n; i += WAVE) {
+		const uint32_t c = ra_code(seq[i]);
+		if (want & RA_FWD) fwd[i] = (uint8_t)c;
+		if (want & RA_REV) rev[n - 1 - i] = (uint8_t)(c < 4 ? 3 - c : 4);
+	}
+}
+
+// the K-mer at offset o of a query's codes, packed like ra_kmer_at's; *ok: all of its bases are A C G T
+__device__ __forceinline__ uint64_t ra_kmer(const uint8_t *code, int o, bool *ok)
+{
+	uint64_t km = 0;
+	bool all = true;
+	for (int k = 0; k < RA_K; ++k) { const uint32_t c = code[o + k]; all = all && c < 4; km |= (uint64_t)(c & 3u) << (2 * k); }
+	*ok = all;
+	return km;
+}
+
+// One locus: same strand, same contig, diagonals at most RA_LOCUS_WINDOW apart.  `second` leaves the winner's locus out, the alternates the winner's and
+// every chosen alternate's: one window for all of them (DESIGN.md 10d rests on that).
+constexpr int RA_LOCUS_WINDOW = 32;
+__device__ __forceinline__ bool ra_same_locus(int st, int tid, int64_t diag, int st2, int tid2, int64_t diag2) { return st == st2 && tid == tid2 && diag - diag2 <= RA_LOCUS_WINDOW && diag2 - diag <= RA_LOCUS_WINDOW; }
+
+// MAPQ from the score and the best score at another locus: 0 when that is as good, 60 from a lead of 10, between them 6 per point
+__device__ __forceinline__ uint8_t ra_mapq(int score, int second)
+{
+	const int gap = score - second;
+	return (uint8_t)(second >= score ? 0 : (gap >= 10 ? 60 : (gap * 6 > 1 ? gap * 6 : 1)));
+}
+
+// the hit of a query that is not aligned: tid and pos -1, everything else 0 but the flags in pad[0]
+__device__ __forceinline__ RaHit ra_unaligned(uint8_t flags) { return RaHit{-1, -1, 0, 0, 0, 0, 0, 0, 0, {flags, 0}}; }
+
 // One wavefront per query.  1. codes of both orientations into LDS.  2. every lane takes K-mer offsets lane, lane + 64, ... of both
 // orientations, probes the table and records the diagonals (reference position of query base 0) of verified seeds.  3. duplicates
 // out (a matching stretch of m bases yields ~(m - K) / SAMPLE seeds on one diagonal).  4. one lane per distinct diagonal scores the
@@ -120,6 +156,8 @@ __device__ __forceinline__ uint32_t ra_code(char ch)
 // the smaller contig id, where the hash index leaves them to the order of the lanes.  k_ra_query = k_ra_query_t<false, RaQueryArgs> is the hash index's
 // kernel (a profiler shows the template's name).  (A template KERNEL, not a __device__ body called from two kernels: inlined from a function hipcc compiled
 // the hash path to other code - 52 VGPRs for 60 - that ran slower; this form measures like the kernel before it)
+// For the same reason step 4's walk stays inline although ra_alt_walk (realign_alts_kernels.h) repeats it - 52-54 VGPRs in every form of a shared function
+// that was tried, DESIGN.md 10e: a change to the scoring goes to both.
 // FLOOR is the score a candidate needs to be kept and a winner to be reported: RA_MIN_SCORE, or RA_K for the gapped query (realign_gap_kernels.h: k_ra_gap
 // refines the winner and applies RA_MIN_SCORE to what it leaves; `second` counts candidates at RA_MIN_SCORE or more only).  At the default every
 // FLOOR test is the one the kernel had before the parameter.
@@ -139,17 +177,12 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 	const RaIndex &ix = a.ix;
 	const uint64_t o0 = a.seq_off[q];
 	const int n = (int)(a.seq_off[q + 1] - o0);
-	RaHit out;
-	out.tid = -1; out.pos = -1; out.q_beg = 0; out.q_end = 0; out.score = 0; out.second = 0; out.n_mismatch = 0; out.reverse = 0; out.mapq = 0; out.pad[0] = out.pad[1] = 0;
+	RaHit out = ra_unaligned(0);
 	if (n < RA_K || n > RA_MAX_Q) {
 		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; }
 		return;
 	}
-	for (int i = lane; i < n; i += WAVE) {
-		const uint32_t c = ra_code(a.seqs[o0 + i]);
-		s_code[w][0][i] = (uint8_t)c;
-		s_code[w][1][n - 1 - i] = (uint8_t)(c < 4 ? 3 - c : 4);
-	}
+	ra_codes(a.seqs + o0, n, lane, RA_FWD | RA_REV, s_code[w][0], s_code[w][1]);
 	if (lane == 0) s_n[w] = 0;
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -160,9 +193,8 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 	} else for (int st = 0; st < 2; ++st) {
 		const uint8_t *code = s_code[w][st];
 		for (int o = lane; o + RA_K <= n; o += WAVE) {
-			uint64_t km = 0;
-			bool ok = true;
-			for (int k = 0; k < RA_K; ++k) { const uint32_t c = code[o + k]; ok = ok && c < 4; km |= (uint64_t)(c & 3u) << (2 * k); }
+			bool ok;
+			const uint64_t km = ra_kmer(code, o, &ok);
 			if (!ok) continue;
 			uint64_t slot = ra_hash(km) & ix.mask;
 			for (int probe = 0; probe < RA_MAX_PROBE; ++probe) {
@@ -249,8 +281,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 	int second = 0;
 	for (int c = lane; c < m; c += WAVE) {
 		const int sc = s_ss[w][c] & 0x7fff;
-		const int64_t d = s_diag[w][c];
-		const bool same_locus = (s_ss[w][c] >> 15) == win_st && s_tid[w][c] == win_tid && (d - win_diag <= 32 && win_diag - d <= 32);
+		const bool same_locus = ra_same_locus(s_ss[w][c] >> 15, s_tid[w][c], s_diag[w][c], win_st, win_tid, win_diag);
 		if (sc > second && !same_locus && (FLOOR == RA_MIN_SCORE || sc >= RA_MIN_SCORE)) second = sc;
 	}
 	second = wave_max(second);
@@ -259,8 +290,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		out.pos = (int32_t)(best_diag + best_beg - ix.ctg_off[best_tid]);
 		out.q_beg = best_beg; out.q_end = best_end; out.score = best_score; out.second = second; out.n_mismatch = best_mm;
 		out.reverse = (uint8_t)best_st;
-		const int gap = best_score - second;
-		out.mapq = (uint8_t)(second >= best_score ? 0 : (gap >= 10 ? 60 : (gap * 6 > 1 ? gap * 6 : 1)));
+		out.mapq = ra_mapq(best_score, second);
 		a.hits[q] = out;
 	}
 	if constexpr (ALTS) ra_alts(a, w, lane, n, m, q, s_code, s_diag, s_ss, s_tid, win_st, win_tid, win_diag, win_score, win_lane, (uint32_t)out.pad[0]);

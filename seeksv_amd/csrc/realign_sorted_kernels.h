@@ -100,9 +100,22 @@ __device__ __forceinline__ int64_t ras_run_end(const uint64_t *keys, int64_t fir
 constexpr int RAS_STATS_ROUNDS = 8;
 constexpr int RAS_STATS_TILE = BLOCK * RAS_STATS_ROUNDS;
 
-__global__ __launch_bounds__(BLOCK) void k_ras_stats(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ n_indexed_p, uint32_t max_occ, RasStats *__restrict__ part)
+// the threads' figures over the whole block (sums, and the maximum of occ) -> *out, written by thread 0; called by every thread of the block
+__device__ __forceinline__ void ras_stats_block(uint64_t distinct, uint64_t occ, uint64_t over, RasStats *out)
 {
 	__shared__ RasStats s_w[WAVES_PER_BLOCK];
+	distinct = wave_sum(distinct); occ = wave_max(occ); over = wave_sum(over);
+	if (lane_id() == 0) { s_w[wave_id()].n_distinct = distinct; s_w[wave_id()].occ_max = occ; s_w[wave_id()].n_over_cap = over; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		RasStats t = s_w[0];
+		for (int w = 1; w < WAVES_PER_BLOCK; ++w) { t.n_distinct += s_w[w].n_distinct; t.occ_max = s_w[w].occ_max > t.occ_max ? s_w[w].occ_max : t.occ_max; t.n_over_cap += s_w[w].n_over_cap; }
+		*out = t;
+	}
+}
+
+__global__ __launch_bounds__(BLOCK) void k_ras_stats(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ n_indexed_p, uint32_t max_occ, RasStats *__restrict__ part)
+{
 	const int64_t n_indexed = *n_indexed_p; // the directory's last slot: the grid covers every sampled position, the blocks behind the indexed ones leave zeros
 	uint64_t distinct = 0, occ = 0, over = 0;
 	for (int r = 0; r < RAS_STATS_ROUNDS; ++r) {
@@ -116,30 +129,15 @@ __global__ __launch_bounds__(BLOCK) void k_ras_stats(const uint64_t *__restrict_
 			over += len > max_occ ? 1 : 0;
 		}
 	}
-	distinct = wave_sum(distinct); occ = wave_max(occ); over = wave_sum(over);
-	if (lane_id() == 0) { s_w[wave_id()].n_distinct = distinct; s_w[wave_id()].occ_max = occ; s_w[wave_id()].n_over_cap = over; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		RasStats t = s_w[0];
-		for (int w = 1; w < WAVES_PER_BLOCK; ++w) { t.n_distinct += s_w[w].n_distinct; t.occ_max = s_w[w].occ_max > t.occ_max ? s_w[w].occ_max : t.occ_max; t.n_over_cap += s_w[w].n_over_cap; }
-		part[blockIdx.x] = t;
-	}
+	ras_stats_block(distinct, occ, over, &part[blockIdx.x]);
 }
 
 // one block
 __global__ __launch_bounds__(BLOCK) void k_ras_stats_sum(const RasStats *__restrict__ part, int64_t n_part, RasStats *__restrict__ out)
 {
-	__shared__ RasStats s_w[WAVES_PER_BLOCK];
 	uint64_t distinct = 0, occ = 0, over = 0;
 	for (int64_t i = threadIdx.x; i < n_part; i += BLOCK) { distinct += part[i].n_distinct; occ = part[i].occ_max > occ ? part[i].occ_max : occ; over += part[i].n_over_cap; }
-	distinct = wave_sum(distinct); occ = wave_max(occ); over = wave_sum(over);
-	if (lane_id() == 0) { s_w[wave_id()].n_distinct = distinct; s_w[wave_id()].occ_max = occ; s_w[wave_id()].n_over_cap = over; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		RasStats t = s_w[0];
-		for (int w = 1; w < WAVES_PER_BLOCK; ++w) { t.n_distinct += s_w[w].n_distinct; t.occ_max = s_w[w].occ_max > t.occ_max ? s_w[w].occ_max : t.occ_max; t.n_over_cap += s_w[w].n_over_cap; }
-		*out = t;
-	}
+	ras_stats_block(distinct, occ, over, out);
 }
 
 // first sorted entry of the 20-mer km, or -1
@@ -164,25 +162,12 @@ __device__ __forceinline__ uint32_t ras_occ(const RasIndex &sx, uint64_t km)
 	return (uint32_t)(ras_run_end(sx.keys, first, lim, km) - first);
 }
 
-__device__ __forceinline__ uint64_t ras_kmer(const uint8_t *code, int o, bool *ok)
-{
-	uint64_t km = 0;
-	bool all = true;
-	for (int k = 0; k < RA_K; ++k) { const uint32_t c = code[o + k]; all = all && c < 4; km |= (uint64_t)(c & 3u) << (2 * k); }
-	*ok = all;
-	return km;
-}
-
 __device__ __forceinline__ int ras_class(uint32_t occ) { return occ <= 1 ? 0 : 32 - __clz((int)(occ - 1)); }
 
-struct RasQueryArgs { // RaQueryArgs + the sorted index
-	RaIndex ix;               // the reference and its contigs (table and mask unused)
-	const char *seqs;         // concatenated ASCII sequences
-	const uint64_t *seq_off;  // [n + 1]
-	int64_t n;
-	RaHit *hits;
+struct RasQueryArgs : RaQueryArgs { // ix: the reference and its contigs (table and mask unused)
 	RasIndex sx;
 };
+static_assert(sizeof(RasQueryArgs) == sizeof(RaQueryArgs) + sizeof(RasIndex), "the sorted index lies right behind the base's fields");
 
 constexpr int RAS_MAX_OFF = RA_MAX_Q - RA_K + 1; // 20-mer offsets of the longest query
 
@@ -199,7 +184,7 @@ __device__ __forceinline__ int ras_seeds(const RasQueryArgs &a, int w, int lane,
 	for (int st = 0; st < 2; ++st) {
 		for (int o = lane; o < n_off; o += WAVE) {
 			bool ok;
-			const uint64_t km = ras_kmer(s_code[w][st], o, &ok);
+			const uint64_t km = ra_kmer(s_code[w][st], o, &ok);
 			uint32_t occ = ok ? ras_occ(sx, km) : 0u;
 			if (occ > (uint32_t)sx.max_occ) { masked = 1; occ = 0; }
 			s_occ[w][st][o] = (uint16_t)occ;
@@ -225,7 +210,7 @@ __device__ __forceinline__ int ras_seeds(const RasQueryArgs &a, int w, int lane,
 				const uint32_t at = filled + inc - occ;
 				if (occ && at < (uint32_t)RA_MAX_CAND) {
 					bool ok;
-					const int64_t first = ras_first(sx, ras_kmer(s_code[w][st], o, &ok));
+					const int64_t first = ras_first(sx, ra_kmer(s_code[w][st], o, &ok));
 					const uint32_t take = occ < (uint32_t)RA_MAX_CAND - at ? occ : (uint32_t)RA_MAX_CAND - at;
 					for (uint32_t j = 0; j < take; ++j) {
 						const int64_t p = (int64_t)sx.vals[first + j] * RA_SAMPLE;

@@ -415,12 +415,16 @@ class Context:
         self._check(self._lib.ssv_realign_index_sorted(self._h, ptr, mem, int(off[-1]), off.ctypes.data, len(off) - 1, int(max_occ), C.byref(st)), "ssv_realign_index_sorted")
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    @staticmethod
+    def _realign_io(seqs):
+        """list of str -> (the sequences back to back, their offsets [n + 1], zeroed ssv_realign_hit [n])"""
+        off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.uint64)
+        return "".join(seqs).encode(), off, np.zeros(len(seqs), dtype=np.dtype(_abi.REALIGN_HIT))
+
     def realign(self, seqs, gapped=False):
         """list of str -> numpy structured array of ssv_realign_hit; gapped: one insertion or deletion per alignment (ssv_realign_query_gapped)
         -> (hits, structured array of ssv_realign_gap)"""
-        blob = "".join(seqs).encode()
-        off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.uint64)
-        hits = np.zeros(len(seqs), dtype=np.dtype(_abi.REALIGN_HIT))
+        blob, off, hits = self._realign_io(seqs)
         if not gapped:
             if len(seqs):
                 self._check(self._lib.ssv_realign_query(self._h, C.c_char_p(blob), off.ctypes.data, len(seqs), hits.ctypes.data), "ssv_realign_query")
@@ -434,9 +438,7 @@ class Context:
         """realign() + every query's other loci (ssv_realign_query_alts, max_alt in 1..16) -> (hits, gaps or None, alt_off, alts): query i's alternates
         are alts[alt_off[i]:alt_off[i + 1]], in the rule's order; hits["pad"][:, 0] & _abi.RA_F_ALT_CUT where more loci qualified than max_alt"""
         n = len(seqs)
-        blob = "".join(seqs).encode()
-        off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.uint64)
-        hits = np.zeros(n, dtype=np.dtype(_abi.REALIGN_HIT))
+        blob, off, hits = self._realign_io(seqs)
         gaps = np.zeros(n, dtype=np.dtype(_abi.REALIGN_GAP)) if gapped else None
         alt_off = np.full(n + 1, -1, dtype=np.int64)
         alts = np.zeros(max(n * max(int(max_alt), 0), 1), dtype=np.dtype(_abi.REALIGN_HIT))
