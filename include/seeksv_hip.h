@@ -587,8 +587,9 @@ const char *ssv_prof_names(void);
  * like random sequence (the synthetic genomes of bench.py / tests).  getsv consumes of each clip.bam record: flag & {4, 16, 256},
  * MAPQ == 0 or not, tid, pos, the CIGAR with its S ends, the read name = the sequence (getsv.cpp:25-71, getsv.h:445-527).
  * K-mer index of the reference in HBM + seed look-ups on both strands + ungapped extension with bwa mem's default scores
- * (match 1, mismatch 4, end clipping 5, minimum 30).  NOT bit-identical to bwa: no gaps unless asked for (one), no chaining, no
- * supplementary records, one record per query unless its other loci are asked for (ssv_realign_query_alts: up to 1 + 16). */
+ * (match 1, mismatch 4, end clipping 5, minimum 30).  NOT bit-identical to bwa: no gaps unless asked for (one), no chaining, one
+ * record per query unless its other loci (ssv_realign_query_alts: up to 1 + 16) or - for whole reads - its second piece as a
+ * supplementary record (ssv_realign_query_split: 1 + 1, never a third piece) are asked for. */
 typedef struct {
 	int32_t tid;         /* -1: unaligned (flag 4) */
 	int32_t pos;         /* 0-based reference position of the aligned segment's first base */
@@ -650,13 +651,29 @@ int ssv_realign_query_gapped(ssv_ctx *ctx, const char *seqs, const uint64_t *seq
  * An unaligned, too short or too long query has none.  Limits: alternates are not gap-refined (with `gapped` they come from the first stage, need 30 or more
  * there, and a primary that the refinement leaves unaligned has none); at most 16; on the hash index a query with more than 192 seeds keeps the candidates
  * it happened to keep (as its primary does), and a primary tied in score, strand and diagonal between two contigs is the lanes' choice there, the other
- * contig's candidate then being an alternate (the sorted index decides both); split sequences still get no supplementary records.
+ * contig's candidate then being an alternate (the sorted index decides both); no supplementary records here (ssv_realign_query_split has them).
  * alt_off[n + 1] (host): query i's alternates are alts[alt_off[i] .. alt_off[i + 1]), in the rule's order; alts (host) needs room for n * max_alt hits,
  * alt_off[n] are written.  Errors as the other query calls; SSV_E_ARG also for max_alt outside 1..16, a NULL alt_off or alts, gapped without gaps.
  * n == 0: SSV_OK and alt_off[0] = 0. */
 int ssv_realign_query_alts(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, int32_t max_alt, int32_t gapped,
                            ssv_realign_hit *hits, ssv_realign_gap *gaps /* required iff gapped */,
                            int64_t *alt_off /* n + 1 */, ssv_realign_hit *alts /* room for n * max_alt; alt_off[n] are written */);
+/* ssv_realign_query for WHOLE reads that may cross a breakpoint (`seeksv realign -P`; its records are what getsv -F reads): the primary and, where the read
+ * has one, a second piece of another diagonal as mates[i] (a supplementary record, flag 2048).  Ungapped, on the index that was built last; the candidates,
+ * their scores and segments and the primary P are ssv_realign_query's.  Every interval is in the READ's orientation: a segment [b, e) is [b, e) on the
+ * forward strand and [n - e, n - b) on the reverse strand; shared(X, Y) = the length of the two intervals' intersection.
+ * Mate M: a scored candidate with another (strand, contig, diagonal) than P, score >= 30 after its end extension, ordered against P (P begins before it
+ * begins and ends before it ends, or the other way round; neither contains the other, equal begins or equal ends do not count) and with at least 20 bases
+ * of its own on both sides: len(P) - shared >= 20 and len(M) - shared >= 20.  The pieces may overlap (getsv reads that as microhomology) or leave a gap; the
+ * locus window of `second` plays no part (a 20-base deletion gives a mate).  Of several: the largest score, then the forward strand, the smaller diagonal,
+ * the smaller contig id.  With a mate, `second` of X in {P, M} is the largest score among the scored candidates that are not X's locus (window 32), are not
+ * the other piece and share >= 20 bases of the read with X (0: none), and mapq follows from it: hits[i].second / mapq may then differ from the plain
+ * call's, no other field does.  mates[i]: tid, pos, q_beg, q_end, score, n_mismatch, reverse of its own diagonal by the primary's rule, second and mapq as
+ * above, pad[0] = the primary's, pad[1] = 0.  Without a mate (also: unaligned, too short, too long) mates[i] is the unaligned hit with the primary's pad[0]
+ * and hits[i] is bit for bit ssv_realign_query's.  Limits: two pieces only; the mate needs a 20-mer seed of its own (23 matching bases in a row); pieces
+ * are not gap-refined; on the hash index the candidates of a query with more than 192 seeds and a tie between two contigs are the lanes' choice as before.
+ * Arguments and errors as ssv_realign_query; mates[n] (host) is required (NULL: SSV_E_ARG).  n == 0: SSV_OK. */
+int ssv_realign_query_split(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_hit *mates);
 int ssv_realign_free(ssv_ctx *ctx);
 
 /* ---- getsv -F: junctions from read-through split alignments: replaces FindJunction (process_bwasw.cpp:5-227, seeksv.cpp:221-225) -----------

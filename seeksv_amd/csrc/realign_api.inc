@@ -1,8 +1,9 @@
-// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h, realign_gap_kernels.h and realign_alts_kernels.h)
+// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h, realign_gap_kernels.h, realign_alts_kernels.h and realign_split_kernels.h)
 
 struct ssv_realign_state {
 	DBuf ref, ctg, table, seqs, offs, hits, gaps, dropped;
 	DBuf alts, alt_n, alt_off, alt_sums, alt_dense; // ssv_realign_query_alts: strided hits and counts, their scan, the dense list
+	DBuf mates; // ssv_realign_query_split: one hit per query
 	DBuf skeys, svals, sdir; // the sorted index (ssv_realign_index_sorted); a context holds one kind of index at a time
 	bool sorted = false;
 	int32_t dir_bits = 0, max_occ = 0;
@@ -118,33 +119,39 @@ int ssv_realign_index_sorted(ssv_ctx *c, const uint64_t *ref2bit, int32_t mem, i
 }
 
 // One instantiation of the query kernel over the n sequences in R.seqs / R.offs -> R.hits: the arguments every one takes, inside the sorted index's
-// and the alternates' layers where the instantiation has them (-> R.alts, max_alt per query, and R.alt_n)
-extern "C++" template <bool SORTED, int FLOOR, bool ALTS> // (this file is included inside extern "C")
+// and the alternates' (-> R.alts, max_alt per query, and R.alt_n) or the split reads' (-> R.mates) layers where the instantiation has them
+extern "C++" template <bool SORTED, int FLOOR, bool ALTS, bool SPLIT = false> // (this file is included inside extern "C")
 static void realign_launch_as(ssv_ctx *c, ssv_realign_state &R, int64_t n, int32_t max_alt)
 {
 	using Query = std::conditional_t<SORTED, RasQueryArgs, RaQueryArgs>;
-	using Args = std::conditional_t<ALTS, RaAltArgs<Query>, Query>;
+	using Args = std::conditional_t<ALTS, RaAltArgs<Query>, std::conditional_t<SPLIT, RaSplitArgs<Query>, Query>>;
 	Args a;
 	static_cast<RaQueryArgs &>(a) = RaQueryArgs{R.index(), P<char>(R.seqs), P<uint64_t>(R.offs), n, P<RaHit>(R.hits)};
 	if constexpr (SORTED) a.sx = RasIndex{P<uint64_t>(R.skeys), P<uint32_t>(R.svals), P<uint32_t>(R.sdir), R.dir_bits, R.max_occ};
 	if constexpr (ALTS) { a.alts = P<RaHit>(R.alts); a.alt_n = P<int32_t>(R.alt_n); a.max_alt = max_alt; }
-	k_ra_query_t<SORTED, Args, FLOOR, ALTS><<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
+	if constexpr (SPLIT) a.mates = P<RaHit>(R.mates);
+	k_ra_query_t<SORTED, Args, FLOOR, ALTS, SPLIT><<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(a);
 }
 
-// the query kernel of the index that stands - with the candidate floor at RA_K when `floor`, going on to the alternates when max_alt > 0
-static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor, int32_t max_alt = 0)
+// the query kernel of the index that stands - with the candidate floor at RA_K when `floor`, going on to the alternates when max_alt > 0 or to the mate
+// pieces when `split` (at the default floor and without alternates only: the callers see to that)
+static void realign_launch_query(ssv_ctx *c, ssv_realign_state &R, int64_t n, bool floor, int32_t max_alt = 0, bool split = false)
 {
-	static constexpr decltype(&realign_launch_as<false, RA_MIN_SCORE, false>) launch[2][2][2] = { // [sorted][floor][alts]: k_ra_query, k_ra_query_alts, k_ra_query_floor, ... k_ras_query_floor_alts
-		{{realign_launch_as<false, RA_MIN_SCORE, false>, realign_launch_as<false, RA_MIN_SCORE, true>}, {realign_launch_as<false, RA_K, false>, realign_launch_as<false, RA_K, true>}},
-		{{realign_launch_as<true, RA_MIN_SCORE, false>, realign_launch_as<true, RA_MIN_SCORE, true>}, {realign_launch_as<true, RA_K, false>, realign_launch_as<true, RA_K, true>}}};
+	static constexpr decltype(&realign_launch_as<false, RA_MIN_SCORE, false>) launch[2][2][3] = { // [sorted][floor][alts, 2 = split]: k_ra_query, k_ra_query_alts, k_ra_query_split, k_ra_query_floor, ... k_ras_query_floor_alts
+		{{realign_launch_as<false, RA_MIN_SCORE, false>, realign_launch_as<false, RA_MIN_SCORE, true>, realign_launch_as<false, RA_MIN_SCORE, false, true>},
+		 {realign_launch_as<false, RA_K, false>, realign_launch_as<false, RA_K, true>, nullptr}},
+		{{realign_launch_as<true, RA_MIN_SCORE, false>, realign_launch_as<true, RA_MIN_SCORE, true>, realign_launch_as<true, RA_MIN_SCORE, false, true>},
+		 {realign_launch_as<true, RA_K, false>, realign_launch_as<true, RA_K, true>, nullptr}}};
 	ProfScope ps(c, P_REALIGN_QUERY, n);
-	launch[R.sorted][floor][max_alt > 0](c, R, n, max_alt);
+	launch[R.sorted][floor][split ? 2 : max_alt > 0](c, R, n, max_alt);
 }
 
-// ssv_realign_query (gaps == nullptr), ssv_realign_query_gapped and - max_alt > 0 - ssv_realign_query_alts; `who` names the caller in the error text
+// ssv_realign_query (gaps == nullptr), ssv_realign_query_gapped, - max_alt > 0 - ssv_realign_query_alts and - mates != nullptr, ungapped, no alternates -
+// ssv_realign_query_split; `who` names the caller in the error text
 static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_gap *gaps, bool gapped, const char *who,
-                         int32_t max_alt = 0, int64_t *alt_off = nullptr, ssv_realign_hit *alts = nullptr)
+                         int32_t max_alt = 0, int64_t *alt_off = nullptr, ssv_realign_hit *alts = nullptr, ssv_realign_hit *mates = nullptr)
 {
+	if (mates && (gapped || max_alt > 0)) return SSV_E_ARG;
 	if (!c || n < 0 || (n > 0 && (!seqs || !seq_off || !hits || (gapped && !gaps)))) return SSV_E_ARG;
 	if (!c->ra || !c->ra->ready) { c->err = std::string(who) + " before ssv_realign_index"; return SSV_E_STATE; }
 	if (n == 0) { if (alt_off) alt_off[0] = 0; return SSV_OK; }
@@ -159,9 +166,10 @@ static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, 
 		CHECK(ensure(c, R.alts, (size_t)n * (size_t)max_alt * sizeof(RaHit))); CHECK(ensure(c, R.alt_n, (size_t)n * 4)); CHECK(ensure(c, R.alt_off, (size_t)(n + 1) * 8));
 		CHECK(ensure(c, R.alt_sums, (size_t)scan_scratch_elems(n) * 8));
 	}
+	if (mates) CHECK(ensure(c, R.mates, (size_t)n * sizeof(RaHit)));
 	HIPCHECK(c, hipMemcpyAsync(R.seqs.p, seqs, bytes, hipMemcpyHostToDevice, c->st));
 	HIPCHECK(c, hipMemcpyAsync(R.offs.p, seq_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->st));
-	realign_launch_query(c, R, n, gapped, max_alt);
+	realign_launch_query(c, R, n, gapped, max_alt, mates != nullptr);
 	HIPCHECK(c, hipGetLastError());
 	if (gapped) {
 		RaGapArgs g;
@@ -181,6 +189,7 @@ static int realign_query(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, 
 		HIPCHECK(c, hipGetLastError());
 		HIPCHECK(c, hipMemcpyAsync(alt_off, R.alt_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->st));
 	}
+	if (mates) HIPCHECK(c, hipMemcpyAsync(mates, R.mates.p, (size_t)n * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));
 	HIPCHECK(c, hipMemcpyAsync(hits, R.hits.p, (size_t)n * sizeof(RaHit), hipMemcpyDeviceToHost, c->st));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
 	if (max_alt > 0 && alt_off[n] > 0) {
@@ -213,6 +222,12 @@ int ssv_realign_query_alts(ssv_ctx *c, const char *seqs, const uint64_t *seq_off
 {
 	if (max_alt < 1 || max_alt > RA_MAX_ALT || !alt_off || !alts || (gapped && !gaps)) return SSV_E_ARG;
 	return realign_query(c, seqs, seq_off, n, hits, gapped ? gaps : nullptr, gapped != 0, "ssv_realign_query_alts", max_alt, alt_off, alts);
+}
+
+int ssv_realign_query_split(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_hit *mates)
+{
+	if (!mates) return SSV_E_ARG;
+	return realign_query(c, seqs, seq_off, n, hits, nullptr, false, "ssv_realign_query_split", 0, nullptr, nullptr, mates);
 }
 
 int ssv_realign_free(ssv_ctx *c)

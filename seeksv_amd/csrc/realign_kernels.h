@@ -6,7 +6,7 @@
 // getsv.h:445-527).  This is a stand-in for that step on hosts without bwa, for references that behave like random sequence
 // (the synthetic genomes of bench / tests): a k-mer index of the reference in HBM, seed look-ups for every k-mer of a query on
 // both strands, ungapped extension with bwa mem's default scores (match 1, mismatch 4, end clipping 5, report >= 30).
-// It does not reproduce bwa's alignments bit for bit (one gap per alignment at the most, and only on request: realign_gap_kernels.h; other loci as secondary hits only on request: realign_alts_kernels.h; no chaining, no supplementary records; at most
+// It does not reproduce bwa's alignments bit for bit (one gap per alignment at the most, and only on request: realign_gap_kernels.h; other loci as secondary hits only on request: realign_alts_kernels.h; a whole read's second piece as a supplementary hit only on request: realign_split_kernels.h; no chaining beyond these two pieces; at most
 // RA_MAX_CAND seed hits per query are followed, probe runs longer than RA_MAX_PROBE are cut).  References with repeats take the second, sorted
 // index of realign_sorted_kernels.h: the same query kernel (k_ra_query_t below) with another seed stage.
 //
@@ -163,13 +163,16 @@ __device__ __forceinline__ RaHit ra_unaligned(uint8_t flags) { return RaHit{-1, 
 // FLOOR test is the one the kernel had before the parameter.
 // ALTS: the query's other loci behind the winner (realign_alts_kernels.h: ra_alts, found like ras_seeds; Args is then RaAltArgs<...>, whose alt_n[q] every
 // query writes).  Off - the default - nothing of it is compiled: the four instantiations from before the parameter keep their code and resources.
-template <bool SORTED, typename Args, int FLOOR = RA_MIN_SCORE, bool ALTS = false>
+// SPLIT: a whole read's second piece behind the winner (realign_split_kernels.h: ra_split; Args is then RaSplitArgs<...>, whose mates[q] every query writes).
+// Every scored candidate's segment then stays in LDS beside its score (s_seg); off, neither the array nor its stores exist.
+template <bool SORTED, typename Args, int FLOOR = RA_MIN_SCORE, bool ALTS = false, bool SPLIT = false>
 __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 {
 	__shared__ uint8_t s_code[WAVES_PER_BLOCK][2][RA_MAX_Q];
 	__shared__ int64_t s_diag[WAVES_PER_BLOCK][RA_MAX_CAND];
 	__shared__ uint16_t s_ss[WAVES_PER_BLOCK][RA_MAX_CAND]; // strand << 15 | score of the candidate (<= RA_MAX_Q; 0 until it is scored: a duplicate, or not reported)
 	__shared__ int32_t s_tid[WAVES_PER_BLOCK][RA_MAX_CAND]; // contig of the seed (a query can hang over a contig's end: same diagonal, two contigs); n_targets is an int32
+	__shared__ uint16_t s_seg[SPLIT ? WAVES_PER_BLOCK : 1][2][RA_MAX_CAND]; // SPLIT: q_beg, q_end of a scored candidate (referenced by no other instantiation, which then has no such array)
 	__shared__ int s_n[WAVES_PER_BLOCK];
 	const int w = wave_id(), lane = lane_id();
 	const int64_t q = (int64_t)blockIdx.x * WAVES_PER_BLOCK + w;
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 	const int n = (int)(a.seq_off[q + 1] - o0);
 	RaHit out = ra_unaligned(0);
 	if (n < RA_K || n > RA_MAX_Q) {
-		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; }
+		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; if constexpr (SPLIT) a.mates[q] = out; }
 		return;
 	}
 	ra_codes(a.seqs + o0, n, lane, RA_FWD | RA_REV, s_code[w][0], s_code[w][1]);
@@ -253,6 +256,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 			}
 		}
 		s_ss[w][c] = (uint16_t)((st << 15) | bs);
+		if constexpr (SPLIT) { s_seg[w][0][c] = (uint16_t)bb; s_seg[w][1][c] = (uint16_t)be; }
 		int mm = 0;
 		for (int i = bb; i < be; ++i) mm += (code[i] < 4 && (uint32_t)code[i] == ra_base_at(ix.ref, d + i)) ? 0 : 1;
 		const bool better = bs > best_score || (bs == best_score && best_tid >= 0 && (st < best_st || (st == best_st && (d < best_diag || (SORTED && d == best_diag && t < best_tid)))));
@@ -272,7 +276,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		if (take) { win_score = os; win_lane = ol; win_diag = od; win_st = ost; win_t = ot; }
 	}
 	if (win_score < FLOOR) {
-		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; }
+		if (lane == 0) { a.hits[q] = out; if constexpr (ALTS) a.alt_n[q] = 0; if constexpr (SPLIT) a.mates[q] = out; }
 		return;
 	}
 	const int win_tid = __shfl(best_tid, win_lane, 64);
@@ -294,6 +298,7 @@ __global__ __launch_bounds__(BLOCK) void k_ra_query_t(Args a)
 		a.hits[q] = out;
 	}
 	if constexpr (ALTS) ra_alts(a, w, lane, n, m, q, s_code, s_diag, s_ss, s_tid, win_st, win_tid, win_diag, win_score, win_lane, (uint32_t)out.pad[0]);
+	if constexpr (SPLIT) ra_split(a, w, lane, n, m, q, s_diag, s_ss, s_tid, s_seg, win_st, win_tid, win_diag, win_score, __shfl(best_beg, win_lane, 64), __shfl(best_end, win_lane, 64), win_lane, (uint32_t)out.pad[0]);
 }
 
 constexpr auto k_ra_query = k_ra_query_t<false, RaQueryArgs>;

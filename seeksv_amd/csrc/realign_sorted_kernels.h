@@ -22,7 +22,7 @@
 //               run's first entry up again and copies its positions, which already ascend.  Admission stops at RA_MAX_CAND slots; seeds left out: flag
 //               SSV_RA_F_OVERFLOW.  No LDS atomic orders anything: every field of every hit is a function of the input.
 //   ties        candidates equal in score, strand and diagonal go to the smaller contig id.
-// Still not bwa: one gap per alignment at the most (realign_gap_kernels.h), no chaining, no supplementary records; one record per query, or up to 1 + 16 when
+// Still not bwa: one gap per alignment at the most (realign_gap_kernels.h), no chaining beyond a whole read's two pieces (realign_split_kernels.h); one record per query, or up to 1 + 16 when
 // the other loci are asked for (realign_alts_kernels.h).
 #pragma once
 

@@ -33,6 +33,7 @@
 #include "realign_sorted_kernels.h"
 #include "realign_gap_kernels.h"
 #include "realign_alts_kernels.h"
+#include "realign_split_kernels.h"
 #include "clip_kernels.h"
 #include "table3_kernels.h"
 #include "tile_sort.h"

@@ -446,6 +446,15 @@ class Context:
                                                      gaps.ctypes.data if gapped else None, alt_off.ctypes.data, alts.ctypes.data), "ssv_realign_query_alts")
         return hits, gaps, alt_off, alts[:int(alt_off[n])].copy()
 
+    def realign_split(self, seqs):
+        """realign() for whole reads that may cross a breakpoint (ssv_realign_query_split) -> (hits, mates): mates[i] is read i's second piece, or
+        unaligned (tid -1, the primary's flags in pad[0]); with a mate, hits[i]'s second / mapq count only competitors for the primary's own part"""
+        n = len(seqs)
+        blob, off, hits = self._realign_io(seqs)
+        mates = np.zeros(max(n, 1), dtype=np.dtype(_abi.REALIGN_HIT))
+        self._check(self._lib.ssv_realign_query_split(self._h, C.c_char_p(blob), off.ctypes.data, n, hits.ctypes.data, mates.ctypes.data), "ssv_realign_query_split")
+        return hits, mates[:n]
+
     # ---- measurement ----
     def prof_enable(self, mode=1):
         self._check(self._lib.ssv_prof_enable(self._h, mode), "ssv_prof_enable")

@@ -1861,6 +1861,8 @@ static int cmd_somatic(int argc, char **argv)
 // stand-in for hosts without bwa (ssv_realign_*, include/seeksv_hip.h): one record per clipped sequence (with -S: followed by up to INT secondary records of its other loci), in FASTQ order, the
 // read name is the sequence.  No gapped alignment unless -g asks for it (one insertion or deletion of up to 16 bases per record).  The default (hash) index is meant for references that behave like random sequence (synthetic
 // genomes); -c selects the sorted index, which keeps every copy of a repeat, skips seeds with more occurrences than the cap and follows the rarest first.
+// -P takes WHOLE reads (e.g. getclip's prefix.unmapped_[12].fq.gz) in the place of `bwa bwasw`: the read name is the FASTQ name, and a read that is two
+// stretches of two loci gets a supplementary record (flag 2048) for its second piece behind its own - what `seeksv getsv -F` reads.
 // ---------------------------------------------------------------------------------------------------------------------
 [[noreturn]] static void usage_realign()
 {
@@ -1868,6 +1870,8 @@ static int cmd_somatic(int argc, char **argv)
 	     << "         -c <int>              skip seeds with more than INT occurrences; selects the sorted index (1..65535; bwa mem's -c, there 500) [hash index, no cap]\n"
 	     << "         -g                    allow one insertion or deletion of 1..16 bases per alignment (M, I / D, M; gap open 6, extend 1) [ungapped]\n"
 	     << "         -S <int>              also write up to INT other loci of a sequence as secondary records (flag 256, MAPQ 0; 1..16; score >= 30 and >= 0.8 x the primary's) [none]\n"
+	     << "         -P                    the input holds whole reads (e.g. prefix.unmapped_[12].fq.gz): read name = FASTQ name, and a read's second piece of another\n"
+	     << "                               locus follows it as a supplementary record (flag 2048, own MAPQ, S M S, never H) - the input of getsv -F; not with -g or -S [off]\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -1880,14 +1884,16 @@ static int parse_max_occ(const char *arg)
 	return (end != arg && *end == 0 && v >= 1 && v <= 65535) ? (int)v : 0;
 }
 
-// realign's options, for `seeksv realign` itself and for the words of `seeksv run -a`; *gpu stays as it is without -G.  -> index of the first operand
-static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped, int *max_alt)
+// realign's options, for `seeksv realign` itself and for the words of `seeksv run -a` (split == nullptr: -P is not one of them); *gpu stays as it is
+// without -G.  -> index of the first operand
+static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped, int *max_alt, bool *split = nullptr)
 {
 	int c;
 	optind = 1;
-	while ((c = getopt(argc, argv, "G:c:gS:")) != -1) {
+	while ((c = getopt(argc, argv, "G:c:gS:P")) != -1) {
 		if (c == 'G') *gpu = atoi(optarg);
 		else if (c == 'g') *gapped = true;
+		else if (c == 'P') { if (!split) usage_realign(); *split = true; }
 		else if (c == 'S') { // 0 = no secondary records
 			char *end = nullptr;
 			const long v = strtol(optarg, &end, 10);
@@ -1897,6 +1903,7 @@ static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, 
 		else if (c == 'c') { if (!(*max_occ = parse_max_occ(optarg))) usage_realign(); }
 		else usage_realign();
 	}
+	if (split && *split && (*gapped || *max_alt > 0)) usage_realign();
 	return optind;
 }
 
@@ -2075,11 +2082,14 @@ struct AlignedRecords {
 	vector<const char *> qn;
 	int64_t n_aligned = 0, n_masked = 0, n_over = 0, n_gapped = 0; // (n_masked, n_over: SSV_RA_F_* of the sorted index; n_gapped: records with an I / D, -g)
 	int64_t n_secondary = 0, n_with_alt = 0, n_cut = 0; // -S: secondary records, sequences that have any, sequences with SSV_RA_F_ALT_CUT
+	int64_t n_split = 0; // -P: supplementary records = reads with a mate piece
 	int64_t size() const { return (int64_t)tid.size(); }
 };
 // the sequences through the aligner (ssv_realign_query, or ssv_realign_query_gapped when `gapped`) and their records appended to `out`; max_alt > 0
-// (ssv_realign_query_alts): behind a sequence's record its alternates in the rule's order, as secondary records
-static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out, bool gapped, int max_alt)
+// (ssv_realign_query_alts): behind a sequence's record its alternates in the rule's order, as secondary records.  names != nullptr (-P: ungapped, no
+// alternates; ssv_realign_query_split): the records carry these read names, and a read's mate piece follows it as a supplementary record - laid out as a
+// list of at most one "alternate" per read
+static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Line> &quals, AlignedRecords &out, bool gapped, int max_alt, const vector<Line> *names = nullptr)
 {
 	const int64_t n = (int64_t)seqs.size();
 	if (!n) return;
@@ -2105,11 +2115,20 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 	vector<ssv_realign_hit> hits((size_t)n);
 	vector<ssv_realign_gap> gaps((size_t)n, ssv_realign_gap{0, 0}); // (all zero without -g)
 	vector<int64_t> alt_off((size_t)n + 1, 0); // (all zero without -S: sequence i is row i)
-	vector<ssv_realign_hit> alts(max_alt > 0 ? (size_t)n * (size_t)max_alt : 0);
-	const int rc = max_alt > 0 ? ssv_realign_query_alts(ctx, blob.data(), soff.data(), n, max_alt, gapped ? 1 : 0, hits.data(), gaps.data(), alt_off.data(), alts.data())
+	vector<ssv_realign_hit> alts(max_alt > 0 ? (size_t)n * (size_t)max_alt : names ? (size_t)n : 0);
+	const int rc = names       ? ssv_realign_query_split(ctx, blob.data(), soff.data(), n, hits.data(), alts.data())
+	               : max_alt > 0 ? ssv_realign_query_alts(ctx, blob.data(), soff.data(), n, max_alt, gapped ? 1 : 0, hits.data(), gaps.data(), alt_off.data(), alts.data())
 	               : gapped    ? ssv_realign_query_gapped(ctx, blob.data(), soff.data(), n, hits.data(), gaps.data())
 	                           : ssv_realign_query(ctx, blob.data(), soff.data(), n, hits.data());
 	if (rc != SSV_OK) die(string("[seeksv] realign query: ") + ssv_last_error(ctx));
+	if (names) { // mates[n] -> the mate pieces that exist, back to back
+		int64_t k = 0;
+		for (int64_t i = 0; i < n; ++i) {
+			if (alts[(size_t)i].tid >= 0) alts[(size_t)k++] = alts[(size_t)i];
+			alt_off[(size_t)i + 1] = k;
+		}
+		out.n_split += k;
+	}
 	const size_t at = (size_t)out.size();
 	const size_t rows = (size_t)(n + alt_off[(size_t)n]); // sequence i: rows i + alt_off[i] (its own record) .. i + 1 + alt_off[i + 1]
 	for (auto *v : {&out.tid, &out.pos, &out.lq}) v->resize(at + rows);
@@ -2141,7 +2160,7 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 			out.n_gapped += gap ? 1 : 0;
 			ncig[row] = (uint16_t)(al ? 1 + (gap ? 2 : 0) + (h.q_beg > 0 ? 1 : 0) + (h.q_end < L ? 1 : 0) : 0);
 			co += ncig[row]; so += ((uint64_t)L + 1) / 2 + (uint64_t)L;
-			out.n_secondary += n_alt; out.n_with_alt += n_alt ? 1 : 0; out.n_cut += (h.pad[0] & SSV_RA_F_ALT_CUT) ? 1 : 0;
+			if (!names) { out.n_secondary += n_alt; out.n_with_alt += n_alt ? 1 : 0; } out.n_cut += (h.pad[0] & SSV_RA_F_ALT_CUT) ? 1 : 0;
 			for (int64_t r = 1; r <= n_alt; ++r) { // the alternates: S M S
 				const ssv_realign_hit &x = alts[(size_t)(alt_off[(size_t)i] + r - 1)];
 				cig_off[row + r] = co; seq_off[row + r] = so;
@@ -2163,9 +2182,9 @@ static void align_lines(ssv_ctx *ctx, const vector<Line> &seqs, const vector<Lin
 				const char *s = seqs[(size_t)qi].p, *q = quals[(size_t)qi].p;
 				const int L = seqs[(size_t)qi].n;
 				const bool al = h.tid >= 0, rev = al && h.reverse, has_q = quals[(size_t)qi].n == L;
-				qn[i] = s;
+				qn[i] = names ? (*names)[(size_t)qi].p : s;
 				tid[i] = al ? h.tid : -1; pos[i] = al ? h.pos : -1; lq[i] = L;
-				flag[i] = (uint16_t)((al ? (rev ? 16 : 0) : 4) | (r ? 256 : 0)); mapq[i] = al ? h.mapq : 0;
+				flag[i] = (uint16_t)((al ? (rev ? 16 : 0) : 4) | (r ? (names ? 2048 : 256) : 0)); mapq[i] = al ? h.mapq : 0;
 				if (al) {
 					uint32_t *c = cig + cig_off[i];
 					if (h.q_beg > 0) *c++ = ((uint32_t)h.q_beg << 4) | 4u;
@@ -2217,13 +2236,14 @@ static void build_realign_index(ssv_ctx *ctx, const Reference &R, int max_occ, i
 	if (rc != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
 }
 
-static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped, int max_alt)
+static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped, int max_alt, bool split = false)
 {
-	string t = "[seeksv realign] " + to_string(A.size() - A.n_secondary) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
+	string t = "[seeksv realign] " + to_string(A.size() - A.n_secondary - A.n_split) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
 	if (gapped) t += ", " + to_string(A.n_gapped) + " with a gap";
 	if (!max_occ) t += dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string();
 	else t += (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
 	if (max_alt) t += ", " + to_string(A.n_secondary) + " secondary records for " + to_string(A.n_with_alt) + " sequences (" + to_string(A.n_cut) + " cut at -S)";
+	if (split) t += ", " + to_string(A.n_split) + " split reads (mate pieces written)";
 	return t;
 }
 
@@ -2237,8 +2257,8 @@ static void resident_alignments(seeksv::AlnRecords &R)
 static int cmd_realign(int argc, char **argv)
 {
 	int gpu = 0, max_occ = 0, max_alt = 0;
-	bool gapped = false;
-	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped, &max_alt) != 3) usage_realign();
+	bool gapped = false, split = false;
+	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped, &max_alt, &split) != 3) usage_realign();
 	const string fasta = argv[optind], fq = argv[optind + 1], out_bam = argv[optind + 2];
 	PhaseTimer pt;
 	Reference R;
@@ -2246,7 +2266,7 @@ static int cmd_realign(int argc, char **argv)
 	pt.lap("read reference");
 	// ---- clipped sequences: the FASTQ file (its gzip members inflated side by side), cut into lines in place (the newline behind a line becomes its
 	//      terminator: the sequences are the read names of the BAM records below) ----
-	vector<Line> seqs, quals;
+	vector<Line> seqs, quals, names; // (names: -P only)
 	string text;
 	{ const string err = seeksv::slurp_gz(fq, text); if (!err.empty()) die("Cannot open clipped reads file " + fq); }
 	{
@@ -2268,6 +2288,12 @@ static int cmd_realign(int argc, char **argv)
 			if (!line(l2) || !line(l3) || !line(l4)) die("Truncated FASTQ record in " + fq);
 			if (l1.n == 0 || l1.p[0] != '@' || l3.n == 0 || l3.p[0] != '+') die("Malformed FASTQ record in " + fq);
 			seqs.push_back(l2); quals.push_back(l4);
+			if (split) { // the read's name: behind '@' up to the first white space ("/1" and "/2" stay)
+				int k = 1;
+				while (k < l1.n && l1.p[k] != ' ' && l1.p[k] != '\t') ++k;
+				l1.p[k] = 0;
+				names.push_back(Line{l1.p + 1, k - 1});
+			}
 		}
 	}
 	pt.lap("read fastq");
@@ -2276,7 +2302,7 @@ static int cmd_realign(int argc, char **argv)
 	build_realign_index(ctx, R, max_occ, &dropped);
 	pt.lap("index");
 	AlignedRecords A;
-	align_lines(ctx, seqs, quals, A, gapped, max_alt);
+	align_lines(ctx, seqs, quals, A, gapped, max_alt, split ? &names : nullptr);
 	pt.lap("align");
 	A.seqqual.resize(A.seqqual.size() + 16, 0);
 	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
@@ -2284,7 +2310,7 @@ static int cmd_realign(int argc, char **argv)
 	setenv("SSV_BGZF_LEVEL", "-1", 0);
 	write_clip_bam(out_bam, R, A);
 	pt.lap("write bam");
-	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt) << endl;
+	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt, split) << endl;
 	ssv_realign_free(ctx);
 	release_ctx(ctx);
 	return 0;

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """The GPU re-aligner (ssv_realign_*) at the size of the bench workload: index of the whole synthetic genome (generated in
 HBM), then queries cut from it - half of them real placements (both strands, 0.5 % substitutions), half random sequence like the bulk of
-a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [--alts K [--family N]] [genome_frac] [n_queries] [query_len]
+a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [--alts K [--family N]] [--split SHARE] [genome_frac] [n_queries] [query_len]
 --gapped: half of the random queries give way to a third class, real placements that carry one insertion or deletion of 1-3 bases at least 12 bases
 from either end; every round then runs the set through ssv_realign_query and through ssv_realign_query_gapped (`seeksv realign -g`) and reports both.
 --alts K: every round also runs the set through ssv_realign_query_alts with max_alt K (`seeksv realign -S K`) and reports the query kernel, the scan and
 k_ra_alt_compact ("realign_alts"), the number of alternates, and whether the primaries are the plain call's.  --family N (with --alts) first plants N elements of
 64 bases in 5 copies each into the reference (word-aligned 2-bit copies on the device, before any index is built) and gives N of the random queries' places to a
 fourth class: 60 bases of such an element; reported: how many come back with all five copies (primary + 4 alternates).
+--split SHARE: that share of the real placements become reads of two loci - their second half comes from another place of the reference, same substitutions,
+either strand -, and every round also runs the set through ssv_realign_query_split (`seeksv realign -P`): reported are the split query kernel's time beside the
+plain kernel's on the same set, how many planted splits come back at both planted places, and whether the primaries without a mate are the plain call's.
 --index both builds and queries the two kinds of index in one process, alternating (hash, sorted, hash, sorted, ...), R times each: one JSON line
 with a list of rounds per kind.  Index bytes are computed from the sizes the library allocates, not measured."""
 import argparse
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--gapped", action="store_true")
     ap.add_argument("--alts", type=int, default=0)
     ap.add_argument("--family", type=int, default=0)
+    ap.add_argument("--split", type=float, default=0.0)
     ap.add_argument("genome_frac", nargs="?", type=float, default=1.0)
     ap.add_argument("n_queries", nargs="?", type=int, default=2_000_000)
     ap.add_argument("query_len", nargs="?", type=int, default=60)
@@ -52,6 +56,8 @@ def main():
     frac, nq, qlen = args.genome_frac, args.n_queries, args.query_len
     if args.family and (not args.alts or qlen > 60):
         ap.error("--family needs --alts and queries of at most 60 bases")
+    if args.split and (not 0 < args.split <= 1 or qlen < 60):
+        ap.error("--split needs a share in (0, 1] and queries of at least 60 bases (two pieces of 30)")
     import torch
     w = synth.Workload(genome_frac=frac, depth=1, n_sv=0)
     t = time.perf_counter()
@@ -85,6 +91,14 @@ def main():
     codes = ((wh[idx >> 5] >> ((idx & 31) * 2).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)
     sub = rng.random_sample(codes.shape) < 0.005
     codes = np.where(sub, (codes + 1 + rng.randint(0, 3, codes.shape)) & 3, codes).astype(np.uint8)
+    n_split = int(n_real * args.split)
+    if n_split:   # the first n_split real placements: bases [qlen / 2, qlen) from another place (a generator of its own: the other classes stay what they are without --split)
+        sp = np.random.RandomState(15)
+        tid2 = sp.randint(0, len(off) - 1, n_split)
+        start2 = (off[tid2] + (sp.random_sample(n_split) * (np.diff(off)[tid2] - qlen)).astype(np.int64)).astype(np.int64)
+        idx2 = start2[:, None] + np.arange(qlen // 2, qlen)[None, :]
+        codes2 = ((wh[idx2 >> 5] >> ((idx2 & 31) * 2).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)
+        codes[:n_split, qlen // 2:] = np.where(sub[:n_split, qlen // 2:], codes[:n_split, qlen // 2:], codes2)
     rev = rng.random_sample(n_real) < 0.5
     codes[rev] = (3 - codes[rev])[:, ::-1]
     junk = rng.randint(0, 4, (nq - n_real, qlen)).astype(np.uint8)
@@ -122,11 +136,16 @@ def main():
     lut = np.frombuffer(b"ACGT", np.uint8)
     text = lut[allc].tobytes().decode()
     seqs = [text[i * qlen:(i + 1) * qlen] for i in range(nq)]
-    is_real = order < n_real
+    is_split = order < n_split
+    is_real = (order < n_real) & ~is_split
     exp_tid = np.full(nq, -1)
     exp_tid[is_real] = tid[order[is_real]]
     exp_pos = np.full(nq, -1, np.int64)
     exp_pos[is_real] = (start - off[tid])[order[is_real]]
+    exp_tid[is_split], exp_pos[is_split] = tid[order[is_split]], (start - off[tid])[order[is_split]]   # the first half's place; the second half's:
+    exp_tid2, exp_pos2 = np.full(nq, -1), np.full(nq, -1, np.int64)
+    if n_split:
+        exp_tid2[is_split], exp_pos2[is_split] = tid2[order[is_split]], (start2 - off[tid2])[order[is_split]]
     is_gap = (order >= n_real) & (order < n_real + n_gap)
     exp_len = np.zeros(nq, np.int64)
     if n_gap:
@@ -135,7 +154,7 @@ def main():
         exp_len[is_gap] = np.where(gins, -glen, glen)[order[is_gap] - n_real]
     is_fam = (order >= n_real + n_gap) & (order < n_real + n_gap + n_fam)
     fam_of = order[is_fam] - n_real - n_gap
-    is_junk = ~is_real & ~is_gap & ~is_fam
+    is_junk = ~is_real & ~is_split & ~is_gap & ~is_fam
     samples = (G + 3) // 4
 
     def one(kind):
@@ -187,6 +206,23 @@ def main():
                 out["alts"].update(family_queries=int(len(qi)), family_with_four_alternates=int(full.sum()),
                                    family_all_five_copies_back=int((np.sort(got, axis=1) == want).all(axis=1).sum()),
                                    family_primary_mapq0=int((h2["mapq"][qi] == 0).sum()))
+        if n_split:   # the same queries once more, with their second pieces
+            ctx.prof_reset()
+            t = time.perf_counter()
+            h3, mates = ctx.realign_split(seqs)
+            t_query = time.perf_counter() - t
+            q_ms = ctx.prof_all()["realign_query"]["total_ms"]
+            has = mates["tid"] >= 0
+
+            def at(h, etid, epos):
+                return (h["tid"] == etid) & (h["pos"] - h["q_beg"] == epos)
+            both = has & ((at(h3, exp_tid, exp_pos) & at(mates, exp_tid2, exp_pos2)) | (at(h3, exp_tid2, exp_pos2) & at(mates, exp_tid, exp_pos)))
+            out["split"] = dict(split_reads=int(is_split.sum()), query_wall_s=round(t_query, 3), query_kernel_ms=round(q_ms, 2), plain_query_kernel_ms=out["query_kernel_ms"],
+                                queries_per_s_kernel=round(nq / (q_ms * 1e-3)), mates=int(has.sum()), split_reads_with_mate=int(has[is_split].sum()),
+                                planted_splits_back_at_both_places=int(both[is_split].sum()), both_pieces_mapq_above_0=int((both & (h3["mapq"] > 0) & (mates["mapq"] > 0))[is_split].sum()),
+                                plain_call_split_reads_mapq0=int((plain["mapq"] == 0)[is_split & (plain["tid"] >= 0)].sum()),
+                                real_with_mate=int(has[is_real].sum()), junk_with_mate=int(has[is_junk].sum()),
+                                primaries_without_mate_equal_plain=bool(h3[~has].tobytes() == plain[~has].tobytes()))
         if args.gapped:   # the same queries once more, with gaps
             at_locus = (hits["tid"] == exp_tid) & (hits["mapq"] > 0)
             out["ungapped_gap_class_at_its_contig"] = int(at_locus[is_gap].sum())
@@ -205,7 +241,7 @@ def main():
         return out
 
     kinds = ["hash", "sorted"] if args.index == "both" else [args.index]
-    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int(is_junk.sum()), "with_planted_gap": int(is_gap.sum()), "from_a_planted_family": int(is_fam.sum()),
+    out = {"genome_bases": G, "sampled_positions": samples, "reference_2bit_s": round(t_ref, 3), "queries": nq, "query_len": qlen, "real": int(is_real.sum()), "junk": int(is_junk.sum()), "with_planted_gap": int(is_gap.sum()), "from_a_planted_family": int(is_fam.sum()), "split_in_two_loci": int(is_split.sum()),
            "rounds": {k: [] for k in kinds}}
     for _ in range(args.rounds):
         for k in kinds:
