@@ -64,7 +64,13 @@ asan: $(LIBDIR)/libseeksv_hip.so
 		SSV_TEST_CXXFLAGS="$(ASAN_FLAGS)" SSV_LIBDIR=$(abspath $(ASAN_DIR)) SSV_ORACLE_SO=$(abspath $(ASAN_DIR))/liboracle.so SSV_CLI=$(abspath $(ASAN_DIR))/seeksv \
 		python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider
 
+# The host rebuild of the cluster table's narrow wire form (seeksv_amd/csrc/table_wire.h, no HIP in it) as a program of its own under ASan + UBSan,
+# against the encoder in the test program
+wire-check:
+	mkdir -p $(ASAN_DIR)
+	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/csrc tests/native/table_wire_check.cpp -o $(ASAN_DIR)/table_wire_check && $(ASAN_DIR)/table_wire_check
+
 clean:
 	rm -rf $(LIBDIR) && $(MAKE) -C oracle clean
 
-.PHONY: all host hip synth cli oracle oracle-ref asan clean
+.PHONY: all host hip synth cli oracle oracle-ref asan wire-check clean

@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
+                             v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
                              v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
                              v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
                              v9 (additive, same version): ssv_samdec_begin / ssv_samdec_decode / ssv_samdec_names / ssv_samdec_last / ssv_samdec_prefetch (getsv -F on SAM text).
@@ -260,6 +261,8 @@ typedef struct {
 	                              on current sequencers. */
 	uint8_t qual_alphabet[64]; /* index -> quality character (v8: 64 places; the entries in use are non-zero and increasing) */
 	/* ---- format 3, the compact table: what the host can rebuild does not cross PCIe ----
+	 * (The arrays below are what a caller reads.  pos, c_len, c_support, c_ncig and c_cigar cross in a narrower form of the library's own, ~7 instead of
+	 * ~17 bytes a cluster, and stand rebuilt at these widths when ssv_clip_table_wait returns: ssv_clip_table_wire_bytes.)
 	 * Handed out by ssv_clip_table_wait: pos, c_cigar (cigar too when cigar_bytes is 4), str and the fields below; tid, side, support, left_len, right_len, qual_missing,
 	 * n_cigar, str_off and cigar_off are NULL until ssv_clip_table_expand() has rebuilt them on the host.
 	 *   c_len      [n_clusters][2] left_len, right_len, len_bytes (2 or 4) wide each
@@ -293,7 +296,7 @@ typedef struct {
 	uint64_t str_bytes;        /* bytes of str / operations of cigar (all formats) */
 	uint64_t cigar_ops;
 	int64_t support_sum;       /* format 3, after ssv_clip_table_expand: sum of the support column (= n_events: every clip event is in one cluster) */
-	const void *c_cigar;       /* format 3 (v7): the CIGAR operations as they crossed PCIe, cigar_bytes wide each - 2: length << 4 | code in 16 bits (every
+	const void *c_cigar;       /* format 3 (v7): the CIGAR operations, cigar_bytes wide each - 2: length << 4 | code in 16 bits (every
 	                              length of the table is below 4096; `cigar` is NULL then: read (const uint16_t *)c_cigar + cigar_off[k]); 4: = cigar */
 	int32_t cigar_bytes, pad4;
 } ssv_cluster_table;
@@ -306,6 +309,21 @@ int ssv_clip_table_format(ssv_ctx *ctx, int format);
  * and CIGAR offsets as running sums) into context-owned host memory, on n_threads host threads (0: as many as the machine has), and
  * set the pointers in *t.  Valid as long as the table. */
 int ssv_clip_table_expand(ssv_ctx *ctx, ssv_cluster_table *t, int32_t n_threads);
+/* What really crossed PCIe for a table handed out by ssv_clip_table_wait[_prev], in bytes per piece (v9, additive).  The widths in ssv_cluster_table
+ * describe the arrays that are handed out; a format-3 table's small columns cross narrower than that (below) and are rebuilt on a host thread of
+ * the context while the strings are still crossing.
+ *   narrow 1: per cluster one row of 6 bytes - pos as a u16 step from the cluster before (0xffff: pos stands in a list of (cluster, pos) escapes: a run's
+ *             first cluster, the first cluster of every 256 sorted slots, steps of 65535 and more), left_len, right_len, support as a byte each, n_cigar
+ *             with a 2-bit CIGAR kind (1: exactly left_len M right_len S; 2: exactly left_len S right_len M; 0: the operations cross in the CIGAR stream);
+ *          0: the columns as they are handed out (a length of 256 or more, a support of 255 or more, a CIGAR of 64 operations or more;
+ *             SSV_TABLE_WIRE=wide, SSV_TABLE_WIDE_COLUMNS, SSV_PACK_COLS=split; format 0)
+ *   flags (one byte a cluster), runs, base exceptions and the strings cross as they are handed out. */
+typedef struct {
+	int32_t narrow, pad;
+	uint64_t total;            /* the sum of the pieces below */
+	uint64_t rows, flags, cigar, runs, base_exc, pos_esc, str;
+} ssv_table_wire;
+int ssv_clip_table_wire_bytes(ssv_ctx *ctx, const ssv_cluster_table *t, ssv_table_wire *out);
 /* Bytes of one cluster's string block in format 3 (n_bases = left_len + right_len). */
 uint64_t ssv_table_block_bytes3(int64_t n_bases, int32_t base_bits, int32_t qual_bits);
 /* The same for a table whose qualities go in groups (ssv_cluster_table.qual_group; 1 = the function above). */

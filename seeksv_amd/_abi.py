@@ -121,6 +121,12 @@ class HipClusterTable(C.Structure):
                                         ("cigar_ops", C.c_uint64), ("support_sum", C.c_int64), ("c_cigar", C.c_void_p), ("cigar_bytes", C.c_int32), ("pad4", C.c_int32)]
 
 
+class TableWire(C.Structure):
+    """ssv_table_wire: the bytes a cluster table's copy really moved, per piece"""
+    _fields_ = [("narrow", C.c_int32), ("pad", C.c_int32), ("total", C.c_uint64), ("rows", C.c_uint64), ("flags", C.c_uint64), ("cigar", C.c_uint64),
+                ("runs", C.c_uint64), ("base_exc", C.c_uint64), ("pos_esc", C.c_uint64), ("str", C.c_uint64)]
+
+
 TABLE_RUN_DTYPE = np.dtype([("tid", "<i4"), ("side", "u1"), ("pad", "u1", (3,)), ("first", "<i8")])  # ssv_table_run
 
 
@@ -356,6 +362,7 @@ def hip_lib():
         lib.ssv_clip_cluster.argtypes = [V, C.POINTER(HipClusterTable)]
         lib.ssv_clip_table_format.argtypes = [V, C.c_int]
         lib.ssv_clip_table_expand.argtypes = [V, C.POINTER(HipClusterTable), C.c_int32]
+        lib.ssv_clip_table_wire_bytes.argtypes = [V, C.POINTER(HipClusterTable), C.POINTER(TableWire)]
         lib.ssv_table_block_bytes3.argtypes = [C.c_int64, C.c_int32, C.c_int32]
         lib.ssv_table_block_bytes3.restype = C.c_uint64
         lib.ssv_table_block_bytes3g.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]

@@ -1,8 +1,33 @@
 // clip_api.inc - C ABI of getclip: the clip scan, the clustering of its events and the cluster table (included by seeksv_hip.hip;
-// kernels in clip_kernels.h, table3_kernels.h, tile_sort.h, radix_sort.h)
+// kernels in clip_kernels.h, table3_kernels.h, tile_sort.h, radix_sort.h; the host rebuild of the table's wire rows in table_wire.h)
 
 // the dense cluster table: device columns + pinned host copy, double buffered so that the PCIe copy of one table can overlap
 // with whatever the caller runs next (ssv_clip_cluster_async / ssv_clip_table_wait)
+// plain host memory that only grows (the columns the helper thread rebuilds: nothing copies into them by address)
+struct PlainBuf {
+	void *p = nullptr; size_t cap = 0;
+	PlainBuf() = default;
+	PlainBuf(const PlainBuf &) = delete;
+	PlainBuf &operator=(const PlainBuf &) = delete;
+	~PlainBuf() { free(p); }
+	bool ensure(size_t bytes)
+	{
+		if (bytes <= cap) return true;
+		const size_t ncap = std::max(bytes, cap + cap / 2);
+		free(p); p = malloc(ncap); cap = p ? ncap : 0;
+		return p != nullptr;
+	}
+};
+
+// the context's helper thread: one table set after the other, in the order ssv_clip_cluster_async queued them
+struct TableHelper {
+	std::thread th;
+	std::mutex mu;
+	std::condition_variable cv_go, cv_done;
+	std::deque<int> jobs;
+	bool quit = false;
+};
+
 struct TableSet {
 	DBuf o_tid, o_pos, o_side, o_support, o_ll, o_lr, o_qmiss, o_ncig, o_stroff, o_cigoff, o_str, o_cig;
 	HBuf h_tid, h_pos, h_side, h_support, h_ll, h_lr, h_qmiss, h_stroff, h_cigoff, h_ncig, h_str, h_cig;
@@ -25,6 +50,20 @@ struct TableSet {
 	hipEvent_t packed_ev = nullptr;                 // the set's pack kernels are done (its copy waits for it): one event per set - a copy that is
 	                                                // still queued behind the table before must not see the next pass's record of a shared event
 	bool in_flight = false;
+	// format 3, the narrow wire form (table_wire.h; wire == 1): rows and position escapes cross instead of pos / len / support / ncig, and the CIGAR stream holds the kind-0
+	// clusters' operations only; the helper thread rebuilds the handed-out columns into r_* while the strings are still crossing.  v_*: what is handed out, either way
+	int wire = 0;
+	DBuf o_row, o_pesc;
+	HBuf h_row, h_pesc;
+	int64_t pesc_tiles = 0, pesc_extra = 0, n_pesc = 0;
+	uint64_t wire_ops = 0;                          // operations in the CIGAR stream that crossed (cig_ops: those of the handed-out c_cigar)
+	uint64_t wire_piece[7] = {0};                   // bytes that crossed: rows (or the wide columns), flags, CIGAR stream, runs, base exceptions, position escapes, strings
+	PlainBuf r_pos, r_len, r_sup, r_nc, r_cig;
+	const void *v_pos = nullptr, *v_len = nullptr, *v_sup = nullptr, *v_nc = nullptr, *v_cig = nullptr;
+	hipEvent_t small_ev = nullptr;                  // the small pieces have landed (the hipMemcpyAsync path; the link path has copied_sig)
+	bool job_pending = false;                       // the helper thread still works on this set (guarded by TableHelper::mu)
+	int job_rc = 0, job_expand_nt = -1;             // its result; >= 0: it also builds the expanded columns, on that many threads (0: as many as the machine has)
+	std::string job_err;
 	int64_t n_clusters = 0, n_events = 0;
 	int packed = 0, qual_bits = 8, qual_group = 1, qual_radix = 0, cig_bytes = 4; // qual_group > 1 (format 3): qual_bits per group of that many qualities, radix = the alphabet's size
 	uint8_t qual_alphabet[64] = {0};
@@ -45,7 +84,10 @@ struct ssv_clip_state {
 	DBuf keys2[2], vals2[2], evs, cum_l, cum_r, c_support, c_ll, c_lr, c_cig_ev, c_qmiss, c_mflag, c_mslot, c_mlist, c_bflag, c_boff, c_blist, c_dlist, bins4_tab, c_strings, slot_cnt, slot_bytes, tile_sums;
 	DBuf o_slowlist, o_desc;
 	TableSet tab[2];
-	HostPool pool;             // ssv_clip_table_expand's threads
+	HostPool pool;             // ssv_clip_table_expand's threads, and the helper's rebuild
+	std::mutex pool_mu;        // ... one user at a time: the caller's own expand may meet the helper at work on the other table set
+	TableHelper helper;
+	int expand_nt = -1;        // >= 0: a caller has expanded a table of this context with that n_threads - later tables get their expanded columns from the helper
 	int tab_cur = 0;           // set of the most recent ssv_clip_cluster[_async]
 	int table_mode = 0;        // ssv_clip_table_format: 0 ASCII, 3 compact
 	DBuf qual_lut, qual_seen, pair_lut; HBuf h_qual_lut, h_pair_lut;
@@ -229,6 +271,11 @@ static int64_t exc_cap_of(int64_t E)
 	return e ? (int64_t)atoll(e) : std::min<int64_t>(E / 2 + 65536, 0xffffffffll);
 }
 
+// the narrow wire form's position escapes: one place per tile of 256 slots, and a list for the others (runs' first clusters, gaps of 65535 bases or more) - a table
+// with more of those than this crosses with the wide columns
+static int64_t pesc_cap_of(int64_t E) { return E / 8 + 65536; }
+static size_t pesc_bytes_of(int64_t E) { return ((size_t)grid_for(E, BLOCK) + (size_t)pesc_cap_of(E)) * 8 + 16; }
+
 // ---- ssv_clip_cluster_async: the events of the pass -> a cluster table on its way to the host, in six phases ----
 
 // 1. the table set's format fields for a pass of E events
@@ -240,6 +287,14 @@ static void table_begin(const ssv_clip_state &C, TableSet &T, int64_t E)
 	T.format = C.table_mode; T.base_bits = fmt3 ? 2 : 4; T.n_runs = 0; T.n_exc = 0; T.expanded = false; T.ordered = false;
 	T.cig_bytes = fmt3 ? 2 : 4; T.len_bytes = fmt3 && C.max_lq < 65536 ? 2 : 4; T.support_bytes = fmt3 ? 2 : 4; T.ncig_bytes = fmt3 ? (C.max_ncig < 256 ? 1 : 2) : 4;
 	if (fmt3 && getenv("SSV_TABLE_WIDE_COLUMNS")) { T.len_bytes = 4; T.support_bytes = 4; T.ncig_bytes = 2; } // (tests: the widths that only reads > 64 kb, > 65535-read clusters, > 255-operation CIGARs ask for)
+	// what crosses: the narrow rows (table_wire.h) unless the pass asks for the columns themselves - SSV_TABLE_WIRE=wide, the wide columns above, the split scans
+	// (SSV_PACK_COLS=split), reads so long that a row would hardly hold their lengths - or cluster_pack meets a value a row cannot hold
+	static const bool split_cols = [] { const char *e = getenv("SSV_PACK_COLS"); return e && !strcmp(e, "split"); }();
+	const char *we = getenv("SSV_TABLE_WIRE");
+	T.wire = fmt3 && !split_cols && !getenv("SSV_TABLE_WIDE_COLUMNS") && !(we && !strcmp(we, "wide")) && C.max_lq <= (int)WIRE_LEN_MAX * 2 ? 1 : 0;
+	T.wire_ops = 0; T.pesc_tiles = 0; T.pesc_extra = 0; T.n_pesc = 0; memset(T.wire_piece, 0, sizeof(T.wire_piece));
+	T.v_pos = T.v_len = T.v_sup = T.v_nc = T.v_cig = nullptr;
+	T.job_rc = 0; T.job_err.clear(); T.job_expand_nt = -1;
 }
 
 // 2. bin the events by (contig, side, position), BAM order inside a bin.  A coordinate-sorted BAM emits its '5' events in key order
@@ -472,6 +527,7 @@ static int cluster_pack(ssv_ctx *c, TableSet &T, const ClusterArgs &ca)
 	if (fmt3) {
 		CHECK(ensure(c, T.o_len, (size_t)E * 8 + 16)); CHECK(ensure(c, T.o_sup, (size_t)E * 4 + 16)); CHECK(ensure(c, T.o_nc, (size_t)E * 2 + 16));
 		CHECK(ensure(c, T.o_runs, (size_t)E * sizeof(TableRun) + 16)); CHECK(ensure(c, T.o_exc, (size_t)exc_cap * 8 + 16));
+		if (T.wire) { CHECK(ensure(c, T.o_row, (size_t)E * sizeof(WireRow) + 16)); CHECK(ensure(c, T.o_pesc, pesc_bytes_of(E))); }
 	}
 	// [0] clusters | CIGAR operations << 32, [1] string bytes, [2] slow-list length, [3] "a quality outside the alphabet" flag,
 	// format 3: [4] runs | base exceptions << 32, [5] "a support count too wide" | "too many base exceptions" << 32
@@ -499,6 +555,9 @@ static int cluster_pack(ssv_ctx *c, TableSet &T, const ClusterArgs &ca)
 			p3.exc = P<uint64_t>(T.o_exc); p3.exc_count = reinterpret_cast<unsigned int *>(tot + 4) + 1; p3.exc_cap = (uint32_t)exc_cap;
 			p3.support_miss = reinterpret_cast<int *>(tot + 5); p3.exc_miss = reinterpret_cast<int *>(tot + 5) + 1;
 			p3.cig_bytes = T.cig_bytes; p3.cig_miss = reinterpret_cast<int *>(tot + 6);
+			// [6] high half: "a value no narrow row holds", [7] the operations of all clusters | position escapes outside the tiles' places << 32
+			p3.wire = T.wire; p3.row = P<WireRow>(T.o_row); p3.pos_esc = P<uint64_t>(T.o_pesc); p3.pos_esc_cap = (uint32_t)pesc_cap_of(E);
+			p3.wire_miss = reinterpret_cast<int *>(tot + 6) + 1; p3.ops_total = reinterpret_cast<uint32_t *>(tot + 7); p3.pos_esc_count = reinterpret_cast<unsigned int *>(tot + 7) + 1;
 		}
 		HIPCHECK(c, hipMemsetAsync(tot, 0, 64, c->st));
 		if (track) HIPCHECK(c, hipMemsetAsync(C.qual_seen.p, 0, 32, c->st));
@@ -528,7 +587,7 @@ static int cluster_pack(ssv_ctx *c, TableSet &T, const ClusterArgs &ca)
 			CHECK(ensure(c, C.tile_sums, (size_t)stride * 3 * 8));
 			TileSums ts;
 			ts.clusters = P<uint64_t>(C.tile_sums); ts.cig = ts.clusters + stride; ts.bytes = ts.cig + stride;
-			k_cluster_tile_sums<<<tiles, BLOCK, 0, c->st>>>(pa, ts);
+			k_cluster_tile_sums<<<tiles, BLOCK, 0, c->st>>>(pa, ts, T.wire);
 			k_scan_sums_lists<uint64_t><<<3, BLOCK, 0, c->st>>>(ts.clusters, (int64_t)tiles, stride);
 			k_cluster_cols3_tiles<<<tiles, BLOCK, 0, c->st>>>(pa, p3, dsc, P<uint32_t>(T.o_cig), ts, tot);
 		} else {
@@ -548,6 +607,7 @@ static int cluster_pack(ssv_ctx *c, TableSet &T, const ClusterArgs &ca)
 			// (rare) a cluster with more than 65535 reads: the support column as u32; more bases outside A/C/G/T than the exception list takes:
 			// the base streams at 4 bits
 			const uint64_t m = h_tot[5];
+			if ((uint32_t)(h_tot[6] >> 32) && T.wire) { T.wire = 0; continue; } // a length of 256 or more, a support of 255 or more, a CIGAR of 64 operations or more: the columns themselves
 			if ((uint32_t)m && T.support_bytes == 2) { T.support_bytes = 4; continue; }
 			if ((uint32_t)(m >> 32) && T.base_bits == 2) { T.base_bits = 4; continue; }
 			if ((uint32_t)h_tot[6] && T.cig_bytes == 2) { T.cig_bytes = 4; continue; } // an operation of 4096 bases or more (a long N / D)
@@ -566,56 +626,174 @@ static int cluster_pack(ssv_ctx *c, TableSet &T, const ClusterArgs &ca)
 		}
 		break;
 	}
-	T.n_clusters = (int64_t)(uint32_t)h_tot[0]; T.cig_ops = h_tot[0] >> 32; T.str_bytes = h_tot[1];
+	T.n_clusters = (int64_t)(uint32_t)h_tot[0]; T.wire_ops = h_tot[0] >> 32; T.cig_ops = T.wire ? (uint64_t)(uint32_t)h_tot[7] : T.wire_ops; T.str_bytes = h_tot[1];
+	if (T.wire) { T.pesc_tiles = (int64_t)grid_for(E, BLOCK); T.pesc_extra = (int64_t)(h_tot[7] >> 32); }
 	if (fmt3) { T.n_runs = (int64_t)(uint32_t)h_tot[4]; T.n_exc = (int64_t)(h_tot[4] >> 32); }
 	return SSV_OK;
 }
 
-// 5. the table goes to pinned host memory behind the pack kernels - on the named SDMA engine of the direction, else on the copy stream;
-//    ssv_clip_table_wait() waits for it
-static int table_copy_out(ssv_ctx *c, TableSet &T)
+// ---- the helper thread: what the host makes of a compact table's small pieces, while its strings are still crossing ----
+
+static int table_expand_columns(ssv_ctx *c, TableSet &T, int32_t n_threads, std::string &err);
+
+// put the runs (appended by whichever thread came first) and the exception lists in order
+static void table_order(TableSet &T)
 {
+	ssv_table_run *r = reinterpret_cast<ssv_table_run *>(T.h_runs.p);
+	std::sort(r, r + T.n_runs, [](const ssv_table_run &a, const ssv_table_run &b) { return a.first < b.first; });
+	uint64_t *e = P<uint64_t>(T.h_exc);
+	std::sort(e, e + T.n_exc);
+	if (T.wire) { // the tiles' places are in order already, with holes: close them up, then merge the few others in
+		uint64_t *pe = P<uint64_t>(T.h_pesc);
+		int64_t m = 0;
+		for (int64_t k = 0; k < T.pesc_tiles; ++k) if (pe[k] != ~0ull) pe[m++] = pe[k];
+		std::sort(pe + T.pesc_tiles, pe + T.pesc_tiles + T.pesc_extra);
+		std::copy(pe + T.pesc_tiles, pe + T.pesc_tiles + T.pesc_extra, pe + m);
+		std::inplace_merge(pe, pe + m, pe + m + T.pesc_extra);
+		T.n_pesc = m + T.pesc_extra;
+	}
+	T.ordered = true;
+}
+
+// one table set's job: wait for the small pieces, order the lists, rebuild the handed-out columns from the rows, and the expanded columns if this context's caller asks for them
+static void table_job(ssv_ctx *c, TableSet &T)
+{
+	ssv_clip_state &C = *c->clip;
+	if (T.via_link) link_wait(c, T.copied_sig);
+	else if (hipEventSynchronize(T.small_ev) != hipSuccess) { (void)hipGetLastError(); T.job_rc = SSV_E_HIP; T.job_err = "compact table: waiting for the copy of the small columns failed"; return; }
+	table_order(T);
+	std::lock_guard<std::mutex> lk(C.pool_mu);
+	const int64_t n = T.n_clusters;
+	const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(T.job_expand_nt > 0 ? T.job_expand_nt : (int32_t)effective_cpus()), 64, n / 32768 + 1}));
+	if (T.wire) {
+		WireIn in{P<WireRow>(T.h_row), n, P<uint64_t>(T.h_pesc), T.n_pesc, T.h_cig.p, T.cig_bytes, T.wire_ops};
+		WireOut out{reinterpret_cast<int32_t *>(T.r_pos.p), T.r_len.p, T.len_bytes, T.r_sup.p, T.support_bytes, T.r_nc.p, T.ncig_bytes, T.r_cig.p, T.cig_ops};
+		if (wire_rebuild(in, out, nt, [&](int k, const std::function<void(int)> &f) { C.pool.run(k, f); })) {
+			T.job_rc = SSV_E_HIP; T.job_err = "compact table: the wire rows do not add up to the table";
+			return;
+		}
+	}
+	if (T.job_expand_nt >= 0) T.job_rc = table_expand_columns(c, T, T.job_expand_nt, T.job_err);
+}
+
+static void table_helper_main(ssv_ctx *c)
+{
+	TableHelper &H = c->clip->helper;
+	(void)hipSetDevice(c->device);
+	for (;;) {
+		int which;
+		{
+			std::unique_lock<std::mutex> lk(H.mu);
+			H.cv_go.wait(lk, [&] { return H.quit || !H.jobs.empty(); });
+			if (H.jobs.empty()) return;
+			which = H.jobs.front(); H.jobs.pop_front();
+		}
+		table_job(c, c->clip->tab[which]);
+		{ std::unique_lock<std::mutex> lk(H.mu); c->clip->tab[which].job_pending = false; }
+		H.cv_done.notify_all();
+	}
+}
+
+static void table_job_start(ssv_ctx *c, int which)
+{
+	TableHelper &H = c->clip->helper;
+	if (!H.th.joinable()) H.th = std::thread(table_helper_main, c);
+	{ std::unique_lock<std::mutex> lk(H.mu); c->clip->tab[which].job_pending = true; H.jobs.push_back(which); }
+	H.cv_go.notify_all();
+}
+
+// the helper is done with the set (what it found is in T.job_rc / job_err)
+static void table_job_join(ssv_ctx *c, TableSet &T)
+{
+	TableHelper &H = c->clip->helper;
+	std::unique_lock<std::mutex> lk(H.mu);
+	H.cv_done.wait(lk, [&] { return !T.job_pending; });
+}
+
+// (ssv_ctx_destroy) let the queued jobs end, then the thread
+static void table_helper_stop(ssv_ctx *c)
+{
+	TableHelper &H = c->clip->helper;
+	if (!H.th.joinable()) return;
+	{ std::unique_lock<std::mutex> lk(H.mu); H.quit = true; }
+	H.cv_go.notify_all();
+	H.th.join();
+}
+
+// 5. the table goes to pinned host memory behind the pack kernels - on the named SDMA engine of the direction, else on the copy stream -, the small pieces first and on a
+//    completion of their own: the helper thread works on them while the string block crosses.  ssv_clip_table_wait() waits for both
+static int table_copy_out(ssv_ctx *c, int which)
+{
+	TableSet &T = c->clip->tab[which];
 	const bool fmt3 = T.format == 3;
 	const size_t nc = (size_t)T.n_clusters;
-	struct CopyItem { HBuf *h; DBuf *d; size_t bytes; };
+	struct CopyItem { HBuf *h; const void *d; size_t bytes; int piece; };
 	std::vector<CopyItem> cp;
-	if (fmt3)
-		cp = {{&T.h_pos, &T.o_pos, nc * 4}, {&T.h_len, &T.o_len, nc * 2 * (size_t)T.len_bytes}, {&T.h_sup, &T.o_sup, nc * (size_t)T.support_bytes},
-		      {&T.h_nc, &T.o_nc, nc * (size_t)T.ncig_bytes}, {&T.h_qmiss, &T.o_qmiss, nc}, {&T.h_str, &T.o_str, (size_t)T.str_bytes}, {&T.h_cig, &T.o_cig, (size_t)T.cig_ops * (size_t)T.cig_bytes},
-		      {&T.h_runs, &T.o_runs, (size_t)T.n_runs * sizeof(TableRun)}, {&T.h_exc, &T.o_exc, (size_t)T.n_exc * 8}};
+	const CopyItem str{&T.h_str, T.o_str.p, (size_t)T.str_bytes, 6};
+	if (fmt3 && T.wire)
+		cp = {{&T.h_row, T.o_row.p, nc * sizeof(WireRow), 0}, {&T.h_qmiss, T.o_qmiss.p, nc, 1}, {&T.h_cig, T.o_cig.p, (size_t)T.wire_ops * (size_t)T.cig_bytes, 2},
+		      {&T.h_runs, T.o_runs.p, (size_t)T.n_runs * sizeof(TableRun), 3}, {&T.h_exc, T.o_exc.p, (size_t)T.n_exc * 8, 4},
+		      {&T.h_pesc, T.o_pesc.p, (size_t)(T.pesc_tiles + T.pesc_extra) * 8, 5}, str}; // (the tiles' places and the list behind them are one piece of memory)
+	else if (fmt3)
+		cp = {{&T.h_pos, T.o_pos.p, nc * 4, 0}, {&T.h_len, T.o_len.p, nc * 2 * (size_t)T.len_bytes, 0}, {&T.h_sup, T.o_sup.p, nc * (size_t)T.support_bytes, 0},
+		      {&T.h_nc, T.o_nc.p, nc * (size_t)T.ncig_bytes, 0}, {&T.h_qmiss, T.o_qmiss.p, nc, 1}, {&T.h_cig, T.o_cig.p, (size_t)T.cig_ops * (size_t)T.cig_bytes, 2},
+		      {&T.h_runs, T.o_runs.p, (size_t)T.n_runs * sizeof(TableRun), 3}, {&T.h_exc, T.o_exc.p, (size_t)T.n_exc * 8, 4}, str};
 	else
-		cp = {{&T.h_tid, &T.o_tid, nc * 4}, {&T.h_pos, &T.o_pos, nc * 4}, {&T.h_side, &T.o_side, nc}, {&T.h_support, &T.o_support, nc * 4},
-		      {&T.h_ll, &T.o_ll, nc * 4}, {&T.h_lr, &T.o_lr, nc * 4}, {&T.h_qmiss, &T.o_qmiss, nc}, {&T.h_stroff, &T.o_stroff, nc * 8},
-		      {&T.h_cigoff, &T.o_cigoff, nc * 8}, {&T.h_ncig, &T.o_ncig, nc * 4}, {&T.h_str, &T.o_str, (size_t)T.str_bytes}, {&T.h_cig, &T.o_cig, (size_t)T.cig_ops * 4}};
-	for (auto &x : cp) CHECK(ensure_host(c, *x.h, x.bytes + 16));
+		cp = {{&T.h_tid, T.o_tid.p, nc * 4, 0}, {&T.h_pos, T.o_pos.p, nc * 4, 0}, {&T.h_side, T.o_side.p, nc, 0}, {&T.h_support, T.o_support.p, nc * 4, 0},
+		      {&T.h_ll, T.o_ll.p, nc * 4, 0}, {&T.h_lr, T.o_lr.p, nc * 4, 0}, {&T.h_qmiss, T.o_qmiss.p, nc, 1}, {&T.h_stroff, T.o_stroff.p, nc * 8, 0},
+		      {&T.h_cigoff, T.o_cigoff.p, nc * 8, 0}, {&T.h_ncig, T.o_ncig.p, nc * 4, 0}, {&T.h_cig, T.o_cig.p, (size_t)T.cig_ops * 4, 2}, str};
+	for (auto &x : cp) { CHECK(ensure_host(c, *x.h, x.bytes + 16)); T.wire_piece[x.piece] += x.bytes; }
+	if (fmt3 && T.wire) {
+		if (!T.r_pos.ensure(nc * 4 + 16) || !T.r_len.ensure(nc * 2 * (size_t)T.len_bytes + 16) || !T.r_sup.ensure(nc * (size_t)T.support_bytes + 16) || !T.r_nc.ensure(nc * (size_t)T.ncig_bytes + 16) ||
+		    !T.r_cig.ensure((size_t)T.cig_ops * (size_t)T.cig_bytes + 16)) { c->err = "out of host memory for the cluster table's columns"; return SSV_E_NOMEM; }
+		T.v_pos = T.r_pos.p; T.v_len = T.r_len.p; T.v_sup = T.r_sup.p; T.v_nc = T.r_nc.p; T.v_cig = T.r_cig.p;
+	} else { T.v_pos = T.h_pos.p; T.v_len = T.h_len.p; T.v_sup = T.h_sup.p; T.v_nc = T.h_nc.p; T.v_cig = T.h_cig.p; }
 	T.via_link = false;
 	if (c->link.ok) {
-		// (the pack kernels are done: cluster_pack left through a synchronisation of the stream.)  Every piece on the engine of the direction; the signal counts them down.
-		int64_t pieces = 0;
-		const CopyItem *big = nullptr;
-		for (auto &x : cp) if (x.bytes) { ++pieces; if (!big || x.bytes > big->bytes) big = &x; }
+		// (the pack kernels are done: cluster_pack left through a synchronisation of the stream.)  Every piece on the engine of the direction; copied_sig counts the small
+		// ones down, the string block has a signal of its own (it is the one that is timed)
+		const CopyItem *big = cp.back().bytes ? &cp.back() : nullptr;
+		int64_t small = 0;
+		for (auto &x : cp) if (x.bytes && &x != big) ++small;
 		T.big_bytes = big ? big->bytes : 0;
-		c->link.signal_store(T.copied_sig, pieces - (big ? 1 : 0));
+		c->link.signal_store(T.copied_sig, small);
 		c->link.signal_store(T.big_sig, big ? 1 : 0);
-		int64_t started = 0;
-		for (auto &x : cp) if (x.bytes) { if (!link_copy(c, x.h->p, x.d->p, x.bytes, true, &x == big ? T.big_sig : T.copied_sig)) break; ++started; }
-		if (started == pieces) T.via_link = true;
-		else { // an engine that refuses: let what was started land, then copy everything the runtime's way
-			bool big_started = false;
-			{ int64_t k = 0; for (auto &x : cp) if (x.bytes) { if (k < started && &x == big) big_started = true; ++k; } }
-			c->link.signal_store(T.copied_sig, c->link.signal_load(T.copied_sig) - ((pieces - started) - (big && !big_started ? 1 : 0)));
-			if (big && !big_started) c->link.signal_store(T.big_sig, 0);
-			link_wait(c, T.copied_sig); link_wait(c, T.big_sig);
+		const char *re = getenv("SSV_LINK_REFUSE_AFTER"); // (tests: the engine takes that many pieces of every table, then refuses)
+		const int64_t refuse_after = re ? (int64_t)atoll(re) : -1;
+		int64_t started_small = 0;
+		bool big_started = false, refused = false;
+		for (auto &x : cp) if (x.bytes) {
+			if ((refuse_after >= 0 && started_small + (big_started ? 1 : 0) >= refuse_after) || !link_copy(c, x.h->p, x.d, x.bytes, true, &x == big ? T.big_sig : T.copied_sig)) { refused = true; break; }
+			if (&x == big) big_started = true; else ++started_small;
+		}
+		if (!refused) T.via_link = true;
+		else {
+			// an engine that refuses: let what was started land, then copy everything the runtime's way.  The pieces under way count their signal down while we stand here:
+			// it is done when it shows the number of pieces that never started, and only then is it ours to set
+			while (c->link.signal_wait(T.copied_sig, HSA_SIGNAL_CONDITION_EQ, small - started_small, UINT64_MAX, HSA_WAIT_STATE_BLOCKED) != small - started_small) {}
+			while (c->link.signal_wait(T.big_sig, HSA_SIGNAL_CONDITION_EQ, big && !big_started ? 1 : 0, UINT64_MAX, HSA_WAIT_STATE_BLOCKED) != (big && !big_started ? 1 : 0)) {}
+			c->link.signal_store(T.copied_sig, 0); c->link.signal_store(T.big_sig, 0);
+			T.big_bytes = 0;
 			c->link.ok = false;
 		}
 	}
 	if (!T.via_link) {
 		HIPCHECK(c, hipEventRecord(T.packed_ev, c->st));
 		HIPCHECK(c, hipStreamWaitEvent(c->st_copy, T.packed_ev, 0));
-		for (auto &x : cp) if (x.bytes) HIPCHECK(c, hipMemcpyAsync(x.h->p, x.d->p, x.bytes, hipMemcpyDeviceToHost, c->st_copy));
+		for (auto &x : cp) if (x.bytes && &x != &cp.back()) HIPCHECK(c, hipMemcpyAsync(x.h->p, x.d, x.bytes, hipMemcpyDeviceToHost, c->st_copy));
+		HIPCHECK(c, hipEventRecord(T.small_ev, c->st_copy));
+		if (cp.back().bytes) HIPCHECK(c, hipMemcpyAsync(cp.back().h->p, cp.back().d, cp.back().bytes, hipMemcpyDeviceToHost, c->st_copy));
 		HIPCHECK(c, hipEventRecord(T.copied, c->st_copy));
 	}
 	T.in_flight = true;
+	static const bool timing = [] { const char *e = getenv("SSV_TIMING"); return e ? atoi(e) : 0; }() >= 2;
+	if (timing) {
+		const uint64_t *w = T.wire_piece;
+		fprintf(stderr, "[timing] (cluster table: %lld clusters cross as %llu bytes, %.1f a cluster - %s %llu, flags %llu, CIGAR stream %llu, runs %llu, base exceptions %llu, position escapes %llu, strings %llu)\n",
+		        (long long)T.n_clusters, (unsigned long long)(w[0] + w[1] + w[2] + w[3] + w[4] + w[5] + w[6]), (double)(w[0] + w[1] + w[2] + w[3] + w[4] + w[5] + w[6]) / (double)T.n_clusters,
+		        T.wire ? "narrow rows" : "columns", (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4], (unsigned long long)w[5], (unsigned long long)w[6]);
+	}
+	if (fmt3) { T.job_expand_nt = c->clip->expand_nt; table_job_start(c, which); }
 	return SSV_OK;
 }
 
@@ -630,7 +808,11 @@ static int table_presize(ssv_ctx *c, const TableSet &T, TableSet &O)
 		      {&O.h_nc, &O.o_nc, nc * (size_t)T.ncig_bytes, E * 2}, {&O.h_qmiss, &O.o_qmiss, nc, E}, {&O.h_str, &O.o_str, str_total, T.o_str.cap - 16},
 		      {&O.h_cig, &O.o_cig, cig_total * 4, sum_ncig * 4}, {&O.h_runs, &O.o_runs, (size_t)T.n_runs * sizeof(TableRun), E * sizeof(TableRun)},
 		      {&O.h_exc, &O.o_exc, (size_t)T.n_exc * 8, (size_t)exc_cap_of((int64_t)E) * 8}};
-	else
+	if (T.format == 3 && T.wire) {
+		oc.push_back({&O.h_row, &O.o_row, nc * sizeof(WireRow), E * sizeof(WireRow)});
+		oc.push_back({&O.h_pesc, &O.o_pesc, (size_t)(T.pesc_tiles + T.pesc_extra) * 8, pesc_bytes_of((int64_t)E) - 16});
+	}
+	if (T.format != 3)
 		oc = {{&O.h_tid, &O.o_tid, nc * 4, E * 4}, {&O.h_pos, &O.o_pos, nc * 4, E * 4}, {&O.h_side, &O.o_side, nc, E}, {&O.h_support, &O.o_support, nc * 4, E * 4},
 		      {&O.h_ll, &O.o_ll, nc * 4, E * 4}, {&O.h_lr, &O.o_lr, nc * 4, E * 4}, {&O.h_qmiss, &O.o_qmiss, nc, E}, {&O.h_stroff, &O.o_stroff, nc * 8, E * 8},
 		      {&O.h_cigoff, &O.o_cigoff, nc * 8, E * 8}, {&O.h_ncig, &O.o_ncig, nc * 4, E * 4}, {&O.h_str, &O.o_str, str_total, T.o_str.cap - 16},
@@ -657,6 +839,7 @@ int ssv_clip_cluster_async(ssv_ctx *c, int64_t *n_clusters, int64_t *n_events)
 	// take the table set that is not the most recent one; its previous copy (two calls ago) must have landed
 	const int s_ = C.tab_cur ^ 1;
 	TableSet &T = C.tab[s_];
+	table_job_join(c, T); // (the helper may still be at work on the set's last table)
 	if (T.in_flight) { if (T.via_link) table_link_wait(c, T); else HIPCHECK(c, hipEventSynchronize(T.copied)); T.in_flight = false; }
 	C.tab_cur = s_;
 	const int64_t E = C.n_events;
@@ -674,7 +857,7 @@ int ssv_clip_cluster_async(ssv_ctx *c, int64_t *n_clusters, int64_t *n_events)
 	CHECK(cluster_pack(c, T, ca));
 	if (n_clusters) *n_clusters = T.n_clusters;
 	if (T.n_clusters == 0) return SSV_OK;
-	CHECK(table_copy_out(c, T));
+	CHECK(table_copy_out(c, s_));
 	if (!C.tab[s_ ^ 1].in_flight) CHECK(table_presize(c, T, C.tab[s_ ^ 1]));
 	return SSV_OK;
 }
@@ -703,6 +886,7 @@ static int table_wait(ssv_ctx *c, int which, ssv_cluster_table *out)
 	HIPCHECK(c, hipSetDevice(c->device));
 	TableSet &T = c->clip->tab[which];
 	memset(out, 0, sizeof(*out));
+	table_job_join(c, T);
 	if (T.in_flight) {
 		ProfScope pd(c, P_TABLE_D2H, T.n_clusters); // what is left of the copy when the caller asks for the table
 		if (T.via_link) table_link_wait(c, T); else HIPCHECK(c, hipEventSynchronize(T.copied));
@@ -713,17 +897,11 @@ static int table_wait(ssv_ctx *c, int which, ssv_cluster_table *out)
 	if (T.n_clusters == 0) return SSV_OK;
 	if (T.format == 3) {
 		out->len_bytes = T.len_bytes; out->support_bytes = T.support_bytes; out->ncig_bytes = T.ncig_bytes;
-		out->pos = P<int32_t>(T.h_pos); out->c_len = T.h_len.p; out->c_support = T.h_sup.p; out->c_ncig = T.h_nc.p; out->c_flags = P<uint8_t>(T.h_qmiss);
-		out->str = P<uint8_t>(T.h_str); out->cigar = T.cig_bytes == 4 ? P<uint32_t>(T.h_cig) : nullptr; out->c_cigar = T.h_cig.p; out->cigar_bytes = T.cig_bytes; out->str_bytes = T.str_bytes; out->cigar_ops = T.cig_ops;
+		if (T.job_rc != SSV_OK) { c->err = T.job_err; return T.job_rc; } // (the helper thread ordered the lists and rebuilt the columns behind the small pieces' copy)
+		out->pos = static_cast<const int32_t *>(T.v_pos); out->c_len = T.v_len; out->c_support = T.v_sup; out->c_ncig = T.v_nc; out->c_flags = P<uint8_t>(T.h_qmiss);
+		out->str = P<uint8_t>(T.h_str); out->cigar = T.cig_bytes == 4 ? static_cast<const uint32_t *>(T.v_cig) : nullptr; out->c_cigar = T.v_cig; out->cigar_bytes = T.cig_bytes; out->str_bytes = T.str_bytes; out->cigar_ops = T.cig_ops;
 		out->runs = reinterpret_cast<const ssv_table_run *>(T.h_runs.p); out->n_runs = T.n_runs;
 		out->base_exc = P<uint64_t>(T.h_exc); out->n_base_exc = T.n_exc;
-		if (!T.ordered) { // once per table: put the runs (appended by whichever thread came first) and the exceptions in order
-			ssv_table_run *r = reinterpret_cast<ssv_table_run *>(T.h_runs.p);
-			std::sort(r, r + T.n_runs, [](const ssv_table_run &a, const ssv_table_run &b) { return a.first < b.first; });
-			uint64_t *e = P<uint64_t>(T.h_exc);
-			std::sort(e, e + T.n_exc);
-			T.ordered = true;
-		}
 		if (T.expanded) { table_expanded_view(T, out); out->support_sum = T.support_sum; }
 		return SSV_OK;
 	}
@@ -742,9 +920,9 @@ int ssv_clip_table_wait_prev(ssv_ctx *c, ssv_cluster_table *out) { return c && o
 template <class LenT, class SupT, class NcT>
 static void expand_range(TableSet &T, int64_t k0, int64_t k1, bool second, uint64_t &so, uint64_t &co, int64_t &ssum)
 {
-	const LenT *len = reinterpret_cast<const LenT *>(T.h_len.p);
-	const SupT *sup = reinterpret_cast<const SupT *>(T.h_sup.p);
-	const NcT *ncg = reinterpret_cast<const NcT *>(T.h_nc.p);
+	const LenT *len = reinterpret_cast<const LenT *>(T.v_len);
+	const SupT *sup = reinterpret_cast<const SupT *>(T.v_sup);
+	const NcT *ncg = reinterpret_cast<const NcT *>(T.v_nc);
 	const uint8_t *fl = P<uint8_t>(T.h_qmiss);
 	const uint64_t bb = (uint64_t)T.base_bits, qb = (uint64_t)T.qual_bits, qg = (uint64_t)T.qual_group;
 	int32_t *x_ll = T.x_ll.data(), *x_lr = T.x_lr.data(), *x_sup = T.x_support.data(), *x_nc = T.x_ncig.data();
@@ -768,16 +946,12 @@ static void expand_range(TableSet &T, int64_t k0, int64_t k1, bool second, uint6
 	}
 }
 
-int ssv_clip_table_expand(ssv_ctx *c, ssv_cluster_table *t, int32_t n_threads)
+// the expanded columns of a format-3 table whose small pieces have landed and whose handed-out columns stand (the caller holds pool_mu)
+static int table_expand_columns(ssv_ctx *c, TableSet &T, int32_t n_threads, std::string &err)
 {
-	if (!c || !t) return SSV_E_ARG;
 	ssv_clip_state &C = *c->clip;
-	TableSet *Tp = nullptr;
-	for (auto &x : C.tab) if (x.format == 3 && !x.in_flight && x.n_clusters == t->n_clusters && (t->n_clusters == 0 || t->pos == P<int32_t>(x.h_pos))) Tp = &x;
-	if (t->format != 3 || !Tp) { c->err = "ssv_clip_table_expand takes a compact (format 3) table handed out by ssv_clip_table_wait"; return SSV_E_ARG; }
-	TableSet &T = *Tp;
 	const int64_t n = T.n_clusters;
-	if (n == 0 || T.expanded) { if (n) table_expanded_view(T, t); t->support_sum = T.support_sum; return SSV_OK; }
+	if (n == 0 || T.expanded) return SSV_OK;
 	T.x_tid.resize((size_t)n); T.x_side.resize((size_t)n); T.x_support.resize((size_t)n); T.x_ll.resize((size_t)n); T.x_lr.resize((size_t)n); T.x_qmiss.resize((size_t)n);
 	T.x_ncig.resize((size_t)n); T.x_stroff.resize((size_t)n); T.x_cigoff.resize((size_t)n);
 	const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(n_threads > 0 ? n_threads : (int32_t)effective_cpus()), 64, n / 32768 + 1}));
@@ -810,12 +984,43 @@ int ssv_clip_table_expand(ssv_ctx *c, ssv_cluster_table *t, int32_t n_threads)
 	C.pool.run(nt, [&](int w) { pass(w, 0); });
 	for (int v = 0; v < nt; ++v) { part_str[(size_t)v + 1] += part_str[(size_t)v]; part_cig[(size_t)v + 1] += part_cig[(size_t)v]; }
 	C.pool.run(nt, [&](int w) { pass(w, 1); });
-	if (part_str[(size_t)nt] != T.str_bytes || part_cig[(size_t)nt] != T.cig_ops) { c->err = "compact table: the rebuilt offsets do not add up to the blob sizes"; return SSV_E_HIP; }
+	if (part_str[(size_t)nt] != T.str_bytes || part_cig[(size_t)nt] != T.cig_ops) { err = "compact table: the rebuilt offsets do not add up to the blob sizes"; return SSV_E_HIP; }
 	T.support_sum = 0;
 	for (int64_t v : part_sup) T.support_sum += v;
 	T.expanded = true;
-	table_expanded_view(T, t);
+	return SSV_OK;
+}
+
+int ssv_clip_table_expand(ssv_ctx *c, ssv_cluster_table *t, int32_t n_threads)
+{
+	if (!c || !t) return SSV_E_ARG;
+	ssv_clip_state &C = *c->clip;
+	TableSet *Tp = nullptr;
+	for (auto &x : C.tab) if (x.format == 3 && !x.in_flight && x.n_clusters == t->n_clusters && (t->n_clusters == 0 || t->pos == static_cast<const int32_t *>(x.v_pos))) Tp = &x;
+	if (t->format != 3 || !Tp) { c->err = "ssv_clip_table_expand takes a compact (format 3) table handed out by ssv_clip_table_wait"; return SSV_E_ARG; }
+	TableSet &T = *Tp;
+	C.expand_nt = std::max(0, n_threads); // this context's caller wants the expanded columns: from now on the helper thread builds them with the others
+	if (T.n_clusters && !T.expanded) {
+		std::lock_guard<std::mutex> lk(C.pool_mu); // (the helper may be at work on the other table set)
+		CHECK(table_expand_columns(c, T, n_threads, c->err));
+	}
+	if (T.n_clusters) table_expanded_view(T, t);
 	t->support_sum = T.support_sum;
+	return SSV_OK;
+}
+
+int ssv_clip_table_wire_bytes(ssv_ctx *c, const ssv_cluster_table *t, ssv_table_wire *out)
+{
+	if (!c || !t || !out) return SSV_E_ARG;
+	memset(out, 0, sizeof(*out));
+	if (t->n_clusters == 0) return SSV_OK;
+	const TableSet *Tp = nullptr;
+	for (auto &x : c->clip->tab) if (!x.in_flight && x.format == t->format && x.n_clusters == t->n_clusters && t->pos == static_cast<const int32_t *>(x.v_pos)) Tp = &x;
+	if (!Tp) { c->err = "ssv_clip_table_wire_bytes takes a table handed out by ssv_clip_table_wait"; return SSV_E_ARG; }
+	const uint64_t *w = Tp->wire_piece;
+	out->narrow = Tp->wire;
+	out->rows = w[0]; out->flags = w[1]; out->cigar = w[2]; out->runs = w[3]; out->base_exc = w[4]; out->pos_esc = w[5]; out->str = w[6];
+	for (int k = 0; k < 7; ++k) out->total += w[k];
 	return SSV_OK;
 }
 

@@ -1040,6 +1040,7 @@ void ssv_ctx_destroy(ssv_ctx *c)
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->st);
 
+	table_helper_stop(c); // (a rebuild still pending ends first: it reads the buffers that go below)
 	for (auto &t : c->clip->tab) if (t.in_flight && t.via_link) { table_link_wait(c, t); t.in_flight = false; } // (a table still on its way out)
 	bamdec_release_handles(c);
 	samdec_release_handles(c);
@@ -1051,6 +1052,7 @@ void ssv_ctx_destroy(ssv_ctx *c)
 	if (c->ev_st) (void)hipEventDestroy(c->ev_st);
 	for (auto &t : c->clip->tab) {
 		if (t.copied) (void)hipEventDestroy(t.copied);
+		if (t.small_ev) (void)hipEventDestroy(t.small_ev);
 		if (c->link.signal_destroy && t.copied_sig.handle) (void)c->link.signal_destroy(t.copied_sig);
 		if (c->link.signal_destroy && t.big_sig.handle) (void)c->link.signal_destroy(t.big_sig);
 		if (t.packed_ev) (void)hipEventDestroy(t.packed_ev);
@@ -1082,7 +1084,7 @@ int ssv_ctx_create(int device, ssv_ctx **out)
 	TableSet *tab = c->clip->tab;
 	bool ok = true;
 	for (hipStream_t *s : {&c->st_copy, &c->st_h2d}) ok = ok && hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
-	for (hipEvent_t *ev : {&c->ev_st, &c->ss[0].ready, &c->ss[1].ready, &c->ev_packed, &tab[0].packed_ev, &tab[1].packed_ev, &tab[0].copied, &tab[1].copied})
+	for (hipEvent_t *ev : {&c->ev_st, &c->ss[0].ready, &c->ss[1].ready, &c->ev_packed, &tab[0].packed_ev, &tab[1].packed_ev, &tab[0].copied, &tab[1].copied, &tab[0].small_ev, &tab[1].small_ev})
 		ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
 	if (!ok) { g_create_error = "cannot create the copy stream / events"; ssv_ctx_destroy(c); return SSV_E_NODEVICE; }
 	link_init(c);

@@ -4,6 +4,8 @@
 //   fixed columns   pos i32 | left_len, right_len (u16 or u32 each) | support (u16 or u32) | n_cigar (u8 or u16) | flags u8  = 12 bytes
 //                   (contig and side come from a handful of (contig, side, first cluster) runs; string / CIGAR offsets are prefix sums)
 //   CIGAR           n_cigar operations
+//                   (these two are what a caller reads; all but the flags cross as a 6-byte row, a few position escapes and the operations of the
+//                   CIGARs that are not just the two lengths - table_wire.h -, and the host rebuilds them while the strings cross)
 //   string block    [base stream | quality stream], each a whole number of dwords: the n = left_len + right_len bases of seq_left + seq_right
 //                   at base_bits (2: index into "ACGT"; 4: BAM's code) each, base i at stream bits [i * base_bits, +base_bits) (bit b of a
 //                   stream = bit b % 32 of dword b / 32), then the n qualities at qual_bits each the same way (8: characters, phred + 33),
@@ -15,6 +17,7 @@
 #pragma once
 
 #include "clip_kernels.h"
+#include "table_wire.h"
 
 namespace ssv {
 
@@ -41,7 +44,25 @@ struct Pack3Args {
 	int cig_bytes;            // 2: a CIGAR operation as length << 4 | code in 16 bits (lengths below 4096); 4: BAM's 32 bits
 	int *cig_miss;            // an operation that does not fit cig_bytes
 	int *exc_miss;            // more exceptions than exc_cap (or a base index / cluster index beyond the entry's fields)
+	// the narrow wire form (table_wire.h; wire == 1): rows instead of pos / len / support / ncig, and only the kind-0 clusters' operations in the CIGAR stream
+	int wire;
+	WireRow *row;             // [n]
+	uint64_t *pos_esc;        // cluster << 32 | pos: [tiles] the tiles' first clusters (~0: a tile without one), then the list the other escapes are appended to
+	unsigned int *pos_esc_count;
+	uint32_t pos_esc_cap;
+	int *wire_miss;           // a value that a row cannot hold, or more escapes than pos_esc_cap
+	uint32_t *ops_total;      // the CIGAR operations of all clusters (the totals' CIGAR count is the stream's)
 };
+
+// 1: the two operations are exactly {ll M, lr S}, 2: exactly {ll S, lr M}, 0: anything else
+__device__ __forceinline__ uint32_t wire_cigar_kind(int ncg, uint32_t cg0, uint32_t cg1, int ll, int lr)
+{
+	if (ncg != 2) return 0;
+	const uint32_t a = (uint32_t)ll << 4, b = (uint32_t)lr << 4;
+	if (cg0 == (a | WIRE_OP_M) && cg1 == (b | WIRE_OP_S)) return 1;
+	if (cg0 == (a | WIRE_OP_S) && cg1 == (b | WIRE_OP_M)) return 2;
+	return 0;
+}
 
 __host__ __device__ __forceinline__ uint64_t table3_block_bytes(uint64_t n, int base_bits, int qual_bits, int qual_group = 1)
 {
@@ -149,19 +170,27 @@ __device__ __forceinline__ SlotWords slot_words(const PackArgs &p, const SlotClu
 	return w;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_cluster_tile_sums(PackArgs p, TileSums ts)
+// (wire == 1: ts.cig counts the operations of the CIGAR stream - the kind-0 clusters' -, and the high half of ts.clusters those of all clusters)
+__global__ __launch_bounds__(BLOCK) void k_cluster_tile_sums(PackArgs p, TileSums ts, int wire)
 {
 	__shared__ uint64_t s_cnt[WAVES_PER_BLOCK], s_bytes[WAVES_PER_BLOCK];
+	__shared__ uint32_t s_ops[WAVES_PER_BLOCK];
 	const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	uint64_t cnt = 0, bytes = 0;
+	uint32_t ops = 0;
 	bool lng = false;
 	if (j < p.c.E && p.c.support[j] > 0) { // (only what the sums need of the line: its second and third quarter)
 		const bool single = !p.c.mflag[j] || p.c.support[j] == 1;
 		const uint32_t e = single ? (uint32_t)j : p.c.c_cig_ev[j];
 		const uint4 *ep = reinterpret_cast<const uint4 *>(p.c.ev + e);
 		const uint4 eb = ep[1], ec = ep[2];
-		const uint64_t n = (uint64_t)(single ? (int)eb.w : p.c.c_ll[j]) + (uint64_t)(single ? (int)ec.x : p.c.c_lr[j]);
+		const int ll = single ? (int)eb.w : p.c.c_ll[j], lr = single ? (int)ec.x : p.c.c_lr[j];
+		const uint64_t n = (uint64_t)ll + (uint64_t)lr;
 		cnt = 1ull | ((uint64_t)ec.z << 32);
+		if (wire) {
+			ops = ec.z;
+			if (ec.z == 2u && wire_cigar_kind(2, ec.w, ep[3].x, ll, lr)) cnt = 1ull;
+		}
 		bytes = 4ull * ((n * (uint64_t)p.base_bits + 31) / 32 + (qual_stream_bits(n, (uint64_t)p.qual_bits, (uint64_t)p.qual_group) + 31) / 32);
 		lng = p.packed && single && (int)ec.y > PACK_MAX_LQ;
 	}
@@ -174,19 +203,20 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_tile_sums(PackArgs p, TileSum
 		if (lng) p.slow_list[base + (uint32_t)__popcll(lm & lanemask_lt())] = (uint32_t)j;
 	}
 	cnt = wave_sum(cnt); bytes = wave_sum(bytes);
-	if (lane_id() == 0) { s_cnt[wave_id()] = cnt; s_bytes[wave_id()] = bytes; }
+	if (wire) ops = wave_sum(ops);
+	if (lane_id() == 0) { s_cnt[wave_id()] = cnt; s_bytes[wave_id()] = bytes; s_ops[wave_id()] = ops; }
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		uint64_t c = 0, b = 0;
-		for (int w = 0; w < WAVES_PER_BLOCK; ++w) { c += s_cnt[w]; b += s_bytes[w]; }
-		ts.clusters[blockIdx.x] = c & 0xffffffffull; ts.cig[blockIdx.x] = c >> 32; ts.bytes[blockIdx.x] = b;
+		uint64_t c = 0, b = 0, o = 0;
+		for (int w = 0; w < WAVES_PER_BLOCK; ++w) { c += s_cnt[w]; b += s_bytes[w]; o += s_ops[w]; }
+		ts.clusters[blockIdx.x] = (c & 0xffffffffull) | (o << 32); ts.cig[blockIdx.x] = c >> 32; ts.bytes[blockIdx.x] = b;
 	}
 }
 
 // ts: the tile sums, scanned (exclusive); tot: [0] clusters | CIGAR operations << 32, [1] string bytes - the totals, written by the last tile
 __global__ __launch_bounds__(BLOCK) void k_cluster_cols3_tiles(PackArgs p, Pack3Args q, PackDesc *__restrict__ desc, uint32_t *__restrict__ out_cig, TileSums ts, uint64_t *__restrict__ tot)
 {
-	__shared__ uint64_t lds[WAVES_PER_BLOCK + 1];
+	__shared__ uint64_t lds[WAVES_PER_BLOCK + 1], s_last[WAVES_PER_BLOCK];
 	const int64_t t = (int64_t)blockIdx.x;
 	const int64_t j = t * BLOCK + threadIdx.x;
 	const uint64_t s_pre[3] = {scalar_load(ts.clusters + t), scalar_load(ts.cig + t), scalar_load(ts.bytes + t)}; // (scanned: k_scan_sums_lists)
@@ -198,12 +228,35 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_cols3_tiles(PackArgs p, Pack3
 		key = s.key;
 		run_start = j == 0 || (p.c.skey[j - 1] >> 32) != (key >> 32);
 	}
-	const SlotWords sw = slot_words(p, s);
+	SlotWords sw = slot_words(p, s);
 	const bool lng = sw.lng;
+	// the narrow wire form: which clusters keep their operations out of the CIGAR stream, and the key of the cluster before in the tile (keys ascend: it is
+	// the last one among the lanes below, else the last one of the nearest wavefront below that has any); prev = that key + 1, 0: the tile's first cluster
+	uint32_t kind = 0;
+	uint64_t prev = 0;
+	if (q.wire) {
+		if (s.cluster) {
+			kind = wire_cigar_kind(s.ncg, s.cg0, s.cg1, s.ll, s.lr);
+			sw.cnt = 1ull | ((uint64_t)(kind ? 0u : (uint32_t)s.ncg) << 16) | ((uint64_t)(uint32_t)s.ncg << 40); // per tile: clusters (9 bits), stream operations, all operations (24 bits each)
+		}
+		const uint64_t cm = __ballot(s.cluster), below = cm & lanemask_lt();
+		const uint64_t k_below = __shfl(key, below ? 63 - __clzll((long long)below) : 0, WAVE), k_last = __shfl(key, cm ? 63 - __clzll((long long)cm) : 0, WAVE);
+		if (below) prev = k_below + 1;
+		if (lane_id() == 0) s_last[wave_id()] = cm ? k_last + 1 : 0;
+	}
 	uint64_t tot_cnt, tot_bytes;
-	const uint64_t ex_cnt = block_exclusive_sum(sw.cnt, lds, &tot_cnt);
+	uint64_t ex_cnt = block_exclusive_sum(sw.cnt, lds, &tot_cnt); // (its barriers also publish s_last)
 	const uint64_t ex_bytes = block_exclusive_sum(sw.bytes, lds, &tot_bytes);
-	if (threadIdx.x == 0 && t == (int64_t)gridDim.x - 1) { tot[0] = (s_pre[0] + (tot_cnt & 0xffffffffull)) | ((s_pre[1] + (tot_cnt >> 32)) << 32); tot[1] = s_pre[2] + tot_bytes; }
+	if (q.wire) {
+		for (int w = wave_id() - 1; w >= 0 && !prev; --w) prev = s_last[w];
+		if (threadIdx.x == 0) {
+			if (!(tot_cnt & 0xffffull)) q.pos_esc[t] = ~0ull;
+			if (t == (int64_t)gridDim.x - 1) *q.ops_total = (uint32_t)((s_pre[0] >> 32) + (tot_cnt >> 40));
+		}
+		tot_cnt = (tot_cnt & 0xffffull) | (((tot_cnt >> 16) & 0xffffffull) << 32);
+		ex_cnt = (ex_cnt & 0xffffull) | (((ex_cnt >> 16) & 0xffffffull) << 32);
+	}
+	if (threadIdx.x == 0 && t == (int64_t)gridDim.x - 1) { tot[0] = ((s_pre[0] & 0xffffffffull) + (tot_cnt & 0xffffffffull)) | ((s_pre[1] + (tot_cnt >> 32)) << 32); tot[1] = s_pre[2] + tot_bytes; }
 	if (j >= p.c.E) return;
 	const uint32_t c = (uint32_t)(s_pre[0] + (ex_cnt & 0xffffffffull));
 	if (run_start) { // first slot of a (contig, side): the next cluster at or after it starts the run
@@ -216,17 +269,36 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_cols3_tiles(PackArgs p, Pack3
 	s.cig_off = s_pre[1] + (ex_cnt >> 32);
 	s.str_off = s_pre[2] + ex_bytes;
 	if (!s.single || lng) { p.slot_cnt[j] = (uint64_t)c | (s.cig_off << 32); p.slot_bytes[j] = s.str_off; } // (the base-by-base kernel finds its clusters by slot: k_pack3_slow)
-	q.pos[c] = (int32_t)(uint32_t)s.key;
-	if (q.len_bytes == 2) reinterpret_cast<uint32_t *>(q.len)[c] = (uint32_t)s.ll | ((uint32_t)s.lr << 16);
-	else reinterpret_cast<uint2 *>(q.len)[c] = make_uint2((uint32_t)s.ll, (uint32_t)s.lr);
-	if (q.support_bytes == 2) {
-		if (s.support > 0xffff) *q.support_miss = 1;
-		reinterpret_cast<uint16_t *>(q.support)[c] = (uint16_t)s.support;
-	} else reinterpret_cast<uint32_t *>(q.support)[c] = (uint32_t)s.support;
-	if (q.ncig_bytes == 1) reinterpret_cast<uint8_t *>(q.ncig)[c] = (uint8_t)s.ncg;
-	else reinterpret_cast<uint16_t *>(q.ncig)[c] = (uint16_t)s.ncg;
+	if (q.wire) {
+		const uint32_t pos = (uint32_t)s.key;
+		uint32_t d = WIRE_ESC;
+		if (prev && ((prev - 1) >> 32) == (s.key >> 32)) d = min(pos - (uint32_t)(prev - 1), WIRE_ESC);
+		if (!prev) q.pos_esc[t] = ((uint64_t)c << 32) | pos;
+		else if (d == WIRE_ESC) { // (a run's first cluster, a gap of 65535 bases or more: a handful per contig)
+			const uint32_t k = atomicAdd(q.pos_esc_count, 1u);
+			if (k < q.pos_esc_cap) q.pos_esc[(uint64_t)gridDim.x + k] = ((uint64_t)c << 32) | pos;
+			else *q.wire_miss = 1;
+		}
+		if ((uint32_t)s.ll > WIRE_LEN_MAX || (uint32_t)s.lr > WIRE_LEN_MAX || (uint32_t)s.support > WIRE_SUPPORT_MAX || (uint32_t)s.ncg > WIRE_NCIG_MAX) *q.wire_miss = 1;
+		uint16_t *rw = reinterpret_cast<uint16_t *>(q.row + c);
+		rw[0] = (uint16_t)d;
+		rw[1] = (uint16_t)(((uint32_t)s.ll & 0xffu) | (((uint32_t)s.lr & 0xffu) << 8));
+		rw[2] = (uint16_t)(((uint32_t)s.support & 0xffu) | ((((uint32_t)s.ncg & WIRE_NCIG_MAX) | (kind << WIRE_NCIG_BITS)) << 8));
+	} else {
+		q.pos[c] = (int32_t)(uint32_t)s.key;
+		if (q.len_bytes == 2) reinterpret_cast<uint32_t *>(q.len)[c] = (uint32_t)s.ll | ((uint32_t)s.lr << 16);
+		else reinterpret_cast<uint2 *>(q.len)[c] = make_uint2((uint32_t)s.ll, (uint32_t)s.lr);
+		if (q.support_bytes == 2) {
+			if (s.support > 0xffff) *q.support_miss = 1;
+			reinterpret_cast<uint16_t *>(q.support)[c] = (uint16_t)s.support;
+		} else reinterpret_cast<uint32_t *>(q.support)[c] = (uint32_t)s.support;
+		if (q.ncig_bytes == 1) reinterpret_cast<uint8_t *>(q.ncig)[c] = (uint8_t)s.ncg;
+		else reinterpret_cast<uint16_t *>(q.ncig)[c] = (uint16_t)s.ncg;
+	}
 	if (!s.single) q.flags[c] = s.qmiss_multi ? 1 : 0;
-	if (q.cig_bytes == 2) {
+	if (kind) {
+		// (its two operations are the row's two lengths)
+	} else if (q.cig_bytes == 2) {
 		uint16_t *dc = reinterpret_cast<uint16_t *>(out_cig) + s.cig_off;
 		uint32_t wide = 0;
 		if (s.ncg <= 5) {

@@ -313,6 +313,12 @@ class Context:
         self._check(self._lib.ssv_clip_table_expand(self._h, C.byref(t), int(n_threads)), "ssv_clip_table_expand")
         return t
 
+    def clip_table_wire_bytes(self, t):
+        """what really crossed PCIe for the handed-out table t (ssv_clip_table_wire_bytes) -> dict: narrow, total and the pieces"""
+        w = _abi.TableWire()
+        self._check(self._lib.ssv_clip_table_wire_bytes(self._h, C.byref(t), C.byref(w)), "ssv_clip_table_wire_bytes")
+        return {k: int(getattr(w, k)) for k, _ in _abi.TableWire._fields_ if k != "pad"}
+
     def clip_scan_range(self, batch, rec_begin, rec_end):
         b, keep = self._as_batch(batch)
         self._check(self._lib.ssv_clip_scan_range(self._h, C.byref(b), int(rec_begin), int(rec_end)), "ssv_clip_scan_range")
