@@ -27,7 +27,7 @@ $(LIBDIR)/libseeksv_hip.so: $(HIP_DEPS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIP_SRC)
 
 # the `seeksv` command line (getclip / getsv) over the two libraries
-seeksv_amd/bin/seeksv: seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.cpp seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.cpp seeksv_amd/host/somatic_stage.h $(LIBDIR)/libseeksv_host.so $(LIBDIR)/libseeksv_hip.so
+seeksv_amd/bin/seeksv: seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.cpp seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.cpp seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.cpp seeksv_amd/host/somatic_stage.h $(LIBDIR)/libseeksv_host.so $(LIBDIR)/libseeksv_hip.so
 	mkdir -p seeksv_amd/bin
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -Iinclude -o $@ seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp -L$(LIBDIR) -lseeksv_host -lseeksv_hip -lz \
 		-Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath-link,$(ROCM)/lib
@@ -60,6 +60,7 @@ asan: $(LIBDIR)/libseeksv_hip.so
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iinclude -o $(ASAN_DIR)/seeksv seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp \
 		-L$(ASAN_DIR) -lseeksv_host -lseeksv_hip -lz -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,$(ROCM)/lib
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Iseeksv_amd/csrc tests/native/inflate_check.cpp -lz -o $(ASAN_DIR)/inflate_check && $(ASAN_DIR)/inflate_check
+	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/fastq_reads_check.cpp -o $(ASAN_DIR)/fastq_reads_check && $(ASAN_DIR)/fastq_reads_check
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so):$$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0 SSV_CLEAN_EXIT=1 \
 		SSV_TEST_CXXFLAGS="$(ASAN_FLAGS)" SSV_LIBDIR=$(abspath $(ASAN_DIR)) SSV_ORACLE_SO=$(abspath $(ASAN_DIR))/liboracle.so SSV_CLI=$(abspath $(ASAN_DIR))/seeksv \
 		python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider

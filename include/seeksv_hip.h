@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
+                             v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
                              v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
                              v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
                              v9 (additive, same version): ssv_aln_pack, ssv_aln_cols (getsv: the clipped-sequence re-alignments as SAM text).
@@ -692,6 +693,24 @@ int ssv_realign_query_alts(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_o
  * are not gap-refined; on the hash index the candidates of a query with more than 192 seeds and a tie between two contigs are the lanes' choice as before.
  * Arguments and errors as ssv_realign_query; mates[n] (host) is required (NULL: SSV_E_ARG).  n == 0: SSV_OK. */
 int ssv_realign_query_split(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, ssv_realign_hit *hits, ssv_realign_hit *mates);
+/* ssv_realign_query_split + its records, built on the device (`seeksv run -P`): what `seeksv realign -P` writes into its BAM, as an SSV_MEM_DEVICE batch of the
+ * kind ssv_samdec_decode hands out - hot columns, cigar_ends, record lines, every CIGAR operation, every record's packed bases + qualities, 8 readable bytes
+ * behind seqqual, n_tid_runs = 0, max_ref_span = 1024 - which ssv_rt_scan (of any context on the same GPU) takes in place.  *out and *out_names are owned by
+ * the context and stay valid until its next ssv_realign_* call.  hits[n] and mates[n] (host, both required) are bit for bit ssv_realign_query_split's.
+ *   quals      NULL, or seq_off[n] bytes: read i's qualities (phred + 33) at seq_off[i], as long as its bases
+ *   names      read i's NUL-terminated name at names + name_off[i]; name_off[n] = the bytes of names.  *out_names is the uploaded blob; a read's two records
+ *              share one offset
+ *   rows       read i gives one record, and a second one directly behind it when mates[i].tid >= 0; row order is read order.  flag 0 / 16 / 4, | 2048 on the
+ *              mate's record; mapq the hit's (0 when unaligned); tid / pos the hit's or -1 / -1; l_qseq = L; mtid = mpos = -1; isize = 0; xc = 0; CIGAR q_beg S
+ *              (when > 0), (q_end - q_beg) M, (L - q_end) S (when > 0) - none, and cigar_ends 0xff, when unaligned.  Bases: A C G T in either case 1 2 4 8, every
+ *              other byte 15; a flag-16 record holds the reversed complement and the reversed qualities; the low nibble behind an odd L is 0.  Qualities:
+ *              byte - 33, 0xff throughout when quals is NULL.  Reads shorter than 20 or longer than 1024 bases are unaligned records with all their bases.
+ *              seq_off values are the library's choice (every record's bytes start dword aligned).
+ * Errors as ssv_realign_query_split; SSV_E_ARG also for a NULL names, name_off, out or out_names and - found on the host before anything is launched - for a
+ * name of 0 or more than 254 bytes; SSV_E_STATE before an index is built; n == 0: SSV_OK and out->n == 0.  Synchronises the stream.  Timed as `realign_rows`
+ * (the query itself: `realign_query`). */
+int ssv_realign_split_batch(ssv_ctx *ctx, const char *seqs, const uint64_t *seq_off, int64_t n, const char *quals, const char *names, const uint64_t *name_off,
+                            ssv_realign_hit *hits, ssv_realign_hit *mates, ssv_batch_t *out, ssv_names_t *out_names);
 int ssv_realign_free(ssv_ctx *ctx);
 
 /* ---- getsv -F: junctions from read-through split alignments: replaces FindJunction (process_bwasw.cpp:5-227, seeksv.cpp:221-225) -----------

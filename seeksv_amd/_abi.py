@@ -394,6 +394,7 @@ def hip_lib():
         lib.ssv_realign_query_gapped.argtypes = [V, V, V, C.c_int64, V, V]
         lib.ssv_realign_query_alts.argtypes = [V, V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V]
         lib.ssv_realign_query_split.argtypes = [V, V, V, C.c_int64, V, V]
+        lib.ssv_realign_split_batch.argtypes = [V, V, V, C.c_int64, V, V, V, V, V, C.POINTER(Batch), C.POINTER(Names)]
         lib.ssv_realign_free.argtypes = [V]
         lib.ssv_prof_enable.argtypes = [V, C.c_int]
         lib.ssv_prof_reset.argtypes = [V]

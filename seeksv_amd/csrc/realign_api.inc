@@ -1,9 +1,12 @@
-// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h, realign_gap_kernels.h, realign_alts_kernels.h and realign_split_kernels.h)
+// realign_api.inc - C ABI of the clipped-sequence re-aligner (included by seeksv_hip.hip; kernels in realign_kernels.h, realign_sorted_kernels.h, realign_gap_kernels.h, realign_alts_kernels.h, realign_split_kernels.h and realign_rows_kernels.h)
 
 struct ssv_realign_state {
 	DBuf ref, ctg, table, seqs, offs, hits, gaps, dropped;
 	DBuf alts, alt_n, alt_off, alt_sums, alt_dense; // ssv_realign_query_alts: strided hits and counts, their scan, the dense list
 	DBuf mates; // ssv_realign_query_split: one hit per query
+	// ssv_realign_split_batch: qualities and names as uploaded, per read its records / operations / seqqual bytes and their scans, the batch handed out
+	DBuf quals, names, name_off, row_n, op_n, sq_n, row_at, op_at, sq_at, rows_small, row_name, row_rec;
+	DecodedColumns row_cols;
 	DBuf skeys, svals, sdir; // the sorted index (ssv_realign_index_sorted); a context holds one kind of index at a time
 	bool sorted = false;
 	int32_t dir_bits = 0, max_occ = 0;
@@ -228,6 +231,68 @@ int ssv_realign_query_split(ssv_ctx *c, const char *seqs, const uint64_t *seq_of
 {
 	if (!mates) return SSV_E_ARG;
 	return realign_query(c, seqs, seq_off, n, hits, nullptr, false, "ssv_realign_query_split", 0, nullptr, nullptr, mates);
+}
+
+// The split query as it stands, then its reads, hits and mates as the records `seeksv realign -P` writes - built on the device, handed out as a device batch
+// (realign_rows_kernels.h): sizes per read, three scans, one read-back of the totals, the rows.
+int ssv_realign_split_batch(ssv_ctx *c, const char *seqs, const uint64_t *seq_off, int64_t n, const char *quals, const char *names, const uint64_t *name_off,
+                            ssv_realign_hit *hits, ssv_realign_hit *mates, ssv_batch_t *out, ssv_names_t *out_names)
+{
+	if (!c) return SSV_E_ARG;
+	if (!names || !name_off || !out || !out_names || !hits || !mates) { c->err = "ssv_realign_split_batch: names, name_off, hits, mates, out and out_names are required"; return SSV_E_ARG; }
+	if (n > ((int64_t)1 << 30)) { c->err = "ssv_realign_split_batch: more than 2^30 reads in one call"; return SSV_E_ARG; }
+	for (int64_t i = 0; i < n; ++i) { // (with its NUL a name is 2..255 bytes)
+		const uint64_t a = name_off[i], b = name_off[i + 1];
+		if (b < a + 2 || b - a > 255) { c->err = "ssv_realign_split_batch: read " + std::to_string(i) + ": a name is 1..254 bytes"; return SSV_E_ARG; }
+	}
+	CHECK(realign_query(c, seqs, seq_off, n, hits, nullptr, false, "ssv_realign_split_batch", 0, nullptr, nullptr, mates));
+	memset(out, 0, sizeof(*out)); memset(out_names, 0, sizeof(*out_names));
+	out->mem = SSV_MEM_DEVICE; out->max_ref_span = RA_MAX_Q;
+	out_names->mem = SSV_MEM_DEVICE;
+	if (n == 0) return SSV_OK;
+	ssv_realign_state &R = *c->ra;
+	hipStream_t st = c->st;
+	const size_t N = (size_t)n;
+	const uint64_t seq_bytes = seq_off[n], name_bytes = name_off[n];
+	if (quals) { CHECK(ensure(c, R.quals, seq_bytes + 16)); HIPCHECK(c, hipMemcpyAsync(R.quals.p, quals, seq_bytes, hipMemcpyHostToDevice, st)); }
+	CHECK(ensure(c, R.names, name_bytes + 16)); CHECK(ensure(c, R.name_off, (N + 1) * 8));
+	HIPCHECK(c, hipMemcpyAsync(R.names.p, names, name_bytes, hipMemcpyHostToDevice, st));
+	HIPCHECK(c, hipMemsetAsync(P<char>(R.names) + name_bytes, 0, 16, st));
+	HIPCHECK(c, hipMemcpyAsync(R.name_off.p, name_off, (N + 1) * 8, hipMemcpyHostToDevice, st));
+	for (DBuf *b : {&R.row_n, &R.op_n, &R.sq_n, &R.row_at, &R.op_at}) CHECK(ensure(c, *b, N * 4 + 16));
+	CHECK(ensure(c, R.sq_at, N * 8 + 16)); CHECK(ensure(c, R.rows_small, 64));
+	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n) * 8 + 64)); CHECK(ensure(c, c->scan_scratch64, (size_t)scan_scratch_elems(n) * 8 + 64));
+	// R.rows_small: [0] records, [1] operations, [2..3] seqqual bytes u64
+	uint32_t *sm = P<uint32_t>(R.rows_small);
+	{
+		ProfScope ps(c, P_REALIGN_ROWS, n);
+		k_rr_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(P<uint64_t>(R.offs), P<RaHit>(R.hits), P<RaHit>(R.mates), n, P<uint32_t>(R.row_n), P<uint32_t>(R.op_n), P<uint32_t>(R.sq_n));
+		exclusive_scan<uint32_t, uint32_t>(st, P<uint32_t>(R.row_n), P<uint32_t>(R.row_at), n, 0u, P<uint32_t>(c->scan_scratch), sm);
+		exclusive_scan<uint32_t, uint32_t>(st, P<uint32_t>(R.op_n), P<uint32_t>(R.op_at), n, 0u, P<uint32_t>(c->scan_scratch), sm + 1);
+		exclusive_scan<uint32_t, uint64_t>(st, P<uint32_t>(R.sq_n), P<uint64_t>(R.sq_at), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 2));
+	}
+	HIPCHECK(c, hipGetLastError());
+	uint32_t tot[4];
+	HIPCHECK(c, hipMemcpyAsync(tot, R.rows_small.p, 16, hipMemcpyDeviceToHost, st));
+	HIPCHECK(c, hipStreamSynchronize(st));
+	const size_t rows = tot[0], ops = tot[1];
+	uint64_t sq_total;
+	memcpy(&sq_total, tot + 2, 8);
+	if (rows < N || rows > 2 * N || ops > 3 * rows) { c->err = "ssv_realign_split_batch: the sizes do not add up"; return SSV_E_STATE; }
+	CHECK(R.row_cols.reserve(c, rows, 1.0)); CHECK(R.row_cols.reserve_variable(c, ops, (size_t)sq_total, 1.0)); // (64 bytes of slack behind seqqual: 8 must be readable)
+	CHECK(ensure(c, R.row_rec, rows * sizeof(ssv_record) + 64)); CHECK(ensure(c, R.row_name, rows * 8 + 16));
+	const RaRowsArgs a{P<char>(R.seqs), quals ? P<char>(R.quals) : nullptr, P<uint64_t>(R.offs), P<uint64_t>(R.name_off), P<RaHit>(R.hits), P<RaHit>(R.mates), n,
+	                   P<uint32_t>(R.row_at), P<uint32_t>(R.op_at), P<uint64_t>(R.sq_at)};
+	{
+		ProfScope ps(c, P_REALIGN_ROWS, (int64_t)rows);
+		k_rr_rows<<<grid_for(n, WAVES_PER_BLOCK), BLOCK, 0, st>>>(a, R.row_cols.view(), P<ssv_record>(R.row_rec), P<uint64_t>(R.row_name));
+	}
+	HIPCHECK(c, hipGetLastError());
+	HIPCHECK(c, hipStreamSynchronize(st));
+	R.row_cols.fill(out, (int64_t)rows, (int64_t)ops, (int64_t)sq_total);
+	out->rec = P<ssv_record>(R.row_rec);
+	out_names->base = P<char>(R.names); out_names->off = P<uint64_t>(R.row_name); out_names->bytes = (int64_t)name_bytes;
+	return SSV_OK;
 }
 
 int ssv_realign_free(ssv_ctx *c)

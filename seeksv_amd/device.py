@@ -461,6 +461,25 @@ class Context:
         self._check(self._lib.ssv_realign_query_split(self._h, C.c_char_p(blob), off.ctypes.data, n, hits.ctypes.data, mates.ctypes.data), "ssv_realign_query_split")
         return hits, mates[:n]
 
+    def realign_split_batch(self, seqs, names, quals=None):
+        """realign_split() + the records `seeksv realign -P` writes, built on the GPU (ssv_realign_split_batch).  seqs, names (and quals: phred + 33, as
+        long as their reads): lists of str -> (hits, mates, Batch, Names); the batch and its names are SSV_MEM_DEVICE, owned by the context and valid until
+        its next realign call: rt_scan() takes them in place, batch_to_host() / aln_pack() copy them out.  A read with a mate gives two records."""
+        n = len(seqs)
+        if len(names) != n or (quals is not None and [len(x) for x in quals] != [len(x) for x in seqs]):
+            raise ValueError("realign_split_batch: one name per read, qualities as long as their reads")
+        blob, off, hits = self._realign_io(seqs)
+        mates = np.zeros(max(n, 1), dtype=np.dtype(_abi.REALIGN_HIT))
+        hits = hits if n else np.zeros(1, dtype=np.dtype(_abi.REALIGN_HIT))
+        raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        nblob = b"".join(x + b"\0" for x in raw)
+        noff = np.concatenate([[0], np.cumsum([len(x) + 1 for x in raw])]).astype(np.uint64)
+        qblob = C.c_char_p("".join(quals).encode()) if quals is not None else None
+        b, nm = _abi.Batch(), _abi.Names()
+        self._check(self._lib.ssv_realign_split_batch(self._h, C.c_char_p(blob), off.ctypes.data, n, qblob, C.c_char_p(nblob), noff.ctypes.data, hits.ctypes.data,
+                                                      mates.ctypes.data, C.byref(b), C.byref(nm)), "ssv_realign_split_batch")
+        return hits[:n], mates[:n], b, nm
+
     # ---- measurement ----
     def prof_enable(self, mode=1):
         self._check(self._lib.ssv_prof_enable(self._h, mode), "ssv_prof_enable")

@@ -4,6 +4,9 @@
 //
 //   seeksv getclip [-t f] [-q n] [-s] [-o prefix] in.sorted.bam
 //   seeksv getsv   [options] clip.bam in.sorted.bam clip.gz out.sv out.unmapped.clip.fq
+//   seeksv run     [-P] [-c "getclip options"] [-v "getsv options"] [-a "realign options"] in.sorted.bam ref.fa prefix
+//                  (getclip, realign and getsv in one process, one decode; -P: the unmapped pairs split-aligned on the way and handed to the -F pass
+//                  as a device batch - run_split_leg, ssv_realign_split_batch)
 //
 // getsv: junctions come from `-B <table>` (ReadBreakpoint, getsv.cpp:1292) and / or from the join of clip.gz with clip.bam
 // (junction_stage.cpp); the BAM passes run on the GPU; OutputBreakpoint's filter chain and columns are reproduced here.
@@ -44,6 +47,7 @@
 #include "sam_text.h"
 #include "somatic_stage.h"
 #include "unmapped_pairs.h"
+#include "fastq_reads.h"
 #include "../csrc/thp.h"
 #include "seeksv_hip.h"
 #include "seeksv_host.h"
@@ -274,6 +278,9 @@ struct ResidentBam {
 		vector<string> names;
 	} aln;
 	std::thread bam_writer;      // clip.bam of `seeksv run`, written beside getsv
+	// `seeksv run -P`: the text of prefix.unmapped_1.fq / _2.fq as the side channel's sinks wrote it, piece by piece in file order (whole records each)
+	bool keep_unmapped = false;
+	std::deque<string> unmapped[2];
 };
 static ResidentBam g_resident;
 
@@ -895,7 +902,10 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 
 	// unmapped-pair side channel, StoreUnmapSeqAndQual (clip_reads.h:172-219): paired up, turned into FASTQ text and compressed by threads of its own
 	// (unmapped_pairs.h); this thread hands every batch's raw UNMAP|MUNMAP records over by pointer
-	seeksv::UnmappedPairs unmapped([&](vector<string> &parts) { fuout1.write_parts(parts); }, [&](vector<string> &parts) { fuout2.write_parts(parts); },
+	auto keep_text = [](int end, vector<string> &parts) { // (both sinks are called by one thread, and a piece is nobody's once it is written)
+		if (g_resident.keep_unmapped) for (string &s : parts) if (!s.empty()) g_resident.unmapped[end].push_back(std::move(s));
+	};
+	seeksv::UnmappedPairs unmapped([&](vector<string> &parts) { fuout1.write_parts(parts); keep_text(0, parts); }, [&](vector<string> &parts) { fuout2.write_parts(parts); keep_text(1, parts); },
 	                               std::max(1, std::min(8, ssv::effective_cpus() / 2)));
 	// The flush sequence (clip_reads.h:428-438, :442): the reference writes out and clears its two maps at every change of contig among the
 	// mapped-pair records.  A pass of the library bins by (contig, side, position), which is the same thing as long as every contig of the
@@ -1233,6 +1243,8 @@ static void resident_alignments(seeksv::AlnRecords &R); // `seeksv run`: the ali
 // A BAM goes through the same readers as the original BAM (host threads, or the GPU with -Z); SAM text is always parsed on the GPU (ssv_samdec_*), whatever -Z
 // says.  Selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
 static const char *kRtOpenError = "[main_samview] fail to open file for reading.";
+// `seeksv run -P`: the -F pass without a file - the unmapped pairs split-aligned in this process, their records handed over on the device (run_split_leg)
+static std::function<void(ssv_ctx *, int, JunctionMap &)> g_run_split_leg;
 
 static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx)
 {
@@ -1443,6 +1455,11 @@ static int cmd_getsv(int argc, char **argv)
 		readthrough_pass(connect_bam, min_mapQ2, rt_ctx, device_inflate, junction2other);
 		cerr << "'FindJunction' finished" << endl;
 		pt.lap("readthrough (-F)");
+	} else if (g_run_split_leg) { // `seeksv run -P`: at the same place, with -w as its floor
+		rt_ctx = acquire_ctx(device);
+		g_run_split_leg(rt_ctx, min_mapQ2, junction2other);
+		cerr << "'FindJunction' finished" << endl;
+		pt.lap("readthrough (run -P: split alignments of the unmapped pairs, device rows)");
 	}
 	{ // InputSoftInfoStoreBreakpoint + GetJunction (getsv.h:423, getsv.cpp:1705): clip clusters x re-alignments of their clipped sequences
 		string err;
@@ -2236,9 +2253,10 @@ static void build_realign_index(ssv_ctx *ctx, const Reference &R, int max_occ, i
 	if (rc != SSV_OK) die(string("[seeksv] realign index: ") + ssv_last_error(ctx));
 }
 
-static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped, int max_alt, bool split = false)
+// (n_queries >= 0: the number of sequences, where the records were never laid out on the host - `seeksv run -P`)
+static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_occ, bool gapped, int max_alt, bool split = false, int64_t n_queries = -1)
 {
-	string t = "[seeksv realign] " + to_string(A.size() - A.n_secondary - A.n_split) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
+	string t = "[seeksv realign] " + to_string(n_queries >= 0 ? n_queries : A.size() - A.n_secondary - A.n_split) + " clipped sequences, " + to_string(A.n_aligned) + " aligned";
 	if (gapped) t += ", " + to_string(A.n_gapped) + " with a gap";
 	if (!max_occ) t += dropped ? ", " + to_string(dropped) + " repetitive index positions dropped" : string();
 	else t += (A.n_masked ? ", " + to_string(A.n_masked) + " with repetitive seeds masked" : string()) + (A.n_over ? ", " + to_string(A.n_over) + " over the candidate limit" : string());
@@ -2332,6 +2350,8 @@ struct RunAligner {
 	int max_occ = 0; // -a "-c INT": the sorted index
 	bool gapped = false; // -a "-g"
 	int max_alt = 0; // -a "-S INT": secondary records
+	bool keep_index = false; // `seeksv run -P`: context and index outlive the thread, for the split leg (release_index)
+	ssv_ctx *kept_ctx = nullptr;
 	double t_index = 0, t_align = 0, t_wait_ref = 0;
 	void start(int device, const string &fasta)
 	{
@@ -2367,9 +2387,17 @@ struct RunAligner {
 				t_align += std::chrono::duration<double>(now() - t0).count();
 			}
 			A.seqqual.resize(A.seqqual.size() + 16, 0);
+			if (keep_index) { ssv_sync(ctx); kept_ctx = ctx; return; }
 			ssv_realign_free(ctx);
 			if (kCleanExit) ssv_ctx_destroy(ctx); else ssv_sync(ctx);
 		});
+	}
+	void release_index()
+	{
+		if (!kept_ctx) return;
+		ssv_realign_free(kept_ctx);
+		if (kCleanExit) ssv_ctx_destroy(kept_ctx); else ssv_sync(kept_ctx);
+		kept_ctx = nullptr;
 	}
 	void submit(const vector<ResidentBam::Piece *> &pass)
 	{
@@ -2383,6 +2411,103 @@ struct RunAligner {
 		th.join();
 	}
 };
+
+// `seeksv run -P`: what `cat prefix.unmapped_1.fq.gz prefix.unmapped_2.fq.gz | seeksv realign -P ref.fa - prefix.F.bam` and the -F pass of `seeksv getsv -F
+// prefix.F.bam` do, without the file: the reads - file 1's, then file 2's, out of the text the side channel's sinks kept - go through the aligner's index in
+// pieces of SSV_REALIGN_SPLIT_PIECE reads (1 << 22; tests make it small), ssv_realign_split_batch lays every piece's records out in HBM, and the -F pass of
+// the getsv context scans them there (same GPU, same process; the call has synchronised).  A read's two records lie in one piece.  Called by cmd_getsv
+// where it runs its -F pass; ssv_rt_finish and the fold into the junction map as there.
+static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, JunctionMap &junction2other)
+{
+	ssv_ctx *actx = aligner.kept_ctx;
+	if (!actx) die("[seeksv] run -P: the aligner's index is gone");
+	rt_begin_for(aligner.R.names, min_mapq, rt_ctx);
+	static const int64_t piece = [] { const char *e = getenv("SSV_REALIGN_SPLIT_PIECE"); const long long v = e ? atoll(e) : 0; return v > 0 ? (int64_t)v : (int64_t)1 << 22; }();
+	seeksv::FastqReads reads;
+	vector<ssv_realign_hit> hits, mates;
+	AlignedRecords S; // (the counts of the closing line only)
+	int64_t n_reads = 0;
+	double t_cut = 0, t_align = 0, t_scan = 0;
+	auto now = [] { return std::chrono::steady_clock::now(); };
+	auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+	auto flush = [&] {
+		const int64_t n = reads.n();
+		if (!n) return;
+		const auto t0 = now();
+		hits.resize((size_t)n); mates.resize((size_t)n);
+		ssv_batch_t b;
+		ssv_names_t nm;
+		if (ssv_realign_split_batch(actx, reads.seqs.data(), reads.seq_off.data(), n, reads.quals.data(), reads.names.data(), reads.name_off.data(), hits.data(), mates.data(), &b, &nm) != SSV_OK)
+			die(string("[seeksv] realign query: ") + ssv_last_error(actx));
+		const auto t1 = now();
+		if (ssv_rt_scan(rt_ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx));
+		if (ssv_sync(rt_ctx) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx)); // (the next piece overwrites the batch)
+		t_align += secs(t0, t1); t_scan += secs(t1, now());
+		for (int64_t i = 0; i < n; ++i) {
+			const ssv_realign_hit &h = hits[(size_t)i];
+			S.n_aligned += h.tid >= 0 ? 1 : 0; S.n_split += mates[(size_t)i].tid >= 0 ? 1 : 0;
+			S.n_masked += (h.pad[0] & SSV_RA_F_MASKED) ? 1 : 0; S.n_over += (h.pad[0] & SSV_RA_F_OVERFLOW) ? 1 : 0;
+		}
+		n_reads += n;
+		reads.clear();
+	};
+	// the texts are cut side by side, a group of them at a time (every one holds whole records), and put together into pieces in their order
+	vector<string *> texts;
+	for (auto &file : g_resident.unmapped) for (string &text : file) texts.push_back(&text);
+	const size_t group = (size_t)std::max(1, std::min(ssv::effective_cpus(), 32));
+	for (size_t g = 0; g < texts.size(); g += group) {
+		const auto t0 = now();
+		const size_t m = std::min(group, texts.size() - g);
+		vector<seeksv::FastqReads> part(m);
+		vector<string> errs(m);
+		auto cut = [&](size_t k) { // (room first - the strings do not grow while they are filled -, on huge pages where they are large enough for that)
+			const string &text = *texts[g + k];
+			seeksv::FastqReads &r = part[k];
+			r.seqs.reserve(text.size() / 2); r.quals.reserve(text.size() / 2); r.names.reserve(text.size() / 8);
+			ssv::thp_advise(r.seqs.data(), r.seqs.capacity()); ssv::thp_advise(r.quals.data(), r.quals.capacity()); ssv::thp_advise(r.names.data(), r.names.capacity());
+			if (seeksv::fastq_all(text.data(), text.size(), r, errs[k]) >= 0) errs[k].clear();
+			string().swap(*texts[g + k]);
+		};
+		{
+			vector<std::thread> th;
+			for (size_t k = 1; k < m; ++k) th.emplace_back(cut, k);
+			cut(0);
+			for (auto &x : th) x.join();
+		}
+		{ // room in the piece for what the group holds (the piece's buffers are kept from piece to piece)
+			size_t sb = 0, nb = 0;
+			int64_t nr = 0;
+			for (const auto &r : part) { sb += r.seqs.size(); nb += r.names.size(); nr += r.n(); }
+			if (reads.seqs.capacity() < reads.seqs.size() + sb) {
+				reads.seqs.reserve(reads.seqs.size() + sb); reads.quals.reserve(reads.quals.size() + sb); reads.names.reserve(reads.names.size() + nb);
+				reads.seq_off.reserve(reads.seq_off.size() + (size_t)nr); reads.name_off.reserve(reads.name_off.size() + (size_t)nr);
+				ssv::thp_advise(reads.seqs.data(), reads.seqs.capacity()); ssv::thp_advise(reads.quals.data(), reads.quals.capacity()); ssv::thp_advise(reads.names.data(), reads.names.capacity());
+			}
+		}
+		for (size_t k = 0; k < m; ++k) if (!errs[k].empty()) die("[seeksv] run -P: " + errs[k] + " among the unmapped pairs");
+		t_cut += secs(t0, now());
+		for (size_t k = 0; k < m; ++k) {
+			for (int64_t i0 = 0, n = part[k].n(); i0 < n;) {
+				const auto t1 = now();
+				const int64_t take = std::min(n - i0, piece - reads.n());
+				seeksv::fastq_append_range(reads, part[k], i0, i0 + take);
+				i0 += take;
+				t_cut += secs(t1, now());
+				if (reads.n() == piece) flush();
+			}
+			part[k] = seeksv::FastqReads();
+		}
+	}
+	for (auto &file : g_resident.unmapped) file.clear();
+	flush();
+	ssv_rt_result res;
+	if (ssv_rt_finish(rt_ctx, &res) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx));
+	seeksv::apply_readthrough(res, aligner.R.names, junction2other);
+	cerr << realign_summary(S, aligner.dropped, aligner.max_occ, false, 0, true, n_reads) << endl;
+	if (getenv("SSV_TIMING")) cerr << "[timing] (run -P: " << n_reads << " reads, " << res.n_candidates << " candidates, " << res.n_pairs << " pairs; cutting the text " << t_cut << " s, split query + device rows "
+	                               << t_align << " s, -F scan " << t_scan << " s)" << endl;
+	aligner.release_index();
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // run: getclip -> realign -> getsv in one process (seeksv.cpp:128-329 + the pipeline's external aligner step, README.md:22-34)
@@ -2398,6 +2523,12 @@ struct RunAligner {
 	     << "Options: -c <string>           options handed to getclip, e.g. -c \"-q 5 -s\"\n"
 	     << "         -v <string>           options handed to getsv, e.g. -v \"-b 5 -L 100\"\n"
 	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500 -g -S 8\" (the GPU is chosen by -G here)\n"
+	     << "         -P                    also split-align the unmapped pairs (prefix.unmapped_1.fq.gz, then prefix.unmapped_2.fq.gz: whole reads, read name =\n"
+	     << "                               FASTQ name) on the aligner's index (-c of -a applies; ungapped, -g / -S of -a stay with the clipped sequences) and seed\n"
+	     << "                               junctions from their two-piece alignments as `getsv -F` does (-w of -v is its MAPQ floor): the table and stdout of\n"
+	     << "                               `seeksv realign -P` on the two files + `seeksv getsv -F`, from one decode.  The records are built on the GPU and stay\n"
+	     << "                               there: no prefix.F.bam is written (`seeksv realign -P` writes one); every other file is unchanged.  Not with -F in -v\n"
+	     << "                               or -N in -c.\n"
 	     << "         -G <int>              GPU ordinal [0]" << endl;
 	exit(1);
 }
@@ -2414,8 +2545,10 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0;
 	string clip_opts, sv_opts, aln_opts;
-	while ((c = getopt(argc, argv, "c:v:a:G:")) >= 0) {
+	bool split = false;
+	while ((c = getopt(argc, argv, "c:v:a:G:P")) >= 0) {
 		switch (c) {
+		case 'P': split = true; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
@@ -2438,6 +2571,23 @@ static int cmd_run(int argc, char **argv)
 		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped, &max_alt) != (int)aln_words.size()) usage_realign();
 		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
 	}
+	if (split) { // refused before anything is written: the pass has one source, and the ranks' getclip has another side channel
+		auto has_option = [](const string &opts, const char *optstring, int which) {
+			vector<string> w = {"x"};
+			for (auto &x : split_words(opts)) w.push_back(x);
+			vector<char *> av;
+			for (auto &x : w) av.push_back(const_cast<char *>(x.c_str()));
+			av.push_back(nullptr);
+			const int save = opterr;
+			opterr = 0; optind = 1;
+			bool found = false;
+			for (int o; (o = getopt((int)w.size(), av.data(), optstring)) >= 0;) found = found || o == which;
+			opterr = save; optind = 1;
+			return found;
+		};
+		if (has_option(sv_opts, "F:B:t:l:q:Q:w:n:a:b:d:e:m:i:R:f:T:L:rDG:J:ZCN:", 'F')) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
+		if (has_option(clip_opts, "t:q:o:sG:ZCN:H:", 'N')) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
+	}
 	PhaseTimer pt;
 	g_resident.ctx = acquire_ctx(device);
 	g_resident.path = bam;
@@ -2447,6 +2597,7 @@ static int cmd_run(int argc, char **argv)
 	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
 	RunAligner &aligner = *new RunAligner; // (never destroyed: die() may exit while its thread runs)
 	aligner.max_occ = max_occ; aligner.gapped = gapped; aligner.max_alt = max_alt;
+	aligner.keep_index = split; g_resident.keep_unmapped = split;
 	aligner.start(device, fasta);
 	g_resident.on_pass = [&aligner](const vector<ResidentBam::Piece *> &pass) { aligner.submit(pass); };
 	auto call = [&](int (*fn)(int, char **), vector<string> words) {
@@ -2474,11 +2625,14 @@ static int cmd_run(int argc, char **argv)
 		g_resident.bam_writer = std::thread([&aligner] { write_clip_bam(g_resident.aln.bam_path + ".tmp", aligner.R, aligner.A); });
 		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
 		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
+		if (split) g_run_split_leg = [&aligner](ssv_ctx *rt_ctx, int min_mapq, JunctionMap &jm) { run_split_leg(aligner, rt_ctx, min_mapq, jm); };
 		a = {"getsv"};
 		for (auto &w : split_words(sv_opts)) a.push_back(w);
 		a.insert(a.end(), {"-G", to_string(device), prefix + ".clip.bam", bam, prefix + ".clip.gz", prefix + ".sv.txt", prefix + ".unmapped.clip.fq"});
 		rc = call(cmd_getsv, a);
+		g_run_split_leg = nullptr;
 	}
+	aligner.release_index(); // (run -P whose getsv did not get as far as the leg)
 	pt.lap("run: getsv (records in HBM)");
 	if (g_resident.bam_writer.joinable()) {
 		g_resident.bam_writer.join();

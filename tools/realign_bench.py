@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The GPU re-aligner (ssv_realign_*) at the size of the bench workload: index of the whole synthetic genome (generated in
 HBM), then queries cut from it - half of them real placements (both strands, 0.5 % substitutions), half random sequence like the bulk of
-a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [--alts K [--family N]] [--split SHARE] [genome_frac] [n_queries] [query_len]
+a sample's soft clips.  usage: python tools/realign_bench.py [--index hash|sorted|both] [--max-occ N] [--rounds R] [--gapped] [--alts K [--family N]] [--split SHARE [--rows]] [genome_frac] [n_queries] [query_len]
 --gapped: half of the random queries give way to a third class, real placements that carry one insertion or deletion of 1-3 bases at least 12 bases
 from either end; every round then runs the set through ssv_realign_query and through ssv_realign_query_gapped (`seeksv realign -g`) and reports both.
 --alts K: every round also runs the set through ssv_realign_query_alts with max_alt K (`seeksv realign -S K`) and reports the query kernel, the scan and
@@ -11,6 +11,9 @@ fourth class: 60 bases of such an element; reported: how many come back with all
 --split SHARE: that share of the real placements become reads of two loci - their second half comes from another place of the reference, same substitutions,
 either strand -, and every round also runs the set through ssv_realign_query_split (`seeksv realign -P`): reported are the split query kernel's time beside the
 plain kernel's on the same set, how many planted splits come back at both planted places, and whether the primaries without a mate are the plain call's.
+--rows (with --split): every round also runs the set through ssv_realign_split_batch (`seeksv run -P`: the records built on the device) with names and
+qualities: reported are the `realign_rows` group (k_rr_sizes, three scans, k_rr_rows) beside `realign_query` of the same call, the batch's sizes, and whether hits
+and mates are the split call's.
 --index both builds and queries the two kinds of index in one process, alternating (hash, sorted, hash, sorted, ...), R times each: one JSON line
 with a list of rounds per kind.  Index bytes are computed from the sizes the library allocates, not measured."""
 import argparse
@@ -49,6 +52,7 @@ def main():
     ap.add_argument("--alts", type=int, default=0)
     ap.add_argument("--family", type=int, default=0)
     ap.add_argument("--split", type=float, default=0.0)
+    ap.add_argument("--rows", action="store_true")
     ap.add_argument("genome_frac", nargs="?", type=float, default=1.0)
     ap.add_argument("n_queries", nargs="?", type=int, default=2_000_000)
     ap.add_argument("query_len", nargs="?", type=int, default=60)
@@ -58,6 +62,8 @@ def main():
         ap.error("--family needs --alts and queries of at most 60 bases")
     if args.split and (not 0 < args.split <= 1 or qlen < 60):
         ap.error("--split needs a share in (0, 1] and queries of at least 60 bases (two pieces of 30)")
+    if args.rows and not args.split:
+        ap.error("--rows needs --split")
     import torch
     w = synth.Workload(genome_frac=frac, depth=1, n_sv=0)
     t = time.perf_counter()
@@ -136,6 +142,11 @@ def main():
     lut = np.frombuffer(b"ACGT", np.uint8)
     text = lut[allc].tobytes().decode()
     seqs = [text[i * qlen:(i + 1) * qlen] for i in range(nq)]
+    if args.rows:   # names like getclip's, qualities of forty values
+        r = np.random.RandomState(16)
+        qtext = (33 + r.randint(2, 42, nq * qlen)).astype(np.uint8).tobytes().decode()
+        quals = [qtext[i * qlen:(i + 1) * qlen] for i in range(nq)]
+        names = [f"read{i}/{1 + (i & 1)}" for i in range(nq)]
     is_split = order < n_split
     is_real = (order < n_real) & ~is_split
     exp_tid = np.full(nq, -1)
@@ -223,6 +234,19 @@ def main():
                                 plain_call_split_reads_mapq0=int((plain["mapq"] == 0)[is_split & (plain["tid"] >= 0)].sum()),
                                 real_with_mate=int(has[is_real].sum()), junk_with_mate=int(has[is_junk].sum()),
                                 primaries_without_mate_equal_plain=bool(h3[~has].tobytes() == plain[~has].tobytes()))
+        if args.rows:   # ... and once more with their records built on the device
+            ctx.prof_reset()
+            t = time.perf_counter()
+            h4, m4, b, _ = ctx.realign_split_batch(seqs, names, quals)
+            t_query = time.perf_counter() - t
+            prof = ctx.prof_all()
+            r_ms = prof["realign_rows"]["total_ms"]
+            n_rec, n_ops, sq = int(b.n), int(b.n_cigar_total), int(b.seqqual_bytes)
+            written = n_rec * (64 + 4 + 4 + 2 + 1 + 2 + 1 + 1 + 4 + 4 + 4 + 4 + 4 + 8 + 4 + 8) + n_ops * 4 + sq   # line, columns, name offset; operations; bases + qualities
+            out["rows"] = dict(call_wall_s=round(t_query, 3), query_kernel_ms=round(prof["realign_query"]["total_ms"], 2), rows_kernels_ms=round(r_ms, 3),
+                               rows_launch_groups=int(prof["realign_rows"]["launches"]), records=n_rec, cigar_operations=n_ops, seqqual_bytes=sq,
+                               bytes_written=written, bytes_read=2 * nq * qlen + 64 * nq, GB_per_s=round((written + 2 * nq * qlen + 64 * nq) / (r_ms * 1e-3) / 1e9, 1),
+                               reads_per_s_rows_kernels=round(nq / (r_ms * 1e-3)), hits_and_mates_equal_split_call=bool(h4.tobytes() == h3.tobytes() and m4.tobytes() == mates.tobytes()))
         if args.gapped:   # the same queries once more, with gaps
             at_locus = (hits["tid"] == exp_tid) & (hits["mapq"] > 0)
             out["ungapped_gap_class_at_its_contig"] = int(at_locus[is_gap].sum())
