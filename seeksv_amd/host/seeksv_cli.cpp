@@ -4,9 +4,9 @@
 //
 //   seeksv getclip [-t f] [-q n] [-s] [-o prefix] in.sorted.bam
 //   seeksv getsv   [options] clip.bam in.sorted.bam clip.gz out.sv out.unmapped.clip.fq
-//   seeksv run     [-P] [-c "getclip options"] [-v "getsv options"] [-a "realign options"] in.sorted.bam ref.fa prefix
+//   seeksv run     [-P] [-N n [-G d0,d1,...]] [-c "getclip options"] [-v "getsv options"] [-a "realign options"] in.sorted.bam ref.fa prefix
 //                  (getclip, realign and getsv in one process, one decode; -P: the unmapped pairs split-aligned on the way and handed to the -F pass
-//                  as a device batch - run_split_leg, ssv_realign_split_batch)
+//                  as a device batch - run_split_leg, ssv_realign_split_batch; -N: the decode and the records over n GPUs - RunRanks, ranks_tally)
 //
 // getsv: junctions come from `-B <table>` (ReadBreakpoint, getsv.cpp:1292) and / or from the join of clip.gz with clip.bam
 // (junction_stage.cpp); the BAM passes run on the GPU; OutputBreakpoint's filter chain and columns are reproduced here.
@@ -166,7 +166,8 @@ static void release_ctx(ssv_ctx *ctx);
 	     << "         -l <int>              Maximum search length to find microhomology [30]\n"
 	     << "         -m <int>              Minimum length of the clipped sequence  in normal [10]\n"
 	     << "         -n <int>              Number of read pairs used to calculate insert size [5000000]; < 100000 switches the insert-size pass off\n"
-	     << "         -G <int>              GPU ordinal [0]\n"
+	     << "         -G <int>[,<int>...]   GPU ordinal(s) [0; with -N: all GPUs of the machine in order]\n"
+	     << "         -N <int>              cut the normal BAM into N runs of records, one per GPU; the ranks' tallies meet in one RCCL all-gather [1]\n"
 	     << "         -Z                    inflate and decode the BAM on the GPU (compressed blocks over PCIe) instead of on the host threads" << endl
 	     << "         -C                    with -Z: check every BGZF block's CRC32 on the GPU (off: like libbam 0.1.16, which checks none)" << endl;
 	exit(1);
@@ -1041,6 +1042,32 @@ struct ClipRank {
 	string err;
 };
 
+// `seeksv run -N n`: what the ranks' getclip leaves behind for the getsv pass of the same process - per rank its context (alive after rank_main) and the
+// batches of its OWN run, copied into that context's memory (ssv_batch_retain, 80 B a record; the halo is scanned and forgotten), and the cuts of the file
+// both steps share.  cmd_run owns all of it and lets go of it at its end.  A batch is only ever scanned by the context that holds it.
+struct RunRank {
+	ssv_ctx *ctx = nullptr;      // (rank 0: the context acquire_ctx hands to the later steps of the process)
+	int device = 0;
+	vector<ssv_batch_t> batches; // in file order
+	int64_t kept = 0;            // records in them
+};
+struct RunRanks {
+	string path;                 // the file these are the records of
+	vector<ssvh_bam_part> parts;
+	vector<RunRank> rank;
+	bool fell_back = false;      // contigs that come back: the ranks gave way to getclip_single, nothing of theirs is left
+	void release() // every batch, and every context but rank 0's (the process's own)
+	{
+		for (size_t r = 0; r < rank.size(); ++r) {
+			RunRank &k = rank[r];
+			if (k.ctx) for (auto &b : k.batches) ssv_batch_release(k.ctx, &b);
+			k.batches.clear(); k.kept = 0;
+			if (r > 0 && k.ctx) { ssv_ctx_destroy(k.ctx); k.ctx = nullptr; }
+		}
+	}
+};
+static RunRanks *g_run_ranks = nullptr; // set by cmd_run around its getclip and getsv steps
+
 static int getclip_ranks(const string &bamfile, const string &prefix, double threshold, int min_mapQ, bool save_low_quality, int n_ranks, const vector<int> &devices, int halo_bp, bool device_inflate)
 {
 	PhaseTimer pt;
@@ -1057,11 +1084,16 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 	pt.lap("open+partition");
 	const int32_t n_targets = ssvh_bam_n_targets(bam);
 	vector<ClipRank> R((size_t)n_ranks);
+	// `seeksv run -N`: the ranks' contexts and the records of their own runs outlive this function
+	RunRanks *const keep = g_run_ranks && g_run_ranks->path == bamfile && (int)g_run_ranks->rank.size() == n_ranks ? g_run_ranks : nullptr;
+	if (keep) keep->parts = parts;
 	auto rank_main = [&](int r) {
 		ClipRank &out = R[(size_t)r];
 		const ssvh_bam_part &P = parts[(size_t)r];
-		ssv_ctx *ctx = nullptr;
-		if (ssv_ctx_create(device_of_rank(r, devices), &ctx) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(nullptr); return; }
+		ssv_ctx *ctx = keep ? keep->rank[(size_t)r].ctx : nullptr;
+		if (!ctx && ssv_ctx_create(device_of_rank(r, devices), &ctx) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(nullptr); return; }
+		if (keep) keep->rank[(size_t)r].ctx = ctx;
+		auto drop_ctx = [&] { if (!keep) ssv_ctx_destroy(ctx); }; // (kept: the run lets go of it)
 		ssv_clip_params p;
 		memset(&p, 0, sizeof(p));
 		p.match_rate = threshold; p.min_mapq = min_mapQ; p.save_low_quality = save_low_quality ? 1 : 0;
@@ -1072,10 +1104,10 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 		p.own_lo_tid = r == 0 ? 0 : P.own_tid; p.own_lo_pos = r == 0 ? 0 : P.own_pos;
 		if (r + 1 < n_ranks) { p.own_hi_tid = parts[(size_t)r + 1].own_tid; p.own_hi_pos = parts[(size_t)r + 1].own_tid < n_targets ? parts[(size_t)r + 1].own_pos : 0; }
 		else { p.own_hi_tid = INT32_MAX; p.own_hi_pos = 0; }
-		if (ssv_clip_begin(ctx, &p) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(ctx); ssv_ctx_destroy(ctx); return; }
+		if (ssv_clip_begin(ctx, &p) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(ctx); drop_ctx(); return; }
 		ssv_clip_table_format(ctx, table_format_default());
 		ssvh_bam *rb = nullptr; // (the header: contig names for the rows)
-		if (ssvh_bam_open(bamfile.c_str(), &rb) != 0) { out.err = "[main_samview] fail to open file for reading."; ssv_ctx_destroy(ctx); return; }
+		if (ssvh_bam_open(bamfile.c_str(), &rb) != 0) { out.err = "[main_samview] fail to open file for reading."; drop_ctx(); return; }
 		// the contig of the last mapped-pair record before the rank's OWN run (its run list continues from there)
 		out.last_tid = r == 0 ? 0 : P.before_own_tid;
 		for (int phase = 0; phase < 2 && out.err.empty(); ++phase) { // 0: the halo (scanned, nothing else), 1: the rank's own records
@@ -1089,7 +1121,15 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 				if (phase != 1) return;
 				src.for_each_unmapped([&](const char *qname, const char *seq, const char *qual, int is_read1) { out.unmapped.push_back(UnmappedRec{qname, seq, qual, is_read1}); });
 				src.contig_runs(b, out.last_tid, out.run_tids);
-			}, [&](const ssv_batch_t &b) { if (out.err.empty() && ssv_clip_scan(ctx, &b) != SSV_OK) out.err = string("[seeksv] ") + ssv_last_error(ctx); });
+			}, [&](const ssv_batch_t &decoded) {
+				if (!out.err.empty()) return;
+				ssv_batch_t b = decoded;
+				if (keep && phase == 1) { // the rank's own records stay in its GPU's memory for the getsv pass
+					if (ssv_batch_retain(ctx, &decoded, &b) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(ctx); return; }
+					keep->rank[(size_t)r].batches.push_back(b); keep->rank[(size_t)r].kept += b.n;
+				}
+				if (ssv_clip_scan(ctx, &b) != SSV_OK) out.err = string("[seeksv] ") + ssv_last_error(ctx);
+			});
 			src.close();
 		}
 		ssv_cluster_table t;
@@ -1105,7 +1145,7 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 			}
 		}
 		ssvh_bam_close(rb);
-		ssv_ctx_destroy(ctx);
+		drop_ctx();
 	};
 	{
 		vector<std::thread> th;
@@ -1128,6 +1168,12 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 			// Contigs that come back: the ranks' intervals of (contig, position) mean nothing for such a file.  The reference's result - one
 			// flush per visit of a contig (clip_reads.h:428-438) - comes from the single-GPU path, which ends a pass at every such visit.
 			ssvh_bam_close(bam);
+			if (keep) { // `seeksv run -N`: from here on the run is `seeksv run` on the first device - one context, which keeps every record
+				keep->release();
+				keep->fell_back = true;
+				cerr << "[seeksv] run -N: contigs come back in " << bamfile << ", the ranks give way to one GPU (as `seeksv run` without -N)" << endl;
+				g_resident.collect = true;
+			}
 			return getclip_single(bamfile, prefix, threshold, min_mapQ, save_low_quality, device_of_rank(0, devices), device_inflate);
 		}
 	// unmapped-pair side channel, StoreUnmapSeqAndQual (clip_reads.h:172-219): sequential over the file, i.e. over the ranks in order
@@ -1389,6 +1435,120 @@ static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, boo
 	seeksv::apply_readthrough(res, names, junction2other);
 }
 
+// ---- N runs of records, one per GPU: every rank scans its own records for ALL junctions and windows; the partial tallies, depth sums
+//      and point depths of the ranks meet in one all-gather (RCCL over xGMI between different GPUs) and are added up.  A rank replays
+//      the records before its run through the pileup's read-cap bookkeeping first (ssv_getsv_prime). ----
+// The one implementation behind `getsv -N`, `run -N` and `somatic -N`.  The callers differ in where a rank's records come from - its range of the file
+// (`resident` empty), or the batches its context already holds, scanned in place - and in which vectors they want (n_counts / n_ranges / n_points == 0: not
+// that one).  The replay's few thousand records are read from the file in either case.
+struct RanksTally {
+	string bam_path;
+	const vector<ssvh_bam_part> *parts = nullptr;       // the cuts (ssvh_bam_partition), one per rank
+	vector<ssv_ctx *> ctxs;                              // one per rank, the caller's
+	vector<const vector<ssv_batch_t> *> resident;        // per rank: the retained batches of ITS context, in file order; empty: file ranges
+	bool device_inflate = false;
+	ssv_getsv_params gp;                                 // junctions, windows, thresholds, contig lengths
+	bool depth = false;                                  // windows are scanned: a rank's pileup state is replayed
+	const ssv_interval *ranges = nullptr, *points = nullptr;
+	size_t n_counts = 0, n_ranges = 0, n_points = 0;
+	int32_t *counts = nullptr; uint64_t *range_sum = nullptr; int32_t *point_depth = nullptr; // the ranks' sums are added to these
+};
+
+static void ranks_tally(const RanksTally &T)
+{
+	const int n_ranks = (int)T.ctxs.size();
+	const string &original_bam = T.bam_path;
+	const bool device_inflate = T.device_inflate, output_depth = T.depth;
+	vector<ssv_ctx *> ctxs = T.ctxs;
+	ssv_group *group = nullptr;
+	if (ssv_group_create(ctxs.data(), n_ranks, &group) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
+	const size_t n_cnt = T.n_counts, n_rs = T.n_ranges, n_pd = T.n_points;
+	const size_t vec_bytes = n_rs * 8 + (n_cnt + n_pd + 2) * 4; // [range sums u64 | counts i32 | point depths i32 | max depth, pad]
+	vector<string> errs((size_t)n_ranks);
+	vector<vector<uint8_t>> gathered((size_t)n_ranks);
+	auto rank_main = [&](int r) {
+		string &err = errs[(size_t)r];
+		ssv_ctx *rc = ctxs[(size_t)r];
+		const ssvh_bam_part &P = (*T.parts)[(size_t)r];
+		const ssv_getsv_params &gp = T.gp;
+		ssvh_bam *rb = nullptr;
+		if (ssvh_bam_open(original_bam.c_str(), &rb) != 0) { err = "[main_samview] fail to open file for reading."; }
+		// the pileup's state at the rank's first record: replay the records before it (more of them while the replay itself starts inside a
+		// > 8000x stack; back to the file's first record at most)
+		for (int64_t back = 24576; err.empty(); back *= 4) {
+			if (ssv_getsv_begin(rc, &gp) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
+			if (r == 0 || !output_depth || P.own_coff == UINT64_MAX) break;
+			uint64_t co; uint32_t uo; int64_t found = 0;
+			if (ssvh_bam_walk_back(original_bam.c_str(), P.own_coff, P.own_uoff, back, &co, &uo, &found) != 0) { err = string("[seeksv] ") + ssvh_partition_last_error(); break; }
+			if (found == 0) break;
+			int32_t sufficient = 1;
+			bool primed = false;
+			if (device_inflate && found <= (1 << 22)) {
+				// -Z: the replayed records are inflated and decoded on the rank's GPU like the run itself (one chunk: they are a few MB)
+				BatchSource rs;
+				rs.set_range(co, uo, P.own_coff, P.own_uoff);
+				rs.open(original_bam, rc, true, "[main_samview] fail to open file for reading.");
+				ssv_batch_t db, more;
+				if (rs.next(&db, 0)) {
+					if (ssv_getsv_prime(rc, &db, &sufficient) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); rs.close(); break; }
+					primed = !rs.next(&more, 0); // (a replay that spans chunks goes through the host reader below: the bookkeeping takes one batch)
+				}
+				rs.close();
+				if (!primed && ssv_getsv_begin(rc, &gp) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
+			}
+			if (!primed) {
+				if (ssvh_bam_set_range(rb, co, uo, P.own_coff, P.own_uoff) != 0) { err = string("[seeksv] ") + ssvh_last_error(); break; }
+				ssv_batch_t hb;
+				if (ssvh_bam_read_batch(rb, found + 16, 0, &hb) != 0) { err = string("[seeksv] ") + ssvh_last_error(); break; }
+				if (ssv_getsv_prime(rc, &hb, &sufficient) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
+			}
+			if (sufficient || found < back) break; // (found < back: the replay began at the file's first record - as far back as a replay can start)
+		}
+		auto scan = [&](const ssv_batch_t &b) { if (err.empty() && ssv_getsv_scan(rc, &b) != SSV_OK) err = string("[seeksv] ") + ssv_last_error(rc); };
+		if (err.empty() && !T.resident.empty()) { // the run itself: where the rank's getclip left it, in this context's memory
+			for (const ssv_batch_t &b : *T.resident[(size_t)r]) scan(b);
+		} else if (err.empty()) { // the run itself: host threads or the GPU (-Z) inflate and decode its blocks
+			BatchSource src;
+			src.set_range(P.own_coff, P.own_uoff, P.end_coff, P.end_uoff);
+			src.open(original_bam, rc, device_inflate, "[main_samview] fail to open file for reading.");
+			src.pump(0, [](const ssv_batch_t &) {}, scan);
+			src.close();
+		}
+		vector<uint8_t> mine(vec_bytes, 0);
+		uint64_t *v_rs = reinterpret_cast<uint64_t *>(mine.data());
+		int32_t *v_cnt = reinterpret_cast<int32_t *>(mine.data() + n_rs * 8), *v_pd = v_cnt + n_cnt, *v_max = v_pd + n_pd;
+		vector<int32_t> tmp_cnt(n_cnt + 1), tmp_pd(n_pd + 1);
+		vector<uint64_t> tmp_rs(n_rs + 1);
+		if (err.empty() && ssv_getsv_finish(rc, T.counts ? tmp_cnt.data() : nullptr, T.ranges, (int64_t)n_rs, tmp_rs.data(), T.points, (int64_t)n_pd, tmp_pd.data(), v_max) != SSV_OK)
+			err = string("[seeksv] ") + ssv_last_error(rc);
+		if (n_rs) memcpy(v_rs, tmp_rs.data(), n_rs * 8);
+		if (n_cnt) memcpy(v_cnt, tmp_cnt.data(), n_cnt * 4);
+		if (n_pd) memcpy(v_pd, tmp_pd.data(), n_pd * 4);
+		// the exchange: every rank takes part, also one that failed (its vector is zero; the error is reported afterwards)
+		gathered[(size_t)r].assign(vec_bytes * (size_t)n_ranks, 0);
+		if (ssv_group_allgather(group, r, mine.data(), vec_bytes, gathered[(size_t)r].data()) != SSV_OK && err.empty()) err = string("[seeksv] ") + ssv_last_error(rc);
+		if (rb) ssvh_bam_close(rb);
+	};
+	{
+		vector<std::thread> th;
+		for (int r = 1; r < n_ranks; ++r) th.emplace_back(rank_main, r);
+		rank_main(0);
+		for (auto &x : th) x.join();
+	}
+	for (auto &e : errs) if (!e.empty()) die(e);
+	// rank 0's copy of the gathered vectors: the sums are the whole file's tallies and depths
+	for (int r = 0; r < n_ranks; ++r) {
+		const uint8_t *v = gathered[0].data() + (size_t)r * vec_bytes;
+		const uint64_t *v_rs = reinterpret_cast<const uint64_t *>(v);
+		const int32_t *v_cnt = reinterpret_cast<const int32_t *>(v + n_rs * 8), *v_pd = v_cnt + n_cnt;
+		for (size_t k = 0; k < n_rs; ++k) T.range_sum[k] += v_rs[k];
+		for (size_t k = 0; k < n_cnt; ++k) T.counts[k] += v_cnt[k];
+		for (size_t k = 0; k < n_pd; ++k) T.point_depth[k] += v_pd[k];
+	}
+	if (getenv("SSV_TIMING")) cerr << "[timing] exchange over " << (ssv_group_uses_rccl(group) ? "RCCL (ncclAllGather)" : "host memory (ranks share a GPU)") << ", " << vec_bytes << " bytes per rank" << endl;
+	ssv_group_destroy(group);
+}
+
 static int cmd_getsv(int argc, char **argv)
 {
 	string connect_bam, temp_breakpoint, dump_junctions;
@@ -1537,104 +1697,36 @@ static int cmd_getsv(int argc, char **argv)
 	vector<int32_t> counts((size_t)nj + 1, 0), pdepth((size_t)np + 1, 0);
 	vector<uint64_t> rsum((size_t)nr + 1, 0);
 	if ((do_discordant || output_depth) && ranks_path) {
-		// ---- N runs of records, one per GPU: every rank scans its own records for ALL junctions and windows; the partial tallies, depth sums
-		//      and point depths of the ranks meet in one all-gather (RCCL over xGMI between different GPUs) and are added up.  A rank replays
-		//      the records before its run through the pileup's read-cap bookkeeping first (ssv_getsv_prime). ----
+		// ---- N runs of records, one per GPU (ranks_tally) ----
+		// `seeksv run -N`: the cuts getclip's ranks used, their contexts, and the records where those ranks left them; else the file is cut here and read
+		const RunRanks *const run = g_run_ranks && !g_run_ranks->fell_back && g_run_ranks->path == original_bam && (int)g_run_ranks->rank.size() == n_ranks && g_run_ranks->rank[0].ctx == ctx ? g_run_ranks : nullptr;
+		RanksTally T;
+		T.bam_path = original_bam;
 		vector<ssvh_bam_part> parts((size_t)n_ranks);
-		if (ssvh_bam_partition(original_bam.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
-		vector<ssv_ctx *> ctxs((size_t)n_ranks, nullptr);
-		ctxs[0] = ctx;
-		for (int r = 1; r < n_ranks; ++r) if (ssv_ctx_create(device_of_rank(r, devices), &ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
-		ssv_group *group = nullptr;
-		if (ssv_group_create(ctxs.data(), n_ranks, &group) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
-		const size_t n_cnt = do_discordant ? (size_t)nj : 0, n_rs = output_depth ? (size_t)nr : 0, n_pd = output_depth ? (size_t)np : 0;
-		const size_t vec_bytes = n_rs * 8 + (n_cnt + n_pd + 2) * 4; // [range sums u64 | counts i32 | point depths i32 | max depth, pad]
-		vector<string> errs((size_t)n_ranks);
-		vector<vector<uint8_t>> gathered((size_t)n_ranks);
-		auto rank_main = [&](int r) {
-			string &err = errs[(size_t)r];
-			ssv_ctx *rc = ctxs[(size_t)r];
-			const ssvh_bam_part &P = parts[(size_t)r];
-			ssv_getsv_params gp;
-			memset(&gp, 0, sizeof(gp));
-			gp.junctions = dj; gp.n_junctions = do_discordant ? nj : 0;
-			gp.mean = mean_insert_size; gp.sd = deviation; gp.times = times; gp.disc_min_mapq = min_mapQ;
-			gp.windows = dw; gp.n_windows = output_depth ? nw : 0; gp.depth_min_mapq = min_mapQ;
-			gp.n_targets = ssvh_bam_n_targets(bam); gp.target_len = ssvh_bam_target_lens(bam);
-			ssvh_bam *rb = nullptr;
-			if (ssvh_bam_open(original_bam.c_str(), &rb) != 0) { err = "[main_samview] fail to open file for reading."; }
-			// the pileup's state at the rank's first record: replay the records before it (more of them while the replay itself starts inside a
-			// > 8000x stack; back to the file's first record at most)
-			for (int64_t back = 24576; err.empty(); back *= 4) {
-				if (ssv_getsv_begin(rc, &gp) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
-				if (r == 0 || !output_depth || P.own_coff == UINT64_MAX) break;
-				uint64_t co; uint32_t uo; int64_t found = 0;
-				if (ssvh_bam_walk_back(original_bam.c_str(), P.own_coff, P.own_uoff, back, &co, &uo, &found) != 0) { err = string("[seeksv] ") + ssvh_partition_last_error(); break; }
-				if (found == 0) break;
-				int32_t sufficient = 1;
-				bool primed = false;
-				if (device_inflate && found <= (1 << 22)) {
-					// -Z: the replayed records are inflated and decoded on the rank's GPU like the run itself (one chunk: they are a few MB)
-					BatchSource rs;
-					rs.set_range(co, uo, P.own_coff, P.own_uoff);
-					rs.open(original_bam, rc, true, "[main_samview] fail to open file for reading.");
-					ssv_batch_t db, more;
-					if (rs.next(&db, 0)) {
-						if (ssv_getsv_prime(rc, &db, &sufficient) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); rs.close(); break; }
-						primed = !rs.next(&more, 0); // (a replay that spans chunks goes through the host reader below: the bookkeeping takes one batch)
-					}
-					rs.close();
-					if (!primed && ssv_getsv_begin(rc, &gp) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
-				}
-				if (!primed) {
-					if (ssvh_bam_set_range(rb, co, uo, P.own_coff, P.own_uoff) != 0) { err = string("[seeksv] ") + ssvh_last_error(); break; }
-					ssv_batch_t hb;
-					if (ssvh_bam_read_batch(rb, found + 16, 0, &hb) != 0) { err = string("[seeksv] ") + ssvh_last_error(); break; }
-					if (ssv_getsv_prime(rc, &hb, &sufficient) != SSV_OK) { err = string("[seeksv] ") + ssv_last_error(rc); break; }
-				}
-				if (sufficient || found < back) break; // (found < back: the replay began at the file's first record - as far back as a replay can start)
-			}
-			if (err.empty()) { // the run itself: host threads or the GPU (-Z) inflate and decode its blocks
-				BatchSource src;
-				src.set_range(P.own_coff, P.own_uoff, P.end_coff, P.end_uoff);
-				src.open(original_bam, rc, device_inflate, "[main_samview] fail to open file for reading.");
-				src.pump(0, [](const ssv_batch_t &) {}, [&](const ssv_batch_t &b) { if (err.empty() && ssv_getsv_scan(rc, &b) != SSV_OK) err = string("[seeksv] ") + ssv_last_error(rc); });
-				src.close();
-			}
-			vector<uint8_t> mine(vec_bytes, 0);
-			uint64_t *v_rs = reinterpret_cast<uint64_t *>(mine.data());
-			int32_t *v_cnt = reinterpret_cast<int32_t *>(mine.data() + n_rs * 8), *v_pd = v_cnt + n_cnt, *v_max = v_pd + n_pd;
-			vector<int32_t> tmp_cnt(n_cnt + 1), tmp_pd(n_pd + 1);
-			vector<uint64_t> tmp_rs(n_rs + 1);
-			if (err.empty() && ssv_getsv_finish(rc, do_discordant ? tmp_cnt.data() : nullptr, dr, (int64_t)n_rs, tmp_rs.data(), dp, (int64_t)n_pd, tmp_pd.data(), v_max) != SSV_OK)
-				err = string("[seeksv] ") + ssv_last_error(rc);
-			if (n_rs) memcpy(v_rs, tmp_rs.data(), n_rs * 8);
-			if (n_cnt) memcpy(v_cnt, tmp_cnt.data(), n_cnt * 4);
-			if (n_pd) memcpy(v_pd, tmp_pd.data(), n_pd * 4);
-			// the exchange: every rank takes part, also one that failed (its vector is zero; the error is reported afterwards)
-			gathered[(size_t)r].assign(vec_bytes * (size_t)n_ranks, 0);
-			if (ssv_group_allgather(group, r, mine.data(), vec_bytes, gathered[(size_t)r].data()) != SSV_OK && err.empty()) err = string("[seeksv] ") + ssv_last_error(rc);
-			if (rb) ssvh_bam_close(rb);
-		};
-		{
-			vector<std::thread> th;
-			for (int r = 1; r < n_ranks; ++r) th.emplace_back(rank_main, r);
-			rank_main(0);
-			for (auto &x : th) x.join();
+		if (run) T.parts = &run->parts;
+		else {
+			if (ssvh_bam_partition(original_bam.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
+			T.parts = &parts;
 		}
-		for (auto &e : errs) if (!e.empty()) die(e);
-		// rank 0's copy of the gathered vectors: the sums are the whole file's tallies and depths
-		for (int r = 0; r < n_ranks; ++r) {
-			const uint8_t *v = gathered[0].data() + (size_t)r * vec_bytes;
-			const uint64_t *v_rs = reinterpret_cast<const uint64_t *>(v);
-			const int32_t *v_cnt = reinterpret_cast<const int32_t *>(v + n_rs * 8), *v_pd = v_cnt + n_cnt;
-			for (size_t k = 0; k < n_rs; ++k) rsum[k] += v_rs[k];
-			for (size_t k = 0; k < n_cnt; ++k) counts[k] += v_cnt[k];
-			for (size_t k = 0; k < n_pd; ++k) pdepth[k] += v_pd[k];
+		T.ctxs.assign((size_t)n_ranks, nullptr);
+		T.ctxs[0] = ctx;
+		for (int r = 1; r < n_ranks; ++r) {
+			if (run) T.ctxs[(size_t)r] = run->rank[(size_t)r].ctx;
+			else if (ssv_ctx_create(device_of_rank(r, devices), &T.ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
 		}
-		if (getenv("SSV_TIMING")) cerr << "[timing] exchange over " << (ssv_group_uses_rccl(group) ? "RCCL (ncclAllGather)" : "host memory (ranks share a GPU)") << ", " << vec_bytes << " bytes per rank" << endl;
-		ssv_group_destroy(group);
-		for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(ctxs[(size_t)r]);
+		if (run) for (const RunRank &k : run->rank) T.resident.push_back(&k.batches);
+		T.device_inflate = device_inflate;
+		memset(&T.gp, 0, sizeof(T.gp));
+		T.gp.junctions = dj; T.gp.n_junctions = do_discordant ? nj : 0;
+		T.gp.mean = mean_insert_size; T.gp.sd = deviation; T.gp.times = times; T.gp.disc_min_mapq = min_mapQ;
+		T.gp.windows = dw; T.gp.n_windows = output_depth ? nw : 0; T.gp.depth_min_mapq = min_mapQ;
+		T.gp.n_targets = ssvh_bam_n_targets(bam); T.gp.target_len = ssvh_bam_target_lens(bam);
+		T.depth = output_depth;
+		T.ranges = dr; T.points = dp;
+		T.n_counts = do_discordant ? (size_t)nj : 0; T.n_ranges = output_depth ? (size_t)nr : 0; T.n_points = output_depth ? (size_t)np : 0;
+		T.counts = do_discordant ? counts.data() : nullptr; T.range_sum = rsum.data(); T.point_depth = pdepth.data();
+		ranks_tally(T);
+		if (!run) for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(T.ctxs[(size_t)r]);
 	} else if (do_discordant || output_depth) {
 		ssv_getsv_params gp;
 		memset(&gp, 0, sizeof(gp));
@@ -1735,24 +1827,27 @@ static int cmd_getsv(int argc, char **argv)
 
 static int cmd_somatic(int argc, char **argv)
 {
-	int offset = 30, c, min_len_of_clipped_seq = 10, read_pair_used = 5000000, min_mapQ = 20, device = 0;
+	int offset = 30, c, min_len_of_clipped_seq = 10, read_pair_used = 5000000, min_mapQ = 20, device = 0, n_ranks = 1;
 	double min_map_rate = 0.9;
 	string dump_lookups;
 	bool device_inflate = device_inflate_default();
+	vector<int> devices;
 	PhaseTimer pt;
-	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZC")) >= 0) {
+	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:")) >= 0) {
 		switch (c) {
 		case 't': min_map_rate = atof(optarg); break;
 		case 'q': min_mapQ = atoi(optarg); break;
 		case 'l': offset = atoi(optarg); break;
 		case 'm': min_len_of_clipped_seq = atoi(optarg); break;
 		case 'n': read_pair_used = atoi(optarg); break;
-		case 'G': device = atoi(optarg); break;
+		case 'G': devices = parse_devices(optarg); device = devices.empty() ? 0 : devices[0]; break;
 		case 'Z': device_inflate = true; break;
 		case 'C': g_verify_crc = true; break;
+		case 'N': n_ranks = atoi(optarg); break;
 		case 'J': dump_lookups = optarg; break; // test hook: the host look-ups only (no BAM pass, no GPU), one line per output row
 		}
 	}
+	if (n_ranks < 1) usage_somatic();
 	if (argc != optind + 4) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
 	else if (offset >= 90 || offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
 	const string normal_bam_file = argv[optind++], clipped_file = argv[optind++], tumor_file = argv[optind++], somatic_file = argv[optind++];
@@ -1785,7 +1880,10 @@ static int cmd_somatic(int argc, char **argv)
 	int mean_insert_size = 0, deviation = 0;
 	IsizeCarry carry;
 	string isize_report; // ReadsClipReads' warnings come first on the reference's stderr (seeksv.cpp:392-398): the lines wait for the loader
-	if (read_pair_used >= 100000) insert_size_pass(get_ctx, normal_bam_file, device_inflate, min_mapQ, read_pair_used, mean_insert_size, deviation, &carry, &isize_report);
+	// -N n: the tally over the normal BAM is split like `getsv -N`'s (SSV_GROUP_RCCL_ONE=1: `-N 1` takes that path too, through a one-rank RCCL communicator);
+	// the insert-size pass stays on rank 0, and leaves no open source behind - the ranks read their own ranges
+	const bool ranks_path = n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
+	if (read_pair_used >= 100000) insert_size_pass(get_ctx, normal_bam_file, device_inflate, min_mapQ, read_pair_used, mean_insert_size, deviation, ranks_path ? nullptr : &carry, &isize_report);
 	get_ctx();
 	pt.lap("isize_pass (+ what was left of the context's start-up)");
 
@@ -1822,22 +1920,37 @@ static int cmd_somatic(int argc, char **argv)
 		gp.mean = mean_insert_size; gp.sd = deviation; gp.times = times; gp.disc_min_mapq = min_mapQ;
 		gp.n_windows = 0; gp.depth_min_mapq = min_mapQ;
 		gp.n_targets = ssvh_bam_n_targets(bam); gp.target_len = ssvh_bam_target_lens(bam);
-		if (ssv_getsv_begin(ctx, &gp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		auto scan = [&](const ssv_batch_t &b) { if (ssv_getsv_scan(ctx, &b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); };
-		if (carry.usable) { // the insert-size pass left its source open behind the chunks it read, whose batches are still valid: ONE reading of the file
-			for (auto &k : carry.kept) { scan(k); if (carry.owned) ssv_batch_release(ctx, &k); }
-			carry.kept.clear();
-			carry.src.pump(0, [](const ssv_batch_t &) {}, scan);
-			carry.src.close();
-			carry.usable = false;
+		if (ranks_path) { // file ranges, counts only: no windows, hence nothing to replay
+			vector<ssvh_bam_part> parts((size_t)n_ranks);
+			if (ssvh_bam_partition(normal_bam_file.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
+			RanksTally T;
+			T.bam_path = normal_bam_file; T.parts = &parts;
+			T.ctxs.assign((size_t)n_ranks, nullptr);
+			T.ctxs[0] = ctx;
+			for (int r = 1; r < n_ranks; ++r) if (ssv_ctx_create(device_of_rank(r, devices), &T.ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
+			T.device_inflate = device_inflate;
+			T.gp = gp;
+			T.n_counts = (size_t)nj; T.counts = counts.data();
+			ranks_tally(T);
+			for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(T.ctxs[(size_t)r]);
 		} else {
-			BatchSource src; // a second handle: `bam` keeps serving the header
-			src.open(normal_bam_file, ctx, device_inflate, "[main_samview] fail to open file for reading.");
-			src.pump(0, [](const ssv_batch_t &) {}, scan);
-			src.close();
+			if (ssv_getsv_begin(ctx, &gp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+			auto scan = [&](const ssv_batch_t &b) { if (ssv_getsv_scan(ctx, &b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); };
+			if (carry.usable) { // the insert-size pass left its source open behind the chunks it read, whose batches are still valid: ONE reading of the file
+				for (auto &k : carry.kept) { scan(k); if (carry.owned) ssv_batch_release(ctx, &k); }
+				carry.kept.clear();
+				carry.src.pump(0, [](const ssv_batch_t &) {}, scan);
+				carry.src.close();
+				carry.usable = false;
+			} else {
+				BatchSource src; // a second handle: `bam` keeps serving the header
+				src.open(normal_bam_file, ctx, device_inflate, "[main_samview] fail to open file for reading.");
+				src.pump(0, [](const ssv_batch_t &) {}, scan);
+				src.close();
+			}
+			int32_t maxd = 0;
+			if (ssv_getsv_finish(ctx, counts.data(), nullptr, 0, nullptr, nullptr, 0, nullptr, &maxd) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 		}
-		int32_t maxd = 0;
-		if (ssv_getsv_finish(ctx, counts.data(), nullptr, 0, nullptr, nullptr, 0, nullptr, &maxd) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
 		vector<int32_t> prev(J.size() + 1, 0); // a row whose left contig is not in the normal's header reports 0
 		ssvh_plan_fold(plan, counts.data(), prev.data(), nullptr, nullptr, abnormal.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
 		ssvh_plan_destroy(plan);
@@ -2272,6 +2385,8 @@ static void resident_alignments(seeksv::AlnRecords &R)
 	R.cigar_off = A.cig_off.data(); R.cigar = A.cig.data(); R.qname = A.qn.data(); R.target_names = g_resident.aln.names;
 }
 
+static void read_fastq_lines(const string &fq, string &text, vector<Line> &seqs, vector<Line> &quals, vector<Line> *names_out);
+
 static int cmd_realign(int argc, char **argv)
 {
 	int gpu = 0, max_occ = 0, max_alt = 0;
@@ -2286,6 +2401,32 @@ static int cmd_realign(int argc, char **argv)
 	//      terminator: the sequences are the read names of the BAM records below) ----
 	vector<Line> seqs, quals, names; // (names: -P only)
 	string text;
+	read_fastq_lines(fq, text, seqs, quals, split ? &names : nullptr);
+	pt.lap("read fastq");
+	ssv_ctx *ctx = acquire_ctx(gpu);
+	int64_t dropped = 0;
+	build_realign_index(ctx, R, max_occ, &dropped);
+	pt.lap("index");
+	AlignedRecords A;
+	align_lines(ctx, seqs, quals, A, gapped, max_alt, split ? &names : nullptr);
+	pt.lap("align");
+	A.seqqual.resize(A.seqqual.size() + 16, 0);
+	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
+	// records, 1.6 x the bytes) unless SSV_BGZF_LEVEL asks for zlib
+	setenv("SSV_BGZF_LEVEL", "-1", 0);
+	write_clip_bam(out_bam, R, A);
+	pt.lap("write bam");
+	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt, split) << endl;
+	ssv_realign_free(ctx);
+	release_ctx(ctx);
+	return 0;
+}
+
+// A FASTQ file (its gzip members inflated side by side) as one text, cut into lines in place (the newline behind a line becomes its terminator); names != nullptr (-P):
+// the reads' names too.  `seeksv realign` and the aligner step of `seeksv run -N` read prefix.clip.fq.gz through this.
+static void read_fastq_lines(const string &fq, string &text, vector<Line> &seqs, vector<Line> &quals, vector<Line> *names_out)
+{
+	const bool split = names_out != nullptr;
 	{ const string err = seeksv::slurp_gz(fq, text); if (!err.empty()) die("Cannot open clipped reads file " + fq); }
 	{
 		char *base = text.empty() ? nullptr : &text[0];
@@ -2310,28 +2451,10 @@ static int cmd_realign(int argc, char **argv)
 				int k = 1;
 				while (k < l1.n && l1.p[k] != ' ' && l1.p[k] != '\t') ++k;
 				l1.p[k] = 0;
-				names.push_back(Line{l1.p + 1, k - 1});
+				names_out->push_back(Line{l1.p + 1, k - 1});
 			}
 		}
 	}
-	pt.lap("read fastq");
-	ssv_ctx *ctx = acquire_ctx(gpu);
-	int64_t dropped = 0;
-	build_realign_index(ctx, R, max_occ, &dropped);
-	pt.lap("index");
-	AlignedRecords A;
-	align_lines(ctx, seqs, quals, A, gapped, max_alt, split ? &names : nullptr);
-	pt.lap("align");
-	A.seqqual.resize(A.seqqual.size() + 16, 0);
-	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
-	// records, 1.6 x the bytes) unless SSV_BGZF_LEVEL asks for zlib
-	setenv("SSV_BGZF_LEVEL", "-1", 0);
-	write_clip_bam(out_bam, R, A);
-	pt.lap("write bam");
-	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt, split) << endl;
-	ssv_realign_free(ctx);
-	release_ctx(ctx);
-	return 0;
 }
 
 // `seeksv run`: the aligner step beside getclip.  A thread with a context of its own (a second stream on the same GPU) builds the index as soon as the
@@ -2342,7 +2465,8 @@ struct RunAligner {
 	std::thread th;
 	std::mutex mu;
 	std::condition_variable cv;
-	std::deque<vector<ResidentBam::Piece *>> todo;
+	struct Work { vector<ResidentBam::Piece *> pass; vector<Line> seqs, quals; }; // a pass of getclip's pieces, or (`run -N`) lines cut out of the finished FASTQ file
+	std::deque<Work> todo;
 	bool done = false;
 	Reference R;
 	AlignedRecords A;
@@ -2366,17 +2490,17 @@ struct RunAligner {
 			build_realign_index(ctx, R, max_occ, &dropped);
 			t_index = std::chrono::duration<double>(now() - t0).count();
 			for (;;) {
-				vector<ResidentBam::Piece *> pass;
+				Work work;
 				{
 					std::unique_lock<std::mutex> lk(mu);
 					cv.wait(lk, [this] { return !todo.empty() || done; });
 					if (todo.empty()) break;
-					pass.swap(todo.front());
+					work = std::move(todo.front());
 					todo.pop_front();
 				}
 				t0 = now();
-				vector<Line> seqs, quals;
-				for (ResidentBam::Piece *p : pass) {
+				vector<Line> &seqs = work.seqs, &quals = work.quals;
+				for (ResidentBam::Piece *p : work.pass) {
 					char *base = p->fq.empty() ? nullptr : &p->fq[0];
 					for (const ResidentBam::FqRef &r : p->reads) {
 						base[r.seq_off + r.seq_len] = 0; base[r.qual_off + r.qual_len] = 0; // (the newline behind a line becomes its terminator: the file is written)
@@ -2401,7 +2525,12 @@ struct RunAligner {
 	}
 	void submit(const vector<ResidentBam::Piece *> &pass)
 	{
-		{ std::lock_guard<std::mutex> lk(mu); todo.push_back(pass); }
+		{ std::lock_guard<std::mutex> lk(mu); todo.emplace_back(); todo.back().pass = pass; }
+		cv.notify_all();
+	}
+	void submit_lines(vector<Line> &seqs, vector<Line> &quals) // (the text they point into stays the caller's until finish())
+	{
+		{ std::lock_guard<std::mutex> lk(mu); todo.emplace_back(); todo.back().seqs.swap(seqs); todo.back().quals.swap(quals); }
 		cv.notify_all();
 	}
 	void finish()
@@ -2529,7 +2658,11 @@ static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, Ju
 	     << "                               `seeksv realign -P` on the two files + `seeksv getsv -F`, from one decode.  The records are built on the GPU and stay\n"
 	     << "                               there: no prefix.F.bam is written (`seeksv realign -P` writes one); every other file is unchanged.  Not with -F in -v\n"
 	     << "                               or -N in -c.\n"
-	     << "         -G <int>              GPU ordinal [0]" << endl;
+	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
+	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
+	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
+	     << "                               then take neither -N nor -G (-H inside -c sets the halo) [1]\n"
+	     << "         -G <int>[,<int>...]   GPU ordinal [0]; with -N: the ranks' GPUs [all GPUs of the machine in order]" << endl;
 	exit(1);
 }
 
@@ -2543,20 +2676,23 @@ static vector<string> split_words(const string &t)
 
 static int cmd_run(int argc, char **argv)
 {
-	int c, device = 0;
-	string clip_opts, sv_opts, aln_opts;
-	bool split = false;
-	while ((c = getopt(argc, argv, "c:v:a:G:P")) >= 0) {
+	int c, device = 0, n_ranks = 1;
+	string clip_opts, sv_opts, aln_opts, device_list;
+	bool split = false, ranks_given = false;
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:")) >= 0) {
 		switch (c) {
 		case 'P': split = true; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
-		case 'G': device = atoi(optarg); break;
+		case 'G': device = atoi(optarg); device_list = optarg; break; // (a list: its first GPU - the ranks' GPUs with -N)
+		case 'N': n_ranks = atoi(optarg); ranks_given = true; break;
 		default: usage_run();
 		}
 	}
-	if (argc != optind + 3) usage_run();
+	if (argc != optind + 3 || n_ranks < 1) usage_run();
+	const vector<int> devices = ranks_given ? parse_devices(device_list.c_str()) : vector<int>();
+	if (n_ranks > 1) device = device_of_rank(0, devices);
 	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
 	int max_occ = 0;
 	bool gapped = false;
@@ -2571,7 +2707,7 @@ static int cmd_run(int argc, char **argv)
 		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped, &max_alt) != (int)aln_words.size()) usage_realign();
 		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
 	}
-	if (split) { // refused before anything is written: the pass has one source, and the ranks' getclip has another side channel
+	{ // refused before anything is written
 		auto has_option = [](const string &opts, const char *optstring, int which) {
 			vector<string> w = {"x"};
 			for (auto &x : split_words(opts)) w.push_back(x);
@@ -2585,13 +2721,30 @@ static int cmd_run(int argc, char **argv)
 			opterr = save; optind = 1;
 			return found;
 		};
-		if (has_option(sv_opts, "F:B:t:l:q:Q:w:n:a:b:d:e:m:i:R:f:T:L:rDG:J:ZCN:", 'F')) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
-		if (has_option(clip_opts, "t:q:o:sG:ZCN:H:", 'N')) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
+		const char *const sv_optstring = "F:B:t:l:q:Q:w:n:a:b:d:e:m:i:R:f:T:L:rDG:J:ZCN:", *const clip_optstring = "t:q:o:sG:ZCN:H:";
+		// -P: the pass has one source, and the ranks' getclip has another side channel
+		if (split && ranks_given && n_ranks > 1) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N is not supported with it");
+		if (split && has_option(sv_opts, sv_optstring, 'F')) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
+		if (split && has_option(clip_opts, clip_optstring, 'N')) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
+		// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
+		if (n_ranks > 1 && (has_option(clip_opts, clip_optstring, 'N') || has_option(clip_opts, clip_optstring, 'G') || has_option(sv_opts, sv_optstring, 'N') || has_option(sv_opts, sv_optstring, 'G')))
+			die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
 	}
 	PhaseTimer pt;
 	g_resident.ctx = acquire_ctx(device);
 	g_resident.path = bam;
-	g_resident.collect = true;
+	// -N n: the ranks of getclip keep their own runs (RunRanks above); rank 0 is this process's context.  Until a file whose contigs come back sends the run down
+	// the one-GPU path (getclip_ranks), nothing is collected in g_resident.
+	const bool ranked = n_ranks > 1;
+	RunRanks &ranks = *new RunRanks; // (never destroyed: die() may exit while the ranks' threads run)
+	if (ranked) {
+		ranks.path = bam;
+		ranks.rank.resize((size_t)n_ranks);
+		for (int r = 0; r < n_ranks; ++r) ranks.rank[(size_t)r].device = device_of_rank(r, devices);
+		ranks.rank[0].ctx = g_resident.ctx;
+		g_run_ranks = &ranks;
+	}
+	g_resident.collect = !ranked;
 	pt.lap("run: gpu_init");
 	g_preread.path = fasta; g_preread.offs.assign(1, 0);
 	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
@@ -2609,14 +2762,46 @@ static int cmd_run(int argc, char **argv)
 	};
 	vector<string> a = {"getclip"};
 	for (auto &w : split_words(clip_opts)) a.push_back(w);
-	a.insert(a.end(), {"-Z", "-G", to_string(device), "-o", prefix, bam});
+	if (ranked) { // (without -G the ranks take the machine's GPUs in order, as under `getclip -N`)
+		a.insert(a.end(), {"-Z", "-N", to_string(n_ranks)});
+		if (!device_list.empty()) a.insert(a.end(), {"-G", device_list});
+		a.insert(a.end(), {"-o", prefix, bam});
+	} else a.insert(a.end(), {"-Z", "-G", to_string(device), "-o", prefix, bam});
 	int rc = call(cmd_getclip, a);
 	g_resident.collect = false;
 	g_resident.on_pass = nullptr;
 	pt.lap("run: getclip (decode once, records kept in HBM)");
+	const bool by_ranks = ranked && !ranks.fell_back; // (fell back: from here on this is `seeksv run` without -N)
+	if (!by_ranks) g_run_ranks = nullptr;
+	if (by_ranks && pt.on)
+		for (int r = 0; r < n_ranks; ++r)
+			cerr << "[timing] (run -N rank " << r << "/" << n_ranks << ": device " << ranks.rank[(size_t)r].device << ", " << ranks.rank[(size_t)r].kept << " records kept, "
+			     << ranks.parts[(size_t)r].halo_records << " halo records)" << endl;
+	string fq_text; // `run -N`: prefix.clip.fq.gz read back - the aligned records' read names point into it
+	if (by_ranks && rc == 0) { // the ranks' getclip hands no pass over while it runs: the aligner takes the finished file's sequences, as `seeksv realign` does
+		vector<Line> seqs, quals;
+		read_fastq_lines(prefix + ".clip.fq.gz", fq_text, seqs, quals, nullptr);
+		aligner.submit_lines(seqs, quals);
+	}
 	aligner.finish();
 	pt.lap("run: realign (what was left of it behind getclip)");
-	if (rc == 0) {
+	if (by_ranks && rc == 0) {
+		// the junction stage of getsv reads prefix.clip.gz and prefix.clip.bam back as files: clip.bam is written whole first (under a temporary name, renamed when it
+		// is whole), then the getsv step runs over the ranks' records where they lie
+		setenv("SSV_BGZF_LEVEL", "-1", 0);
+		const string clip_bam = prefix + ".clip.bam";
+		write_clip_bam(clip_bam + ".tmp", aligner.R, aligner.A);
+		if (rename((clip_bam + ".tmp").c_str(), clip_bam.c_str()) != 0) die("Cannot write file " + clip_bam);
+		pt.lap("run: clip.bam written");
+		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
+		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
+		a = {"getsv"};
+		for (auto &w : split_words(sv_opts)) a.push_back(w);
+		a.insert(a.end(), {"-Z", "-N", to_string(n_ranks)});
+		if (!device_list.empty()) a.insert(a.end(), {"-G", device_list});
+		a.insert(a.end(), {clip_bam, bam, prefix + ".clip.gz", prefix + ".sv.txt", prefix + ".unmapped.clip.fq"});
+		rc = call(cmd_getsv, a);
+	} else if (rc == 0) {
 		// clip.bam is read back by nobody in this process (getsv's join takes the records from memory): it is written beside getsv, by a thread that is joined below;
 		// its BGZF blocks are literal-only Huffman blocks (huff_gz.h) unless SSV_BGZF_LEVEL asks for zlib
 		setenv("SSV_BGZF_LEVEL", "-1", 0);
@@ -2640,6 +2825,9 @@ static int cmd_run(int argc, char **argv)
 		pt.lap("run: clip.bam written");
 	}
 	ssv_ctx *ctx = g_resident.ctx;
+	g_run_ranks = nullptr;
+	if (kCleanExit) ranks.release(); // (the ranks' batches, and every context but rank 0's - which is `ctx`)
+	else for (size_t r = 1; r < ranks.rank.size(); ++r) if (ranks.rank[r].ctx) ssv_sync(ranks.rank[r].ctx);
 	if (kCleanExit) {
 		for (auto &b : g_resident.batches) ssv_batch_release(ctx, &b);
 		g_resident.ctx = nullptr;
