@@ -9,6 +9,9 @@ HIPFLAGS = -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Iinclude -Wall -Wno-unus
 LIBDIR = seeksv_amd/lib
 HOST_SRC = seeksv_amd/host/bam_reader.cpp seeksv_amd/host/bam_partition.cpp seeksv_amd/host/getsv_plan.cpp
 HIP_SRC  = seeksv_amd/csrc/seeksv_hip.hip
+# the `seeksv` command line: its sources, and the headers only they include
+CLI_SRC  = seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp
+CLI_DEPS = seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.h
 HIP_DEPS = $(wildcard seeksv_amd/csrc/*.h) $(wildcard seeksv_amd/csrc/*.inc) $(wildcard seeksv_amd/csrc/*.hip) include/seeksv_hip.h
 
 all: host hip synth cli
@@ -27,9 +30,9 @@ $(LIBDIR)/libseeksv_hip.so: $(HIP_DEPS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIP_SRC)
 
 # the `seeksv` command line (getclip / getsv) over the two libraries
-seeksv_amd/bin/seeksv: seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.cpp seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.cpp seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.cpp seeksv_amd/host/somatic_stage.h $(LIBDIR)/libseeksv_host.so $(LIBDIR)/libseeksv_hip.so
+seeksv_amd/bin/seeksv: $(CLI_SRC) $(CLI_DEPS) $(LIBDIR)/libseeksv_host.so $(LIBDIR)/libseeksv_hip.so
 	mkdir -p seeksv_amd/bin
-	$(CXX) -O2 -std=c++17 -Wall -Wextra -Iinclude -o $@ seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp -L$(LIBDIR) -lseeksv_host -lseeksv_hip -lz \
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -Iinclude -o $@ $(CLI_SRC) -L$(LIBDIR) -lseeksv_host -lseeksv_hip -lz \
 		-Wl,-rpath,'$$ORIGIN/../lib' -Wl,-rpath-link,$(ROCM)/lib
 
 # synthetic BAM-record generator: the same source compiled for the GPU (bench) and for the CPU (tests, cpu baseline)
@@ -57,7 +60,7 @@ asan: $(LIBDIR)/libseeksv_hip.so
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -fPIC -Iinclude -shared -o $(ASAN_DIR)/libseeksv_synth_cpu.so seeksv_amd/csrc/synth_cpu.cpp
 	gcc $(ASAN_FLAGS) -std=c11 -Wall -Wextra -fPIC -shared -o $(ASAN_DIR)/liboracle.so oracle/seeksv_oracle.c -lm
 	cp $(LIBDIR)/libseeksv_hip.so $(ASAN_DIR)/
-	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iinclude -o $(ASAN_DIR)/seeksv seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp \
+	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iinclude -o $(ASAN_DIR)/seeksv $(CLI_SRC) \
 		-L$(ASAN_DIR) -lseeksv_host -lseeksv_hip -lz -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,$(ROCM)/lib
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Iseeksv_amd/csrc tests/native/inflate_check.cpp -lz -o $(ASAN_DIR)/inflate_check && $(ASAN_DIR)/inflate_check
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/fastq_reads_check.cpp -o $(ASAN_DIR)/fastq_reads_check && $(ASAN_DIR)/fastq_reads_check

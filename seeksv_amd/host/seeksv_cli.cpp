@@ -99,7 +99,7 @@ struct PhaseTimer {
 // only drained (SSV_CLEAN_EXIT=1 - sanitizer and leak-check runs - destroys it the long way, and main() returns instead of _exit).
 static const bool kCleanExit = getenv("SSV_CLEAN_EXIT") != nullptr;
 static bool g_verify_crc = false; // -C: the device decoder checks the CRC32 of every BGZF block it inflates
-static void release_ctx(ssv_ctx *ctx);
+static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); } // a library call that must not fail
 
 [[noreturn]] static void usage_top()
 {
@@ -255,13 +255,46 @@ template <class Side, class Scan> static string pump_host_batches(ssvh_bam *rb, 
 // memory of its own (ssv_batch_retain: hot columns, one 64-byte line per record, CIGARs, bases of the soft-clipped reads: 80 B/record -
 // a 30x genome is 50 GB of the GPU's 288); the getsv passes of the same process then find the file's records there instead of reading,
 // inflating and decoding the file a second and third time (the reference does: cluster.cpp:48, getsv.cpp:1067, bam2depth.h:29).
-struct ResidentBam {
-	string path;                 // the file these are the records of
-	ssv_ctx *ctx = nullptr;      // the context every command of the process shares
-	bool collect = false;        // getclip keeps what it decodes
+//
+// `seeksv run -N n`: what the ranks' getclip leaves behind for the getsv pass of the same process - per rank its context (alive after rank_main) and the
+// batches of its OWN run, copied into that context's memory (ssv_batch_retain, 80 B a record; the halo is scanned and forgotten), and the cuts of the file
+// both steps share.  A batch is only ever scanned by the context that holds it.
+struct RunRank {
+	ssv_ctx *ctx = nullptr;      // (rank 0: the context acquire_ctx hands to the later steps of the process)
+	int device = 0;
 	vector<ssv_batch_t> batches; // in file order
-	// what getclip wrote, still in memory for the steps that follow (the files are written all the same: they are outputs)
-	string clip_path, fq_path;   // prefix.clip.gz, prefix.clip.fq.gz
+	int64_t kept = 0;            // records in them
+};
+struct RunRanks {
+	vector<ssvh_bam_part> parts;
+	vector<RunRank> rank;        // (empty: a run without -N)
+	bool fell_back = false;      // contigs that come back: the ranks gave way to getclip_single, nothing of theirs is left
+	void release() // every batch, and every context but rank 0's (the process's own)
+	{
+		for (size_t r = 0; r < rank.size(); ++r) {
+			RunRank &k = rank[r];
+			if (k.ctx) for (auto &b : k.batches) ssv_batch_release(k.ctx, &b);
+			k.batches.clear(); k.kept = 0;
+			if (r > 0 && k.ctx) { ssv_ctx_destroy(k.ctx); k.ctx = nullptr; }
+		}
+	}
+};
+
+// `seeksv run`: the reference is read (and packed to 2 bits) by a thread of its own while getclip runs
+struct PrereadFasta {
+	std::thread th;
+	bool ok = false;
+	vector<string> names; vector<int32_t> lens; vector<int64_t> offs = vector<int64_t>(1, 0); vector<uint64_t> words;
+};
+
+// What the steps of one `seeksv run` hand to each other.  cmd_run owns the one session of the process (on the heap, never destroyed: die() may exit while
+// the ranks', the aligner's or the reference reader's threads run) and passes a pointer to the step bodies with the call that works on the run's own BAM;
+// stand-alone commands - and sources opened for any other file - pass nullptr.
+struct RunSession {
+	ssv_ctx *ctx = nullptr;      // the context every step of the run shares
+	bool collect = false;        // getclip_single keeps what it decodes (batches) and what it formats (pieces)
+	vector<ssv_batch_t> batches; // in file order
+	bool rows_kept = false;      // the pieces below are prefix.clip.gz / prefix.clip.fq.gz (the files are written all the same: they are outputs)
 	// their decompressed contents, in the pieces the formatting threads made (whole rows / whole records each; never glued together: appending 2.5 GB to
 	// one string on one thread was a second of `seeksv run`) - and, since round 6, what the formatter knew while it wrote them: every row as views into
 	// its text (the junction stage parsed 5.5 M rows back out of it: 0.35 s) and where every FASTQ record's sequence and qualities lie (the aligner
@@ -273,21 +306,23 @@ struct ResidentBam {
 	bool all_clean() const { for (const Piece &p : pieces) if (!p.clean) return false; return true; }
 	vector<seeksv::TextView> row_views() const { vector<seeksv::TextView> v; for (const Piece &p : pieces) v.push_back(seeksv::TextView{p.rows.data(), p.rows.size()}); return v; }
 	// what the aligner step made of the clipped sequences (clip.bam is written all the same); the read names point into the pieces' FASTQ text
-	struct Aligned {
-		string bam_path;
-		const struct AlignedRecords *rec = nullptr; // (the run's aligner thread owns them)
-		vector<string> names;
-	} aln;
+	struct Aligned { const struct AlignedRecords *rec = nullptr; vector<string> names; } aln; // (the run's aligner thread owns the records)
 	std::thread bam_writer;      // clip.bam of `seeksv run`, written beside getsv
 	// `seeksv run -P`: the text of prefix.unmapped_1.fq / _2.fq as the side channel's sinks wrote it, piece by piece in file order (whole records each)
 	bool keep_unmapped = false;
 	std::deque<string> unmapped[2];
+	std::function<void(ssv_ctx *, int, JunctionMap &)> split_leg; // ... and the -F pass without a file over them (run_split_leg), called where getsv runs its -F pass
+	// `seeksv run -N n`: the ranks of getclip keep their own runs; rank 0's context is `ctx`.  Nothing above is collected until a file whose contigs come
+	// back sends the run down the one-GPU path.
+	RunRanks ranks;
+	bool ranked() const { return !ranks.rank.empty() && !ranks.fell_back; }
+	void fall_back() { ranks.release(); ranks.fell_back = true; collect = true; } // from here on the run is `seeksv run` on the first device: one context, which keeps every record
+	PrereadFasta preread;        // the reference, handed to the aligner step that reads it
 };
-static ResidentBam g_resident;
 
-static void release_ctx(ssv_ctx *ctx)
+static void release_ctx(ssv_ctx *ctx, const RunSession *run)
 {
-	if (ctx == g_resident.ctx) return; // shared by the commands of `seeksv run`, which lets go of it at its end
+	if (run && ctx == run->ctx) return; // shared by the steps of `seeksv run`, which lets go of it at its end
 	if (kCleanExit) ssv_ctx_destroy(ctx);
 	else ssv_sync(ctx);
 }
@@ -315,9 +350,9 @@ static void early_ctx_start(int device)
 	});
 }
 
-static ssv_ctx *acquire_ctx(int device)
+static ssv_ctx *acquire_ctx(int device, const RunSession *run)
 {
-	if (g_resident.ctx) return g_resident.ctx;
+	if (run && run->ctx) return run->ctx;
 	if (g_early.started && !g_early.taken) {
 		early_ctx_join();
 		g_early.taken = true;
@@ -412,9 +447,8 @@ struct BatchSource {
 	ssvh_bam *bam = nullptr;
 	ssv_ctx *ctx = nullptr;
 	bool on_device = false;
-	bool resident = false;   // the records are in HBM already (g_resident)
-	bool allow_resident = true; // (getsv -F reads its file itself: the resident batches carry no read names)
-	bool any_order = false;     // -Z: a file in any record order (getsv -F: split alignments in read order) - ssv_bamdec_any_order
+	const RunSession *resident = nullptr; // the records are in HBM already: the run's retained batches
+	bool any_order = false;    // -Z: a file in any record order (getsv -F: split alignments in read order) - ssv_bamdec_any_order
 	size_t resident_next = 0;
 	// ---- device mode: a reader thread runs up to three chunks ahead of the decoder ----
 	// A chunk = whole BGZF blocks, the file's bytes as they are.  Two ways to get them to the GPU:
@@ -458,14 +492,14 @@ struct BatchSource {
 
 	void open(const string &path, ssv_ctx *c, bool device_inflate, const char *open_error) { open(path, [c] { return c; }, device_inflate, open_error); }
 	// get_ctx: asked for the context as late as possible - the file is opened and the reader thread is on its first chunks before (the context of a
-	// fresh process may still be coming up, acquire_ctx)
-	void open(const string &path, const std::function<ssv_ctx *()> &get_ctx, bool device_inflate, const char *open_error)
+	// fresh process may still be coming up, acquire_ctx).  run: `seeksv run` opening its own BAM - whole, and once getclip has kept its batches in this
+	// context, they are the source (every other file, -F's among them, is opened without: the caller knows which file is which)
+	void open(const string &path, const std::function<ssv_ctx *()> &get_ctx, bool device_inflate, const char *open_error, const RunSession *run = nullptr)
 	{
 		on_device = device_inflate;
 		if (ssvh_bam_open(path.c_str(), &bam) != 0) die(open_error);
-		if (g_resident.ctx || !on_device) ctx = get_ctx();
-		ssv_ctx *const c = ctx;
-		if (allow_resident && !ranged && !g_resident.collect && c && g_resident.ctx == c && !g_resident.batches.empty() && path == g_resident.path) { resident = true; on_device = true; return; }
+		if (run || !on_device) ctx = get_ctx();
+		if (run && !ranged && !run->collect && ctx && run->ctx == ctx && !run->batches.empty()) { resident = run; on_device = true; return; }
 		if (!on_device) {
 			if (ranged && ssvh_bam_set_range(bam, r_start_coff, r_start_uoff, r_end_coff, r_end_uoff) != 0) die(string("[seeksv] ") + ssvh_last_error());
 			use_pinned_batches(bam);
@@ -492,10 +526,10 @@ struct BatchSource {
 		first_bytes = std::min(stage_bytes, first_bytes_default());
 		reader = std::thread([this] { reader_main(); }); // (reads, and locks its buffers: needs no context)
 		if (!ctx) ctx = get_ctx();
-		if (ssv_bamdec_begin(ctx, ssvh_bam_n_targets(bam), first) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		if (ssv_bamdec_target_lens(ctx, ssvh_bam_target_lens(bam)) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_bamdec_begin(ctx, ssvh_bam_n_targets(bam), first));
+		check(ctx, ssv_bamdec_target_lens(ctx, ssvh_bam_target_lens(bam)));
 		if (g_verify_crc) ssv_bamdec_verify_crc(ctx, 1);
-		if (any_order && ssv_bamdec_any_order(ctx, 1) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		if (any_order) check(ctx, ssv_bamdec_any_order(ctx, 1));
 		if (ranged) ssv_bamdec_prev_tid(ctx, r_prev_tid);
 		if (!file_bytes || file_bytes > first_bytes_default()) ssv_bamdec_expect(ctx, chunk_inflated);
 	}
@@ -577,8 +611,8 @@ struct BatchSource {
 	bool next(ssv_batch_t *b, int keep_all_seq)
 	{
 		if (resident) {
-			if (resident_next >= g_resident.batches.size()) return false;
-			*b = g_resident.batches[resident_next++];
+			if (resident_next >= resident->batches.size()) return false;
+			*b = resident->batches[resident_next++];
 			return true;
 		}
 		if (!on_device) {
@@ -589,7 +623,7 @@ struct BatchSource {
 			if (at_end) return false;
 			if (end_pending) { // the last chunk has been handed out: tell the decoder the input is over (an unfinished record is an error)
 				ssv_batch_t none;
-				if (ssv_bamdec_decode(ctx, nullptr, 0, nullptr, 0, keep_all_seq, &none) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+				check(ctx, ssv_bamdec_decode(ctx, nullptr, 0, nullptr, 0, keep_all_seq, &none));
 				at_end = true;
 				return false;
 			}
@@ -607,11 +641,11 @@ struct BatchSource {
 			// the chunk behind this one starts its way over PCIe now, under this chunk's kernels
 			if (!last_chunk && next_ready && announced < cur + 1) {
 				Slot &N = slot[(cur + 1) % NS];
-				if (N.err.empty() && N.n_blocks > 0 && ssv_bamdec_prefetch(ctx, N.data, N.n_bytes) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+				if (N.err.empty() && N.n_blocks > 0) check(ctx, ssv_bamdec_prefetch(ctx, N.data, N.n_bytes));
 				announced = cur + 1;
 			}
 			if (S.limit != UINT64_MAX) ssv_bamdec_limit(ctx, S.limit);
-			if (ssv_bamdec_decode(ctx, S.data, S.n_bytes, S.blocks.data(), S.n_blocks, keep_all_seq, b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+			check(ctx, ssv_bamdec_decode(ctx, S.data, S.n_bytes, S.blocks.data(), S.n_blocks, keep_all_seq, b));
 			if (kTimingChunks) cerr << "[timing] (chunk of " << S.n_bytes << " bytes, " << S.n_blocks << " blocks, " << (S.reg_base ? "page-locked in the mapping" : "copied to staging") << " in " << S.t_fill
 			                        << " s: waited " << std::chrono::duration<double>(tw1 - tw0).count() << " s for the reader, " << (announced >= cur && cur > 0 ? "announced ahead, " : "") << "decoded in "
 			                        << std::chrono::duration<double>(std::chrono::steady_clock::now() - tw1).count() << " s)" << endl;
@@ -825,7 +859,7 @@ static void format_clusters(const ssv_cluster_table &t, ssvh_bam *bam, int64_t k
 }
 
 // `seeksv run`: a formatted piece's rows and FASTQ records as views into its text (the strings do not change any more)
-static void index_piece(ResidentBam::Piece &p, const vector<RowAt> &ix)
+static void index_piece(RunSession::Piece &p, const vector<RowAt> &ix)
 {
 	auto has_space = [](const char *q, size_t n) { for (size_t i = 0; i < n; ++i) if ((unsigned char)q[i] <= ' ') return true; return false; };
 	const char *r = p.rows.data();
@@ -841,72 +875,91 @@ static void index_piece(ResidentBam::Piece &p, const vector<RowAt> &ix)
 		if (!a.chr_len || !a.cigar_len || !a.aligned_len || !a.clipped_len || !a.cqual_len || has_space(row.chr.p, row.chr.n)) p.clean = false;
 		p.parsed.push_back(row);
 		// the record's FASTQ text: '@' name '\n' sequence "\n+\n" qualities '\n' (clip_reads.h:320-321) - name = sequence
-		p.reads.push_back(ResidentBam::FqRef{a.fq + 1 + a.clipped_len + 1, a.clipped_len, a.fq + 1 + a.clipped_len + 1 + a.clipped_len + 3, a.cqual_len});
+		p.reads.push_back(RunSession::FqRef{a.fq + 1 + a.clipped_len + 1, a.clipped_len, a.fq + 1 + a.clipped_len + 1 + a.clipped_len + 3, a.cqual_len});
 	}
 }
 
-static int getclip_ranks(const string &bamfile, const string &prefix, double threshold, int min_mapQ, bool save_low_quality, int n_ranks, const vector<int> &devices, int halo_bp, bool device_inflate);
-static int getclip_single(const string &bamfile, const string &prefix, double threshold, int min_mapQ, bool save_low_quality, int device, bool device_inflate);
-
-static int cmd_getclip(int argc, char **argv)
-{
-	int c, min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
+// A command's options AND operands, as its one parser made them of (argc, argv): the parser holds the command's optstring, prints its usage text and leaves
+// with status 1 where the words are not a valid command line.  for_run: the words of `seeksv run -c / -v / -a` - options only, run fills in the operands
+// (and what it decides itself) as fields.  What run must know to have been GIVEN, not defaulted, is a field too (`*_given`, an empty string).
+struct GetclipOptions {
 	double threshold = 0.9;
-	string prefix = "output";
-	bool save_low_quality = false, device_inflate = device_inflate_default();
+	int min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
+	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false;
 	vector<int> devices;
+	string prefix = "output", bamfile;
+	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
+};
+
+static GetclipOptions parse_getclip(int argc, char **argv, bool for_run = false)
+{
+	GetclipOptions o;
+	int c;
+	optind = 0; // (a fresh scan: nothing of the words scanned before is looked at again)
 	while ((c = getopt(argc, argv, "t:q:o:sG:ZCN:H:")) >= 0) {
 		switch (c) {
-		case 't': threshold = atof(optarg); break;
-		case 'q': min_mapQ = atoi(optarg); break;
-		case 's': save_low_quality = true; break;
-		case 'o': prefix = optarg; break;
-		case 'G': devices = parse_devices(optarg); device = devices.empty() ? 0 : devices[0]; break;
-		case 'Z': device_inflate = true; break;
-		case 'C': g_verify_crc = true; break;
-		case 'N': n_ranks = atoi(optarg); break;
-		case 'H': halo_bp = atoi(optarg); break;
+		case 't': o.threshold = atof(optarg); break;
+		case 'q': o.min_mapQ = atoi(optarg); break;
+		case 's': o.save_low_quality = true; break;
+		case 'o': o.prefix = optarg; break;
+		case 'G': o.set_devices(optarg); o.devices_given = true; break;
+		case 'Z': o.device_inflate = true; break;
+		case 'C': o.verify_crc = true; break;
+		case 'N': o.n_ranks = atoi(optarg); o.ranks_given = true; break;
+		case 'H': o.halo_bp = atoi(optarg); break;
 		default: usage_getclip();
 		}
 	}
-	if (argc != optind + 1 || n_ranks < 1 || halo_bp < 0) usage_getclip();
-	const string bamfile = argv[optind];
-	if (n_ranks > 1) return getclip_ranks(bamfile, prefix, threshold, min_mapQ, save_low_quality, n_ranks, devices, halo_bp, device_inflate);
-	return getclip_single(bamfile, prefix, threshold, min_mapQ, save_low_quality, device, device_inflate);
+	if (argc != optind + (for_run ? 0 : 1) || o.n_ranks < 1 || o.halo_bp < 0) usage_getclip();
+	if (!for_run) o.bamfile = argv[optind];
+	return o;
 }
 
-static int getclip_single(const string &bamfile, const string &prefix, double threshold, int min_mapQ, bool save_low_quality, int device, bool device_inflate)
+// getclip's four outputs, created in the reference's order with its messages
+struct ClipOutputs {
+	GzOut soft, fq, unmapped1, unmapped2;
+	explicit ClipOutputs(const string &prefix)
+	{
+		const char *suffix[4] = {".clip.gz", ".clip.fq.gz", ".unmapped_1.fq.gz", ".unmapped_2.fq.gz"};
+		GzOut *out[4] = {&soft, &fq, &unmapped1, &unmapped2};
+		for (int k = 0; k < 4; ++k) if (!out[k]->open(prefix + suffix[k])) die("Cannot open file " + prefix + suffix[k]);
+	}
+	void close() { soft.close(); fq.close(); unmapped1.close(); unmapped2.close(); }
+};
+
+static ssv_clip_params clip_params(const GetclipOptions &o)
+{
+	ssv_clip_params p;
+	memset(&p, 0, sizeof(p));
+	p.match_rate = o.threshold; p.min_mapq = o.min_mapQ; p.save_low_quality = o.save_low_quality ? 1 : 0;
+	return p;
+}
+
+static int getclip_single(const GetclipOptions &o, RunSession *run)
 {
 	PhaseTimer pt;
 	{ // like the reference: complain about the input before anything is created
 		ssvh_bam *probe = nullptr;
-		if (ssvh_bam_open(bamfile.c_str(), &probe) != 0) die("[main_samview] fail to open file for reading.");
+		if (ssvh_bam_open(o.bamfile.c_str(), &probe) != 0) die("[main_samview] fail to open file for reading.");
 		ssvh_bam_close(probe);
 	}
-	GzOut softfout, fqfout, fuout1, fuout2;
-	const string f_clip = prefix + ".clip.gz", f_fq = prefix + ".clip.fq.gz", f_u1 = prefix + ".unmapped_1.fq.gz", f_u2 = prefix + ".unmapped_2.fq.gz";
-	if (!softfout.open(f_clip)) die("Cannot open file " + f_clip);
-	if (!fqfout.open(f_fq)) die("Cannot open file " + f_fq);
-	if (!fuout1.open(f_u1)) die("Cannot open file " + f_u1);
-	if (!fuout2.open(f_u2)) die("Cannot open file " + f_u2);
+	ClipOutputs out(o.prefix);
 
 	BatchSource src;
-	src.open(bamfile, [device] { return acquire_ctx(device); }, device_inflate, "[main_samview] fail to open file for reading.");
+	src.open(o.bamfile, [&] { return acquire_ctx(o.device, run); }, o.device_inflate, "[main_samview] fail to open file for reading.", run);
 	ssv_ctx *ctx = src.ctx;
-	ssv_clip_params p;
-	memset(&p, 0, sizeof(p));
-	p.match_rate = threshold; p.min_mapq = min_mapQ; p.save_low_quality = save_low_quality ? 1 : 0;
-	if (ssv_clip_begin(ctx, &p) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	ssv_clip_params p = clip_params(o);
+	check(ctx, ssv_clip_begin(ctx, &p));
 	ssv_clip_table_format(ctx, table_format_default()); // the compact table over PCIe; expanded by the formatting threads below
 	ssvh_bam *bam = src.bam;
 	pt.lap("open+gpu_init");
 
 	// unmapped-pair side channel, StoreUnmapSeqAndQual (clip_reads.h:172-219): paired up, turned into FASTQ text and compressed by threads of its own
 	// (unmapped_pairs.h); this thread hands every batch's raw UNMAP|MUNMAP records over by pointer
-	auto keep_text = [](int end, vector<string> &parts) { // (both sinks are called by one thread, and a piece is nobody's once it is written)
-		if (g_resident.keep_unmapped) for (string &s : parts) if (!s.empty()) g_resident.unmapped[end].push_back(std::move(s));
+	auto keep_text = [run](int end, vector<string> &parts) { // (both sinks are called by one thread, and a piece is nobody's once it is written)
+		if (run && run->keep_unmapped) for (string &s : parts) if (!s.empty()) run->unmapped[end].push_back(std::move(s));
 	};
-	seeksv::UnmappedPairs unmapped([&](vector<string> &parts) { fuout1.write_parts(parts); keep_text(0, parts); }, [&](vector<string> &parts) { fuout2.write_parts(parts); keep_text(1, parts); },
+	seeksv::UnmappedPairs unmapped([&](vector<string> &parts) { out.unmapped1.write_parts(parts); keep_text(0, parts); }, [&](vector<string> &parts) { out.unmapped2.write_parts(parts); keep_text(1, parts); },
 	                               std::max(1, std::min(8, ssv::effective_cpus() / 2)));
 	// The flush sequence (clip_reads.h:428-438, :442): the reference writes out and clears its two maps at every change of contig among the
 	// mapped-pair records.  A pass of the library bins by (contig, side, position), which is the same thing as long as every contig of the
@@ -927,8 +980,8 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 		if (emitter.joinable()) emitter.join();
 		pt.lap("wait for the previous pass's output");
 		ssv_cluster_table t;
-		if (ssv_clip_cluster(ctx, &t) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		if (t.format == 3 && ssv_clip_table_expand(ctx, &t, 0) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_clip_cluster(ctx, &t));
+		if (t.format == 3) check(ctx, ssv_clip_table_expand(ctx, &t, 0));
 		pt.lap("gpu_cluster+table");
 		// DisplaySClipReadsAndClipFq ('5' rows then '3' rows per contig run), clip_reads.h:300-345.  The rows of one cluster depend on nothing
 		// else, so cluster ranges are formatted by several host threads and written out in order.
@@ -944,7 +997,7 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 			const auto t0 = std::chrono::steady_clock::now();
 			const int n_fmt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ssv::effective_cpus(), 32, k_end / 4096}));
 			vector<string> rows((size_t)n_fmt), fqs((size_t)n_fmt);
-			const bool keep = g_resident.collect && g_resident.ctx == ctx; // `seeksv run`: the aligner step and the junction stage take these from memory
+			const bool keep = run && run->collect; // `seeksv run`: the aligner step and the junction stage take these from memory
 			vector<vector<RowAt>> index(keep ? (size_t)n_fmt : 0);
 			auto format_range = [&](int w) {
 				const int64_t k0 = k_end * w / n_fmt, k1 = k_end * (w + 1) / n_fmt;
@@ -957,14 +1010,14 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 				for (auto &x : th) x.join();
 			}
 			const auto t1 = std::chrono::steady_clock::now();
-			softfout.write_parts(rows); fqfout.write_parts(fqs);
+			out.soft.write_parts(rows); out.fq.write_parts(fqs);
 			if (keep) {
-				g_resident.clip_path = f_clip; g_resident.fq_path = f_fq;
-				vector<ResidentBam::Piece *> fresh;
+				run->rows_kept = true;
+				vector<RunSession::Piece *> fresh;
 				vector<vector<RowAt> *> fresh_index;
 				for (int w = 0; w < n_fmt; ++w) if (!rows[(size_t)w].empty()) {
-					g_resident.pieces.emplace_back();
-					ResidentBam::Piece &p = g_resident.pieces.back();
+					run->pieces.emplace_back();
+					RunSession::Piece &p = run->pieces.back();
 					p.rows = std::move(rows[(size_t)w]); p.fq = std::move(fqs[(size_t)w]);
 					fresh.push_back(&p); fresh_index.push_back(&index[(size_t)w]);
 				}
@@ -974,7 +1027,7 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 					if (!fresh.empty()) index_piece(*fresh[0], *fresh_index[0]);
 					for (auto &x : th) x.join();
 				}
-				if (g_resident.on_pass) g_resident.on_pass(fresh); // the aligner step starts on this pass's clipped sequences while the next pass is read
+				if (run->on_pass) run->on_pass(fresh); // the aligner step starts on this pass's clipped sequences while the next pass is read
 			}
 			emit_format_s += std::chrono::duration<double>(t1 - t0).count();
 			emit_gzip_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
@@ -982,31 +1035,31 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 		if (last) { emitter.join(); pt.lap("wait for the last pass's output"); }
 	};
 	src.pump(0, [&](const ssv_batch_t &b) {
-		pt.lap(device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
+		pt.lap(o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
 		{ const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
 		changes_of.emplace_back();
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
 		pt.lap("host_side_channel");
 	}, [&](const ssv_batch_t &decoded) {
 		ssv_batch_t b = decoded;
-		if (g_resident.collect && g_resident.ctx == ctx) { // `seeksv run`: the batch stays in HBM for the getsv passes
-			if (ssv_batch_retain(ctx, &decoded, &b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-			g_resident.batches.push_back(b);
+		if (run && run->collect) { // `seeksv run`: the batch stays in HBM for the getsv passes
+			check(ctx, ssv_batch_retain(ctx, &decoded, &b));
+			run->batches.push_back(b);
 		}
 		int64_t lo = 0;
 		for (const auto &ch : changes_of.front()) {
 			pass_flushes.push_back(scan_last_tid); // the visit that ends here is flushed
 			if (ch.second <= pass_max_tid || pass_records + (ch.first - lo) >= pass_records_max) { // a contig that comes back (or a pass that is long enough): the pass ends in front of this record
-				if (ssv_clip_scan_range(ctx, &b, lo, ch.first) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+				check(ctx, ssv_clip_scan_range(ctx, &b, lo, ch.first));
 				emit_pass(false);
 				p.initial_last_tid = scan_last_tid;
-				if (ssv_clip_begin(ctx, &p) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+				check(ctx, ssv_clip_begin(ctx, &p));
 				lo = ch.first;
 			}
 			pass_max_tid = scan_last_tid = ch.second;
 		}
 		changes_of.pop_front();
-		if (ssv_clip_scan_range(ctx, &b, lo, b.n) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_clip_scan_range(ctx, &b, lo, b.n));
 		pass_records += b.n - lo;
 		pt.lap("gpu_scan(wait h2d+kernels)");
 	});
@@ -1014,12 +1067,12 @@ static int getclip_single(const string &bamfile, const string &prefix, double th
 	emit_pass(true);
 	cerr << "[GetSClipReads] finished!" << endl;
 	unmapped.finish();
-	softfout.close(); fqfout.close(); fuout1.close(); fuout2.close();
+	out.close();
 	pt.lap("gzip");
 	if (pt.on) cerr << "[timing] (unmapped side channel, beside the reading: " << unmapped.records() << " records, " << unmapped.pairs() << " pairs written, its thread busy " << unmapped.busy_seconds() << " s)" << endl;
 	if (pt.on) cerr << "[timing] (format, all passes, beside the reading: " << emit_format_s << " s; gzip: " << emit_gzip_s << " s)" << endl;
 	src.close();
-	release_ctx(ctx);
+	release_ctx(ctx, run);
 	pt.lap("teardown");
 	return 0;
 }
@@ -1042,72 +1095,39 @@ struct ClipRank {
 	string err;
 };
 
-// `seeksv run -N n`: what the ranks' getclip leaves behind for the getsv pass of the same process - per rank its context (alive after rank_main) and the
-// batches of its OWN run, copied into that context's memory (ssv_batch_retain, 80 B a record; the halo is scanned and forgotten), and the cuts of the file
-// both steps share.  cmd_run owns all of it and lets go of it at its end.  A batch is only ever scanned by the context that holds it.
-struct RunRank {
-	ssv_ctx *ctx = nullptr;      // (rank 0: the context acquire_ctx hands to the later steps of the process)
-	int device = 0;
-	vector<ssv_batch_t> batches; // in file order
-	int64_t kept = 0;            // records in them
-};
-struct RunRanks {
-	string path;                 // the file these are the records of
-	vector<ssvh_bam_part> parts;
-	vector<RunRank> rank;
-	bool fell_back = false;      // contigs that come back: the ranks gave way to getclip_single, nothing of theirs is left
-	void release() // every batch, and every context but rank 0's (the process's own)
-	{
-		for (size_t r = 0; r < rank.size(); ++r) {
-			RunRank &k = rank[r];
-			if (k.ctx) for (auto &b : k.batches) ssv_batch_release(k.ctx, &b);
-			k.batches.clear(); k.kept = 0;
-			if (r > 0 && k.ctx) { ssv_ctx_destroy(k.ctx); k.ctx = nullptr; }
-		}
-	}
-};
-static RunRanks *g_run_ranks = nullptr; // set by cmd_run around its getclip and getsv steps
-
-static int getclip_ranks(const string &bamfile, const string &prefix, double threshold, int min_mapQ, bool save_low_quality, int n_ranks, const vector<int> &devices, int halo_bp, bool device_inflate)
+static int getclip_ranks(const GetclipOptions &o, RunSession *run)
 {
 	PhaseTimer pt;
 	ssvh_bam *bam = nullptr;
-	if (ssvh_bam_open(bamfile.c_str(), &bam) != 0) die("[main_samview] fail to open file for reading.");
-	GzOut softfout, fqfout, fuout1, fuout2;
-	const string f_clip = prefix + ".clip.gz", f_fq = prefix + ".clip.fq.gz", f_u1 = prefix + ".unmapped_1.fq.gz", f_u2 = prefix + ".unmapped_2.fq.gz";
-	if (!softfout.open(f_clip)) die("Cannot open file " + f_clip);
-	if (!fqfout.open(f_fq)) die("Cannot open file " + f_fq);
-	if (!fuout1.open(f_u1)) die("Cannot open file " + f_u1);
-	if (!fuout2.open(f_u2)) die("Cannot open file " + f_u2);
-	vector<ssvh_bam_part> parts((size_t)n_ranks);
-	if (ssvh_bam_partition(bamfile.c_str(), n_ranks, halo_bp, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
+	if (ssvh_bam_open(o.bamfile.c_str(), &bam) != 0) die("[main_samview] fail to open file for reading.");
+	ClipOutputs files(o.prefix);
+	vector<ssvh_bam_part> parts((size_t)o.n_ranks);
+	if (ssvh_bam_partition(o.bamfile.c_str(), o.n_ranks, o.halo_bp, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
 	pt.lap("open+partition");
 	const int32_t n_targets = ssvh_bam_n_targets(bam);
-	vector<ClipRank> R((size_t)n_ranks);
+	vector<ClipRank> R((size_t)o.n_ranks);
 	// `seeksv run -N`: the ranks' contexts and the records of their own runs outlive this function
-	RunRanks *const keep = g_run_ranks && g_run_ranks->path == bamfile && (int)g_run_ranks->rank.size() == n_ranks ? g_run_ranks : nullptr;
+	RunRanks *const keep = run && !run->ranks.rank.empty() ? &run->ranks : nullptr;
 	if (keep) keep->parts = parts;
 	auto rank_main = [&](int r) {
 		ClipRank &out = R[(size_t)r];
 		const ssvh_bam_part &P = parts[(size_t)r];
 		ssv_ctx *ctx = keep ? keep->rank[(size_t)r].ctx : nullptr;
-		if (!ctx && ssv_ctx_create(device_of_rank(r, devices), &ctx) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(nullptr); return; }
+		if (!ctx && ssv_ctx_create(device_of_rank(r, o.devices), &ctx) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(nullptr); return; }
 		if (keep) keep->rank[(size_t)r].ctx = ctx;
 		auto drop_ctx = [&] { if (!keep) ssv_ctx_destroy(ctx); }; // (kept: the run lets go of it)
-		ssv_clip_params p;
-		memset(&p, 0, sizeof(p));
-		p.match_rate = threshold; p.min_mapq = min_mapQ; p.save_low_quality = save_low_quality ? 1 : 0;
+		ssv_clip_params p = clip_params(o);
 		// breakpoints (contig, 1-based position) owned by this rank: from its first record's 0-based start taken as a 1-based position - the
 		// smallest key a record can give (a '5' event sits at start + 1, a '3' event at start + reference span, and the span is 0 for a CIGAR
 		// that is one lone soft clip, clip_reads.cpp:150-190) - up to the next rank's
 		p.use_ownership = 1; p.initial_last_tid = P.initial_last_tid;
 		p.own_lo_tid = r == 0 ? 0 : P.own_tid; p.own_lo_pos = r == 0 ? 0 : P.own_pos;
-		if (r + 1 < n_ranks) { p.own_hi_tid = parts[(size_t)r + 1].own_tid; p.own_hi_pos = parts[(size_t)r + 1].own_tid < n_targets ? parts[(size_t)r + 1].own_pos : 0; }
+		if (r + 1 < o.n_ranks) { p.own_hi_tid = parts[(size_t)r + 1].own_tid; p.own_hi_pos = parts[(size_t)r + 1].own_tid < n_targets ? parts[(size_t)r + 1].own_pos : 0; }
 		else { p.own_hi_tid = INT32_MAX; p.own_hi_pos = 0; }
 		if (ssv_clip_begin(ctx, &p) != SSV_OK) { out.err = string("[seeksv] ") + ssv_last_error(ctx); drop_ctx(); return; }
 		ssv_clip_table_format(ctx, table_format_default());
 		ssvh_bam *rb = nullptr; // (the header: contig names for the rows)
-		if (ssvh_bam_open(bamfile.c_str(), &rb) != 0) { out.err = "[main_samview] fail to open file for reading."; drop_ctx(); return; }
+		if (ssvh_bam_open(o.bamfile.c_str(), &rb) != 0) { out.err = "[main_samview] fail to open file for reading."; drop_ctx(); return; }
 		// the contig of the last mapped-pair record before the rank's OWN run (its run list continues from there)
 		out.last_tid = r == 0 ? 0 : P.before_own_tid;
 		for (int phase = 0; phase < 2 && out.err.empty(); ++phase) { // 0: the halo (scanned, nothing else), 1: the rank's own records
@@ -1115,7 +1135,7 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 			BatchSource src; // host threads or the GPU (-Z) inflate and decode the run's blocks
 			if (phase == 0) src.set_range(P.scan_coff, P.scan_uoff, P.own_coff, P.own_uoff);
 			else { src.set_range(P.own_coff, P.own_uoff, P.end_coff, P.end_uoff); src.r_prev_tid = out.last_tid; }
-			src.open(bamfile, ctx, device_inflate, "[main_samview] fail to open file for reading.");
+			src.open(o.bamfile, ctx, o.device_inflate, "[main_samview] fail to open file for reading.");
 			src.pump(0, [&](const ssv_batch_t &b) {
 				out.max_span = std::max(out.max_span, b.max_ref_span);
 				if (phase != 1) return;
@@ -1149,19 +1169,19 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 	};
 	{
 		vector<std::thread> th;
-		for (int r = 1; r < n_ranks; ++r) th.emplace_back(rank_main, r);
+		for (int r = 1; r < o.n_ranks; ++r) th.emplace_back(rank_main, r);
 		rank_main(0);
 		for (auto &x : th) x.join();
 	}
 	pt.lap("ranks(scan+cluster+format)");
 	int32_t max_span = 0;
 	for (auto &o : R) { if (!o.err.empty()) die(o.err); max_span = std::max(max_span, o.max_span); }
-	if (max_span > halo_bp) die("[seeksv] a read spans " + to_string(max_span) + " reference bases, more than the halo of " + to_string(halo_bp) + " bp before a run of records: rerun with -H " + to_string(max_span));
+	if (max_span > o.halo_bp) die("[seeksv] a read spans " + to_string(max_span) + " reference bases, more than the halo of " + to_string(o.halo_bp) + " bp before a run of records: rerun with -H " + to_string(max_span));
 	// the flush sequence of the whole file: the ranks' run lists one after the other (a rank's list continues the previous rank's)
 	vector<int32_t> run_tids;
 	for (auto &o : R) run_tids.insert(run_tids.end(), o.run_tids.begin(), o.run_tids.end());
 	int32_t last_tid = 0;
-	for (int r = n_ranks - 1; r >= 0; --r) if (parts[(size_t)r].own_coff != UINT64_MAX || r == 0) { last_tid = R[(size_t)r].last_tid; break; }
+	for (int r = o.n_ranks - 1; r >= 0; --r) if (parts[(size_t)r].own_coff != UINT64_MAX || r == 0) { last_tid = R[(size_t)r].last_tid; break; }
 	run_tids.push_back(last_tid);
 	for (size_t k = 1; k < run_tids.size(); ++k)
 		if (run_tids[k] <= run_tids[k - 1]) {
@@ -1169,12 +1189,12 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 			// flush per visit of a contig (clip_reads.h:428-438) - comes from the single-GPU path, which ends a pass at every such visit.
 			ssvh_bam_close(bam);
 			if (keep) { // `seeksv run -N`: from here on the run is `seeksv run` on the first device - one context, which keeps every record
-				keep->release();
-				keep->fell_back = true;
-				cerr << "[seeksv] run -N: contigs come back in " << bamfile << ", the ranks give way to one GPU (as `seeksv run` without -N)" << endl;
-				g_resident.collect = true;
+				run->fall_back();
+				cerr << "[seeksv] run -N: contigs come back in " << o.bamfile << ", the ranks give way to one GPU (as `seeksv run` without -N)" << endl;
 			}
-			return getclip_single(bamfile, prefix, threshold, min_mapQ, save_low_quality, device_of_rank(0, devices), device_inflate);
+			GetclipOptions single = o;
+			single.device = device_of_rank(0, o.devices);
+			return getclip_single(single, run);
 		}
 	// unmapped-pair side channel, StoreUnmapSeqAndQual (clip_reads.h:172-219): sequential over the file, i.e. over the ranks in order
 	map<string, pair<pair<string, string>, char>> id2seq_qual;
@@ -1182,12 +1202,12 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 		auto it = id2seq_qual.find(u.qname);
 		if (it != id2seq_qual.end()) {
 			if (u.is_read1 && it->second.second == '2') {
-				fuout1.write(string("@") + it->first + "/1\n" + u.seq + "\n+\n" + u.qual + "\n");
-				fuout2.write(string("@") + it->first + "/2\n" + it->second.first.first + "\n+\n" + it->second.first.second + "\n");
+				files.unmapped1.write(string("@") + it->first + "/1\n" + u.seq + "\n+\n" + u.qual + "\n");
+				files.unmapped2.write(string("@") + it->first + "/2\n" + it->second.first.first + "\n+\n" + it->second.first.second + "\n");
 				id2seq_qual.erase(it);
 			} else if (!u.is_read1 && it->second.second == '1') {
-				fuout1.write(string("@") + it->first + "/1\n" + it->second.first.first + "\n+\n" + it->second.first.second + "\n");
-				fuout2.write(string("@") + it->first + "/2\n" + u.seq + "\n+\n" + u.qual + "\n");
+				files.unmapped1.write(string("@") + it->first + "/1\n" + it->second.first.first + "\n+\n" + it->second.first.second + "\n");
+				files.unmapped2.write(string("@") + it->first + "/2\n" + u.seq + "\n+\n" + u.qual + "\n");
 				id2seq_qual.erase(it);
 			}
 		} else id2seq_qual.insert(make_pair(u.qname, make_pair(make_pair(u.seq, u.qual), u.is_read1 ? '1' : '2')));
@@ -1203,13 +1223,21 @@ static int getclip_ranks(const string &bamfile, const string &prefix, double thr
 				rows.push_back(std::move(it->second.first)); fqs.push_back(std::move(it->second.second));
 			}
 	}
-	softfout.write_parts(rows); fqfout.write_parts(fqs);
+	files.soft.write_parts(rows); files.fq.write_parts(fqs);
 	cerr << "[GetSClipReads] finished!" << endl;
-	softfout.close(); fqfout.close(); fuout1.close(); fuout2.close();
+	files.close();
 	pt.lap("output");
 	ssvh_bam_close(bam);
 	return 0;
 }
+
+static int getclip_main(const GetclipOptions &o, RunSession *run)
+{
+	if (o.verify_crc) g_verify_crc = true;
+	return o.n_ranks > 1 ? getclip_ranks(o, run) : getclip_single(o, run);
+}
+
+static int cmd_getclip(int argc, char **argv) { return getclip_main(parse_getclip(argc, argv), nullptr); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // getsv (junctions from -B)
@@ -1247,14 +1275,17 @@ static double largest_base_frequency(const string &seq) // CountLargestBaseFrequ
 // CalculateInsertsizeDeviation (cluster.cpp:15-83) reads the file until it has its pairs - the first chunk or the first few.  With the records decoded on the
 // GPU their batches are copied into memory that stays (ssv_batch_retain; resident ones stay anyway): `keep` then holds the open source and those batches, and the
 // fused pass scans them and goes on from the next chunk instead of reading, inflating and decoding the head of the file again.
-struct IsizeCarry { BatchSource src; vector<ssv_batch_t> kept; bool owned = false, usable = false; };
+struct IsizeCarry {
+	BatchSource src; vector<ssv_batch_t> kept; bool owned = false, usable = false;
+	void drop(ssv_ctx *ctx) { if (usable) { if (owned) for (auto &k : kept) ssv_batch_release(ctx, &k); kept.clear(); src.close(); usable = false; } } // the pass that went on from it is over, or there was none
+};
 
-static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const string &bamfile, bool device_inflate, int min_mapQ, int read_pair_used, int &mean_insert_size, int &deviation, IsizeCarry *keep = nullptr,
-                             string *report = nullptr) // report: the pass's stderr lines go there instead (a caller that has earlier lines still to print)
+static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const string &bamfile, bool device_inflate, int min_mapQ, int read_pair_used, int &mean_insert_size, int &deviation, IsizeCarry *keep,
+                             const RunSession *run, string *report = nullptr) // report: the pass's stderr lines go there instead (a caller that has earlier lines still to print)
 {
 	BatchSource local;
 	BatchSource &src = keep ? keep->src : local;
-	src.open(bamfile, get_ctx, device_inflate, "[main_samview] fail to open file for reading.");
+	src.open(bamfile, get_ctx, device_inflate, "[main_samview] fail to open file for reading.", run);
 	ssv_ctx *ctx = src.ctx ? src.ctx : get_ctx();
 	ssv_isize_begin(ctx, min_mapQ, read_pair_used);
 	int32_t done = 0;
@@ -1264,10 +1295,10 @@ static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const st
 	while (!done) {
 		if (!src.next(&b, 0)) break;
 		++chunks;
-		if (ssv_isize_accumulate(ctx, &b, &done) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_isize_accumulate(ctx, &b, &done));
 		if (keep && src.on_device) { // a decoder's batch is valid until the next decode: a copy that stays (80 B/record, device to device)
 			ssv_batch_t k = b;
-			if (!src.resident) { if (ssv_batch_retain(ctx, &b, &k) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); keep->owned = true; }
+			if (!src.resident) { check(ctx, ssv_batch_retain(ctx, &b, &k)); keep->owned = true; }
 			keep->kept.push_back(k);
 		}
 	}
@@ -1283,14 +1314,12 @@ static void insert_size_pass(const std::function<ssv_ctx *()> &get_ctx, const st
 	src.close();
 }
 
-static void resident_alignments(seeksv::AlnRecords &R); // `seeksv run`: the aligner step's records as the join reads them
+static void resident_alignments(const RunSession &run, seeksv::AlnRecords &R); // `seeksv run`: the aligner step's records as the join reads them
 
 // getsv -F: FindJunction (process_bwasw.cpp:5-227).  A name that ends in ".bam" is BAM, every other name SAM text (the reference's rule, process_bwasw.cpp:12-16).
 // A BAM goes through the same readers as the original BAM (host threads, or the GPU with -Z); SAM text is always parsed on the GPU (ssv_samdec_*), whatever -Z
 // says.  Selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
 static const char *kRtOpenError = "[main_samview] fail to open file for reading.";
-// `seeksv run -P`: the -F pass without a file - the unmapped pairs split-aligned in this process, their records handed over on the device (run_split_leg)
-static std::function<void(ssv_ctx *, int, JunctionMap &)> g_run_split_leg;
 
 static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx)
 {
@@ -1303,7 +1332,7 @@ static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx
 	ssv_rt_params rp;
 	memset(&rp, 0, sizeof(rp));
 	rp.min_mapq = min_mapq; rp.n_targets = nt; rp.name_rank = rank.data();
-	if (ssv_rt_begin(ctx, &rp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	check(ctx, ssv_rt_begin(ctx, &rp));
 }
 
 static void *sam_stage_alloc(size_t bytes) { void *p = nullptr; return ssv_host_alloc(bytes, &p) == SSV_OK ? p : nullptr; }
@@ -1331,7 +1360,7 @@ static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &name
 	ssv_samdec_params sp;
 	memset(&sp, 0, sizeof(sp));
 	sp.n_targets = (int32_t)names.size(); sp.target_names = cnames.data(); sp.first_line = rd.first_record_line();
-	if (ssv_samdec_begin(ctx, &sp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	check(ctx, ssv_samdec_begin(ctx, &sp));
 	const char *e = getenv("SSV_SAM_CHUNK_KB");
 	const size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) << 10 : (size_t)256 << 20;
 	rd.start(chunk, sam_stage_alloc, sam_stage_free);
@@ -1344,17 +1373,17 @@ static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &name
 			die(m.compare(0, 11, "Parse error") == 0 ? m : "[seeksv] " + m);
 		}
 		ssv_names_t nm;
-		if (ssv_samdec_names(ctx, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_samdec_names(ctx, &nm));
 		if (b.n) on_batch(b, nm);
 	};
 	while (rd.next(ck, err)) {
-		if (!ck.last && rd.ready_behind(nx) && ssv_samdec_prefetch(ctx, nx.data, nx.bytes) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		if (!ck.last && rd.ready_behind(nx)) check(ctx, ssv_samdec_prefetch(ctx, nx.data, nx.bytes));
 		decode(ck.data, ck.bytes, ck.last ? 1 : 0);
 		ended = ck.last;
 	}
 	if (!err.empty()) die(err);
 	if (!ended) decode(nullptr, 0, 1);
-	if (ssv_sync(ctx) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); // (the staging buffers go with the reader)
+	check(ctx, ssv_sync(ctx)); // (the staging buffers go with the reader)
 	rd.close();
 }
 
@@ -1364,7 +1393,7 @@ static bool is_bam_name(const string &path) { return path.size() >= 4 && path.rf
 static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
 {
 	sam_text_pass(path, ctx, names, [&] { rt_begin_for(names, min_mapq, ctx); },
-	              [&](const ssv_batch_t &b, const ssv_names_t &nm) { if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); });
+	              [&](const ssv_batch_t &b, const ssv_names_t &nm) { check(ctx, ssv_rt_scan(ctx, &b, &nm)); });
 }
 
 // The re-alignments of the clipped sequences as SAM text (`bwa mem ref.fa out.clip.fq.gz > out.clip.sam`, or piped in: getsv.h:437-446 opens every name
@@ -1385,7 +1414,7 @@ static void clip_sam_pass(const string &path, ssv_ctx *ctx, ClipAlignments &A)
 {
 	sam_text_pass(path, ctx, A.R.target_names, [] {}, [&](const ssv_batch_t &b, const ssv_names_t &nm) {
 		ssv_aln_cols c;
-		if (ssv_aln_pack(ctx, &b, &nm, &c) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+		check(ctx, ssv_aln_pack(ctx, &b, &nm, &c));
 		const size_t n = (size_t)c.n, n0 = A.tid.size(), ops0 = A.cigar.size(), bytes0 = A.names.size();
 		if (ops0 + (size_t)c.n_cigar_total >= ((size_t)1 << 32)) die("[seeksv] more than 2^32 CIGAR operations among the clipped-sequence alignments");
 		A.tid.insert(A.tid.end(), c.tid, c.tid + n); A.pos.insert(A.pos.end(), c.pos, c.pos + n);
@@ -1417,7 +1446,6 @@ static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, boo
 		ssvh_bam_close(hdr);
 		rt_begin_for(names, min_mapq, ctx);
 		BatchSource src;
-		src.allow_resident = false;
 		src.any_order = true; // (a bwasw file is in read order, not coordinate order)
 		src.open(path, ctx, device_inflate, kRtOpenError);
 		if (!src.on_device && ssvh_bam_keep_names(src.bam, 1) != 0) die(string("[seeksv] ") + ssvh_last_error());
@@ -1426,12 +1454,12 @@ static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, boo
 			ssv_names_t nm;
 			const int rc = src.on_device ? ssv_bamdec_names(ctx, &nm) : (ssvh_bam_batch_names(src.bam, &nm) == 0 ? SSV_OK : SSV_E_ARG);
 			if (rc != SSV_OK) die(string("[seeksv] ") + (src.on_device ? ssv_last_error(ctx) : ssvh_last_error()));
-			if (ssv_rt_scan(ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+			check(ctx, ssv_rt_scan(ctx, &b, &nm));
 		}
 		src.close();
 	}
 	ssv_rt_result res;
-	if (ssv_rt_finish(ctx, &res) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
+	check(ctx, ssv_rt_finish(ctx, &res));
 	seeksv::apply_readthrough(res, names, junction2other);
 }
 
@@ -1549,48 +1577,101 @@ static void ranks_tally(const RanksTally &T)
 	ssv_group_destroy(group);
 }
 
-static int cmd_getsv(int argc, char **argv)
+// One tally over a BAM for getsv and somatic: T holds the filled ssv_getsv_params, what to sum and where to.  n_ranks == 0, one GPU: begin, scan - the insert-size
+// pass's carry (its kept batches, then what its open source still holds) or a fresh source over the file, which under `seeksv run` is the batches the session's context
+// holds -, finish.  n_ranks >= 1: ranks_tally over a session's ranks where they lie (its cuts, contexts and batches), else over file ranges cut here, contexts 1..n-1 made here.
+static void tally_records(ssv_ctx *ctx, RanksTally &T, int n_ranks, const vector<int> &devices, IsizeCarry &carry, const RunSession *run)
 {
-	string connect_bam, temp_breakpoint, dump_junctions;
+	if (n_ranks) {
+		const RunRanks *const ranks = run && run->ranked() ? &run->ranks : nullptr;
+		vector<ssvh_bam_part> parts((size_t)n_ranks);
+		if (!ranks && ssvh_bam_partition(T.bam_path.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
+		T.parts = ranks ? &ranks->parts : &parts;
+		T.ctxs.assign((size_t)n_ranks, nullptr);
+		T.ctxs[0] = ctx;
+		for (int r = 1; r < n_ranks; ++r) {
+			if (ranks) T.ctxs[(size_t)r] = ranks->rank[(size_t)r].ctx;
+			else if (ssv_ctx_create(device_of_rank(r, devices), &T.ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
+		}
+		if (ranks) for (const RunRank &k : ranks->rank) T.resident.push_back(&k.batches);
+		ranks_tally(T);
+		if (!ranks) for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(T.ctxs[(size_t)r]);
+	} else {
+		check(ctx, ssv_getsv_begin(ctx, &T.gp));
+		auto scan = [&](const ssv_batch_t &b) { check(ctx, ssv_getsv_scan(ctx, &b)); };
+		if (carry.usable) { // the insert-size pass left its source open behind the chunks it read, whose batches are still valid: ONE reading of the file
+			for (auto &k : carry.kept) scan(k);
+			carry.src.pump(0, [](const ssv_batch_t &) {}, scan);
+		} else {
+			BatchSource src; // a second handle: the caller's keeps serving the header
+			src.open(T.bam_path, [ctx] { return ctx; }, T.device_inflate, "[main_samview] fail to open file for reading.", run);
+			src.pump(0, [](const ssv_batch_t &) {}, scan);
+			src.close();
+		}
+		int32_t maxd = 0;
+		check(ctx, ssv_getsv_finish(ctx, T.counts, T.ranges, (int64_t)T.n_ranges, T.range_sum, T.points, (int64_t)T.n_points, T.point_depth, &maxd));
+	}
+	carry.drop(ctx);
+}
+
+struct GetsvOptions {
+	string connect_bam, temp_breakpoint, dump_junctions; // -F, -B, -J: empty = not given
 	double frequency = 0.1;
-	int c, min_mapQ2 = 1, min_mapQ = 20, read_pair_used = 5000000, sum_min_no_both_clipped_reads = 3, min_distance = 50, microhomology_length = 50, times = 4, device = 0,
-	       min_abnormal_read_pair_no = 0, flank_length = 200, min_seq_len = 30, max_seq_indel_no = 1, flank = 50, n_ranks = 1;
-	bool output_depth = true, device_inflate = device_inflate_default();
+	int min_mapQ2 = 1, min_mapQ = 20, read_pair_used = 5000000, sum_min_no_both_clipped_reads = 3, min_distance = 50, microhomology_length = 50, device = 0,
+	    min_abnormal_read_pair_no = 0, flank_length = 200, min_seq_len = 30, max_seq_indel_no = 1, flank = 50, n_ranks = 1;
+	bool output_depth = true, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false;
 	vector<int> devices;
-	PhaseTimer pt;
+	string clip_bam, original_bam, clipfile, breakpoint_file, clip_unmap_fq_file;
+	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
+};
+
+static GetsvOptions parse_getsv(int argc, char **argv, bool for_run = false)
+{
+	GetsvOptions o;
+	int c;
+	optind = 0;
 	while ((c = getopt(argc, argv, "F:B:t:l:q:Q:w:n:a:b:d:e:m:i:R:f:T:L:rDG:J:ZCN:")) >= 0) {
 		switch (c) {
-		case 'F': connect_bam = optarg; break;
-		case 'B': temp_breakpoint = optarg; break;
-		case 'l': flank = atoi(optarg); break;
-		case 'q': min_mapQ = atoi(optarg); break;
-		case 'n': read_pair_used = atoi(optarg); break;
-		case 'b': sum_min_no_both_clipped_reads = atoi(optarg); break;
-		case 'd': min_distance = atoi(optarg); break;
-		case 'e': min_abnormal_read_pair_no = atoi(optarg); break;
-		case 'm': min_seq_len = atoi(optarg); break;
-		case 'i': max_seq_indel_no = atoi(optarg); break;
-		case 'D': output_depth = false; break;
-		case 'f': frequency = atof(optarg); break;
-		case 'T': microhomology_length = atoi(optarg); break;
-		case 'L': flank_length = atoi(optarg); break;
-		case 'G': devices = parse_devices(optarg); device = devices.empty() ? 0 : devices[0]; break;
-		case 'Z': device_inflate = true; break;
-		case 'C': g_verify_crc = true; break;
-		case 'N': n_ranks = atoi(optarg); break;
-		case 'J': dump_junctions = optarg; break;
-		case 'w': min_mapQ2 = atoi(optarg); break; // -F's mapping-quality floor (seeksv.cpp:221-225)
+		case 'F': o.connect_bam = optarg; break;
+		case 'B': o.temp_breakpoint = optarg; break;
+		case 'l': o.flank = atoi(optarg); break;
+		case 'q': o.min_mapQ = atoi(optarg); break;
+		case 'n': o.read_pair_used = atoi(optarg); break;
+		case 'b': o.sum_min_no_both_clipped_reads = atoi(optarg); break;
+		case 'd': o.min_distance = atoi(optarg); break;
+		case 'e': o.min_abnormal_read_pair_no = atoi(optarg); break;
+		case 'm': o.min_seq_len = atoi(optarg); break;
+		case 'i': o.max_seq_indel_no = atoi(optarg); break;
+		case 'D': o.output_depth = false; break;
+		case 'f': o.frequency = atof(optarg); break;
+		case 'T': o.microhomology_length = atoi(optarg); break;
+		case 'L': o.flank_length = atoi(optarg); break;
+		case 'G': o.set_devices(optarg); o.devices_given = true; break;
+		case 'Z': o.device_inflate = true; break;
+		case 'C': o.verify_crc = true; break;
+		case 'N': o.n_ranks = atoi(optarg); o.ranks_given = true; break;
+		case 'J': o.dump_junctions = optarg; break;
+		case 'w': o.min_mapQ2 = atoi(optarg); break; // -F's mapping-quality floor (seeksv.cpp:221-225)
 		default: break; // -t -Q -a -R -r: accepted, unused (as in the reference, where -t / -Q no longer reach the join)
 		}
 	}
-	if (argc != optind + 5) usage_getsv();
-	if (flank > 90 || flank < 0 || min_seq_len < 0 || n_ranks < 1) usage_getsv();
-	const string clip_bam = argv[optind], original_bam = argv[optind + 1], clipfile = argv[optind + 2], breakpoint_file = argv[optind + 3], clip_unmap_fq_file = argv[optind + 4];
+	if (argc != optind + (for_run ? 0 : 5)) usage_getsv();
+	if (o.flank > 90 || o.flank < 0 || o.min_seq_len < 0 || o.n_ranks < 1) usage_getsv();
+	if (!for_run) { o.clip_bam = argv[optind]; o.original_bam = argv[optind + 1]; o.clipfile = argv[optind + 2]; o.breakpoint_file = argv[optind + 3]; o.clip_unmap_fq_file = argv[optind + 4]; }
+	return o;
+}
 
+static int getsv_main(const GetsvOptions &opt, RunSession *run)
+{
+	PhaseTimer pt;
+	if (opt.verify_crc) g_verify_crc = true;
+	const int times = 4;
+	double frequency = opt.frequency;
+	int min_abnormal_read_pair_no = opt.min_abnormal_read_pair_no;
 	JunctionMap junction2other;
-	if (!temp_breakpoint.empty()) { // ReadBreakpoint, getsv.cpp:1292-1323
-		ifstream fin(temp_breakpoint.c_str());
-		if (!fin) cerr << "Cannot open file " << temp_breakpoint << endl;
+	if (!opt.temp_breakpoint.empty()) { // ReadBreakpoint, getsv.cpp:1292-1323
+		ifstream fin(opt.temp_breakpoint.c_str());
+		if (!fin) cerr << "Cannot open file " << opt.temp_breakpoint << endl;
 		string up_chr, down_chr, svt, up_cigar, down_cigar, up_seq, down_seq, temp;
 		int up_pos, up_reads_no, down_pos, down_reads_no, micro, abnormal, d1, d2, d3, d4, d5, d6;
 		char up_strand, down_strand;
@@ -1610,46 +1691,46 @@ static int cmd_getsv(int argc, char **argv)
 		cerr << "[ReadBreakpoint] finish" << endl;
 	}
 	ssv_ctx *rt_ctx = nullptr;
-	if (!connect_bam.empty()) { // FindJunction (seeksv.cpp:221-225): after the -B rows, before the clip join; with -N n once, on the first device
-		rt_ctx = acquire_ctx(device);
-		readthrough_pass(connect_bam, min_mapQ2, rt_ctx, device_inflate, junction2other);
+	if (!opt.connect_bam.empty()) { // FindJunction (seeksv.cpp:221-225): after the -B rows, before the clip join; with -N n once, on the first device
+		rt_ctx = acquire_ctx(opt.device, run);
+		readthrough_pass(opt.connect_bam, opt.min_mapQ2, rt_ctx, opt.device_inflate, junction2other);
 		cerr << "'FindJunction' finished" << endl;
 		pt.lap("readthrough (-F)");
-	} else if (g_run_split_leg) { // `seeksv run -P`: at the same place, with -w as its floor
-		rt_ctx = acquire_ctx(device);
-		g_run_split_leg(rt_ctx, min_mapQ2, junction2other);
+	} else if (run && run->split_leg) { // `seeksv run -P`: at the same place, with -w as its floor
+		rt_ctx = acquire_ctx(opt.device, run);
+		run->split_leg(rt_ctx, opt.min_mapQ2, junction2other);
 		cerr << "'FindJunction' finished" << endl;
 		pt.lap("readthrough (run -P: split alignments of the unmapped pairs, device rows)");
 	}
 	{ // InputSoftInfoStoreBreakpoint + GetJunction (getsv.h:423, getsv.cpp:1705): clip clusters x re-alignments of their clipped sequences
 		string err;
-		const bool rows_resident = g_resident.ctx && clipfile == g_resident.clip_path;
+		const bool rows_resident = run && run->rows_kept; // the rows of prefix.clip.gz are still in memory
 		auto join_records = [&](const seeksv::AlnRecords &R) { // the alignments in memory; the rows too when this process wrote them
-			if (!rows_resident) return seeksv::assemble_junctions_file_records(clipfile, R, junction2other);
-			if (g_resident.all_clean() && !getenv("SSV_RUN_PARSE_ROWS")) { // the rows as the formatter kept them: nothing is parsed (SSV_RUN_PARSE_ROWS, tests: the text is)
+			if (!rows_resident) return seeksv::assemble_junctions_file_records(opt.clipfile, R, junction2other);
+			if (run->all_clean() && !getenv("SSV_RUN_PARSE_ROWS")) { // the rows as the formatter kept them: nothing is parsed (SSV_RUN_PARSE_ROWS, tests: the text is)
 				vector<const vector<seeksv::ClipRow> *> parts;
-				for (const auto &p : g_resident.pieces) parts.push_back(&p.parsed);
+				for (const auto &p : run->pieces) parts.push_back(&p.parsed);
 				return seeksv::assemble_junctions_rows(parts, R, junction2other);
 			}
-			return seeksv::assemble_junctions_records(g_resident.row_views(), R, junction2other);
+			return seeksv::assemble_junctions_records(run->row_views(), R, junction2other);
 		};
-		if (!is_bam_name(clip_bam)) { // SAM text (the reference's rule, getsv.h:437-446): always parsed on the GPU, whatever -Z says; with -N n once, on the first device
-			if (!rt_ctx) { rt_ctx = acquire_ctx(device); pt.lap("context start-up (waited for in front of the SAM decode)"); }
+		if (!is_bam_name(opt.clip_bam)) { // SAM text (the reference's rule, getsv.h:437-446): always parsed on the GPU, whatever -Z says; with -N n once, on the first device
+			if (!rt_ctx) { rt_ctx = acquire_ctx(opt.device, run); pt.lap("context start-up (waited for in front of the SAM decode)"); }
 			ClipAlignments A;
-			clip_sam_pass(clip_bam, rt_ctx, A);
+			clip_sam_pass(opt.clip_bam, rt_ctx, A);
 			pt.lap("clip alignments (SAM text: decode + pack)");
 			err = join_records(A.R);
-		} else if (rows_resident && clip_bam == g_resident.aln.bam_path && g_resident.aln.rec) {
+		} else if (rows_resident && run->aln.rec) {
 			seeksv::AlnRecords R; // rows and alignments are both still in memory
-			resident_alignments(R);
+			resident_alignments(*run, R);
 			err = join_records(R);
-		} else err = rows_resident ? seeksv::assemble_junctions_text(g_resident.row_views(), clip_bam, junction2other) : seeksv::assemble_junctions(clipfile, clip_bam, junction2other);
+		} else err = rows_resident ? seeksv::assemble_junctions_text(run->row_views(), opt.clip_bam, junction2other) : seeksv::assemble_junctions(opt.clipfile, opt.clip_bam, junction2other);
 		if (!err.empty()) die(err);
 	}
 	cerr << "'InputSoftInfoStoreBreakpoint' finished" << endl;
-	seeksv::merge_junctions(junction2other, flank); // MergeJunction(flank = -l)
-	if (!dump_junctions.empty()) { // test hook: the junction table before any BAM pass (no GPU needed)
-		ofstream jd(dump_junctions.c_str());
+	seeksv::merge_junctions(junction2other, opt.flank); // MergeJunction(flank = -l)
+	if (!opt.dump_junctions.empty()) { // test hook: the junction table before any BAM pass (no GPU needed)
+		ofstream jd(opt.dump_junctions.c_str());
 		for (auto &kv : junction2other) {
 			const Junction &j = kv.first; const OtherInfo &o = kv.second;
 			jd << j.up_chr << '\t' << j.up_pos << '\t' << j.up_strand << '\t' << o.up.support << '\t' << j.down_chr << '\t' << j.down_pos << '\t' << j.down_strand << '\t' << o.down.support << '\t'
@@ -1661,18 +1742,18 @@ static int cmd_getsv(int argc, char **argv)
 
 	pt.lap("junction_stage");
 	ssvh_bam *bam = nullptr;
-	if (ssvh_bam_open(original_bam.c_str(), &bam) != 0) die("[main_samview] fail to open file " + original_bam + "for reading.");
+	if (ssvh_bam_open(opt.original_bam.c_str(), &bam) != 0) die("[main_samview] fail to open file " + opt.original_bam + "for reading.");
 	ssv_ctx *ctx = rt_ctx;
-	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(device); return ctx; }; // (main() started it before the junction stage)
+	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(opt.device, run); return ctx; }; // (main() started it before the junction stage)
 
 	int mean_insert_size = 0, deviation = 0;
-	const bool do_discordant = read_pair_used >= 100000; // seeksv.cpp:246
+	const bool do_discordant = opt.read_pair_used >= 100000; // seeksv.cpp:246
 	IsizeCarry carry;
 	// SSV_GROUP_RCCL_ONE=1: `-N 1` takes the ranks' path too - one run of records, its vector through a one-rank RCCL communicator (what a
 	// one-GPU box can execute of the exchange)
-	const bool ranks_path = n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
+	const bool ranks_path = opt.n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
 	if (do_discordant) {
-		insert_size_pass(get_ctx, original_bam, device_inflate, min_mapQ, read_pair_used, mean_insert_size, deviation, !ranks_path ? &carry : nullptr);
+		insert_size_pass(get_ctx, opt.original_bam, opt.device_inflate, opt.min_mapQ, opt.read_pair_used, mean_insert_size, deviation, !ranks_path ? &carry : nullptr, run);
 		cerr << "'CalculateInsertsizeDeviation' finished" << endl;
 	} else min_abnormal_read_pair_no = 0; // seeksv.cpp:285
 	get_ctx();
@@ -1687,7 +1768,7 @@ static int cmd_getsv(int argc, char **argv)
 	}
 	const int64_t nJ = (int64_t)J.size();
 	ssvh_plan *plan = nullptr;
-	ssvh_plan_create(bam, J.data(), nJ, nullptr, nullptr, 0, mean_insert_size, deviation, times, flank_length, &plan);
+	ssvh_plan_create(bam, J.data(), nJ, nullptr, nullptr, 0, mean_insert_size, deviation, times, opt.flank_length, &plan);
 	int64_t nj, nw, nr, np;
 	const ssv_junction *dj = ssvh_plan_junctions(plan, &nj);
 	const ssv_interval *dw = ssvh_plan_windows(plan, &nw);
@@ -1696,66 +1777,24 @@ static int cmd_getsv(int argc, char **argv)
 	pt.lap("plan");
 	vector<int32_t> counts((size_t)nj + 1, 0), pdepth((size_t)np + 1, 0);
 	vector<uint64_t> rsum((size_t)nr + 1, 0);
-	if ((do_discordant || output_depth) && ranks_path) {
-		// ---- N runs of records, one per GPU (ranks_tally) ----
+	if (do_discordant || opt.output_depth) {
 		// `seeksv run -N`: the cuts getclip's ranks used, their contexts, and the records where those ranks left them; else the file is cut here and read
-		const RunRanks *const run = g_run_ranks && !g_run_ranks->fell_back && g_run_ranks->path == original_bam && (int)g_run_ranks->rank.size() == n_ranks && g_run_ranks->rank[0].ctx == ctx ? g_run_ranks : nullptr;
 		RanksTally T;
-		T.bam_path = original_bam;
-		vector<ssvh_bam_part> parts((size_t)n_ranks);
-		if (run) T.parts = &run->parts;
-		else {
-			if (ssvh_bam_partition(original_bam.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
-			T.parts = &parts;
-		}
-		T.ctxs.assign((size_t)n_ranks, nullptr);
-		T.ctxs[0] = ctx;
-		for (int r = 1; r < n_ranks; ++r) {
-			if (run) T.ctxs[(size_t)r] = run->rank[(size_t)r].ctx;
-			else if (ssv_ctx_create(device_of_rank(r, devices), &T.ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
-		}
-		if (run) for (const RunRank &k : run->rank) T.resident.push_back(&k.batches);
-		T.device_inflate = device_inflate;
+		T.bam_path = opt.original_bam; T.device_inflate = opt.device_inflate;
 		memset(&T.gp, 0, sizeof(T.gp));
 		T.gp.junctions = dj; T.gp.n_junctions = do_discordant ? nj : 0;
-		T.gp.mean = mean_insert_size; T.gp.sd = deviation; T.gp.times = times; T.gp.disc_min_mapq = min_mapQ;
-		T.gp.windows = dw; T.gp.n_windows = output_depth ? nw : 0; T.gp.depth_min_mapq = min_mapQ;
+		T.gp.mean = mean_insert_size; T.gp.sd = deviation; T.gp.times = times; T.gp.disc_min_mapq = opt.min_mapQ;
+		T.gp.windows = dw; T.gp.n_windows = opt.output_depth ? nw : 0; T.gp.depth_min_mapq = opt.min_mapQ;
 		T.gp.n_targets = ssvh_bam_n_targets(bam); T.gp.target_len = ssvh_bam_target_lens(bam);
-		T.depth = output_depth;
+		T.depth = opt.output_depth;
 		T.ranges = dr; T.points = dp;
-		T.n_counts = do_discordant ? (size_t)nj : 0; T.n_ranges = output_depth ? (size_t)nr : 0; T.n_points = output_depth ? (size_t)np : 0;
+		T.n_counts = do_discordant ? (size_t)nj : 0; T.n_ranges = opt.output_depth ? (size_t)nr : 0; T.n_points = opt.output_depth ? (size_t)np : 0;
 		T.counts = do_discordant ? counts.data() : nullptr; T.range_sum = rsum.data(); T.point_depth = pdepth.data();
-		ranks_tally(T);
-		if (!run) for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(T.ctxs[(size_t)r]);
-	} else if (do_discordant || output_depth) {
-		ssv_getsv_params gp;
-		memset(&gp, 0, sizeof(gp));
-		gp.junctions = dj; gp.n_junctions = do_discordant ? nj : 0;
-		gp.mean = mean_insert_size; gp.sd = deviation; gp.times = times; gp.disc_min_mapq = min_mapQ;
-		gp.windows = dw; gp.n_windows = output_depth ? nw : 0; gp.depth_min_mapq = min_mapQ;
-		gp.n_targets = ssvh_bam_n_targets(bam); gp.target_len = ssvh_bam_target_lens(bam);
-		if (ssv_getsv_begin(ctx, &gp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		auto scan = [&](const ssv_batch_t &b) { if (ssv_getsv_scan(ctx, &b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); };
-		if (carry.usable) { // the insert-size pass left its source open behind the file's first chunk, whose batch is still valid
-			for (auto &k : carry.kept) { scan(k); if (carry.owned) ssv_batch_release(ctx, &k); }
-			carry.kept.clear();
-			carry.src.pump(0, [](const ssv_batch_t &) {}, scan);
-			carry.src.close();
-			carry.usable = false;
-		} else {
-			BatchSource src; // a second handle: `bam` keeps serving the header
-			src.open(original_bam, ctx, device_inflate, "[main_samview] fail to open file for reading.");
-			src.pump(0, [](const ssv_batch_t &) {}, scan);
-			src.close();
-		}
-		int32_t maxd = 0;
-		if (ssv_getsv_finish(ctx, do_discordant ? counts.data() : nullptr, dr, output_depth ? nr : 0, rsum.data(), dp, output_depth ? np : 0, pdepth.data(), &maxd) != SSV_OK)
-			die(string("[seeksv] ") + ssv_last_error(ctx));
+		tally_records(ctx, T, ranks_path ? opt.n_ranks : 0, opt.devices, carry, run);
 	}
-	if (carry.usable) { if (carry.owned) for (auto &k : carry.kept) ssv_batch_release(ctx, &k); carry.kept.clear(); carry.src.close(); carry.usable = false; }
 	pt.lap("fused_pass");
 	if (do_discordant) { cerr << "'StoreSeqName2Tid' finished" << endl; cerr << "'FindDiscordantReadPairs' finished" << endl; }
-	if (output_depth) { cerr << "'MergeOverlap' finished" << endl; cerr << "'main_depth' finished" << endl; }
+	if (opt.output_depth) { cerr << "'MergeOverlap' finished" << endl; cerr << "'main_depth' finished" << endl; }
 	else frequency = 0; // seeksv.cpp:300
 	vector<int32_t> abnormal((size_t)nJ + 1), up_depth((size_t)nJ + 1), down_depth((size_t)nJ + 1);
 	vector<uint64_t> flank_sum((size_t)nJ * 4 + 4);
@@ -1763,8 +1802,8 @@ static int cmd_getsv(int argc, char **argv)
 	ssvh_plan_fold(plan, do_discordant ? counts.data() : nullptr, prev.data(), rsum.data(), pdepth.data(), abnormal.data(), up_depth.data(), down_depth.data(), flank_sum.data(),
 	               flank_len.data(), nullptr);
 
-	ofstream fout(breakpoint_file.c_str());
-	if (!fout) die("Cannot open file " + breakpoint_file);
+	ofstream fout(opt.breakpoint_file.c_str());
+	if (!fout) die("Cannot open file " + opt.breakpoint_file);
 	fout << "@left_chr\tleft_pos\tleft_strand\tleft_clip_read_NO\tright_chr\tright_pos\tright_strand\tright_clip_read_NO\tmicrohomology_length\tabnormal_readpair_NO\tsvtype\tleft_pos_depth\t"
 	        "right_pos_depth\taverage_depth_of_left_pos_5end\taverage_depth_of_left_pos_3end\taverage_depth_of_right_pos_5end\taverage_depth_of_right_pos_3end\tleft_pos_clip_percentage\t"
 	        "right_pos_clip_percentage\tleft_seq_cigar\tright_seq_cigar\tleft_seq\tright_seq" << endl;
@@ -1774,10 +1813,10 @@ static int cmd_getsv(int argc, char **argv)
 		const Junction &j = it->first;
 		OtherInfo &o = it->second;
 		if (do_discordant) o.abnormal = abnormal[(size_t)idx];
-		const int updepth = (output_depth ? up_depth[(size_t)idx] : 0) + o.down.support;     // without the depth pass pos2depth is empty: the reference prints an error and uses 0
-		const int downdepth = (output_depth ? down_depth[(size_t)idx] : 0) + o.up.support;
-		const int up_only = output_depth ? updepth : 0, down_only = output_depth ? downdepth : 0;
-		if (!output_depth) {
+		const int updepth = (opt.output_depth ? up_depth[(size_t)idx] : 0) + o.down.support;     // without the depth pass pos2depth is empty: the reference prints an error and uses 0
+		const int downdepth = (opt.output_depth ? down_depth[(size_t)idx] : 0) + o.up.support;
+		const int up_only = opt.output_depth ? updepth : 0, down_only = opt.output_depth ? downdepth : 0;
+		if (!opt.output_depth) {
 			cerr << "Error: There is something wrong in upstream position " << j.up_chr << ":" << j.up_pos << endl;
 			cerr << "Error: There is something wrong in downstream position " << j.down_chr << ":" << j.down_pos << endl;
 		}
@@ -1790,82 +1829,97 @@ static int cmd_getsv(int argc, char **argv)
 			     << cigar_text(o.up) << '\t' << cigar_text(o.down) << '\t' << o.up.seq << '\t' << o.down.seq << endl;
 		};
 		if (!(o.up.uniq + o.down.uniq >= 2 || o.abnormal > 0)) { filtered("mappingQ_too_low"); continue; }
-		if (j.up_chr == j.down_chr && abs(j.up_pos - j.down_pos) < min_distance) { filtered("distance_too_near"); continue; }
-		if (o.microhomology > microhomology_length) { filtered("microhomology_len_too_long"); continue; }
+		if (j.up_chr == j.down_chr && abs(j.up_pos - j.down_pos) < opt.min_distance) { filtered("distance_too_near"); continue; }
+		if (o.microhomology > opt.microhomology_length) { filtered("microhomology_len_too_long"); continue; }
 		if (o.abnormal < min_abnormal_read_pair_no) { filtered("abnormal_read_pair_no_not_pass"); continue; }
 		if ((o.up.support > 0 && o.down.support > 0 && rate1 < frequency && rate2 < frequency) || (o.up.support == 0 && rate2 < frequency) || (o.down.support == 0 && rate1 < frequency)) {
 			filtered("frequency_too_low"); continue;
 		}
-		if (o.up.support + o.down.support < sum_min_no_both_clipped_reads) { filtered("total_clipped_reads_NO_not_pass"); continue; }
+		if (o.up.support + o.down.support < opt.sum_min_no_both_clipped_reads) { filtered("total_clipped_reads_NO_not_pass"); continue; }
 		if (o.abnormal == 0) {
-			if (o.up.seq.length() < (size_t)(o.up.left_clipped + o.up.right_clipped + min_seq_len) || o.down.seq.length() < (size_t)(o.down.left_clipped + o.down.right_clipped + min_seq_len)) {
+			if (o.up.seq.length() < (size_t)(o.up.left_clipped + o.up.right_clipped + opt.min_seq_len) || o.down.seq.length() < (size_t)(o.down.left_clipped + o.down.right_clipped + opt.min_seq_len)) {
 				filtered("seq_length_too_short"); continue;
 			}
-			if (o.up.cigar_vec.size() > (size_t)(2 * max_seq_indel_no + 1) || o.down.cigar_vec.size() > (size_t)(2 * max_seq_indel_no + 1)) { filtered("seq_with_too_many_indels"); continue; }
+			if (o.up.cigar_vec.size() > (size_t)(2 * opt.max_seq_indel_no + 1) || o.down.cigar_vec.size() > (size_t)(2 * opt.max_seq_indel_no + 1)) { filtered("seq_with_too_many_indels"); continue; }
 			if (largest_base_frequency(o.up.seq) >= 0.8 || largest_base_frequency(o.down.seq) >= 0.8) { filtered("repeat_bases"); continue; }
 		}
 		unsigned int fl[4] = {0, 0, 0, 0};
-		if (output_depth) for (int k = 0; k < 4; ++k) fl[k] = (unsigned int)(flank_sum[(size_t)idx * 4 + k] / flank_len[(size_t)idx * 4 + k]); // getsv.cpp:946 (divides by zero like the reference if a window is empty)
+		if (opt.output_depth) for (int k = 0; k < 4; ++k) fl[k] = (unsigned int)(flank_sum[(size_t)idx * 4 + k] / flank_len[(size_t)idx * 4 + k]); // getsv.cpp:946 (divides by zero like the reference if a window is empty)
 		else cerr << "Error depth in the vicinity of junction " << j.up_chr << '\t' << j.up_pos << '\t' << j.up_strand << '\t' << j.down_chr << '\t' << j.down_pos << '\t' << j.down_strand << endl;
 		fout << j.up_chr << '\t' << j.up_pos << '\t' << j.up_strand << '\t' << o.up.support << '\t' << j.down_chr << '\t' << j.down_pos << '\t' << j.down_strand << '\t' << o.down.support << '\t'
 		     << o.microhomology << '\t' << o.abnormal << '\t' << sv_type(j) << '\t' << ud << '\t' << dd << '\t' << (int)fl[0] << '\t' << (int)fl[1] << '\t' << (int)fl[2] << '\t' << (int)fl[3] << '\t'
 		     << rate1 << '\t' << rate2 << '\t' << cigar_text(o.up) << '\t' << cigar_text(o.down) << '\t' << o.up.seq << '\t' << o.down.seq << endl;
 	}
-	ofstream foutuq(clip_unmap_fq_file.c_str()); // OutputOneendUnmapBreakpoint: always empty (GetJunction returns early for type 'n')
-	if (!foutuq) die("Cannot open file " + clip_unmap_fq_file);
+	ofstream foutuq(opt.clip_unmap_fq_file.c_str()); // OutputOneendUnmapBreakpoint: always empty (GetJunction returns early for type 'n')
+	if (!foutuq) die("Cannot open file " + opt.clip_unmap_fq_file);
 	pt.lap("fold+output");
 	ssvh_plan_destroy(plan);
-	release_ctx(ctx);
+	release_ctx(ctx, run);
 	ssvh_bam_close(bam);
 	pt.lap("teardown");
 	return 0;
 }
 
+
+static int cmd_getsv(int argc, char **argv) { return getsv_main(parse_getsv(argc, argv), nullptr); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // somatic (CallSomatic, seeksv.cpp:366-407; ReadTumorFileAndOutputSomaticInfo, somatic.cpp:14-427)
 // ---------------------------------------------------------------------------------------------------------------------
 
-static int cmd_somatic(int argc, char **argv)
-{
-	int offset = 30, c, min_len_of_clipped_seq = 10, read_pair_used = 5000000, min_mapQ = 20, device = 0, n_ranks = 1;
+struct SomaticOptions {
+	int offset = 30, min_len_of_clipped_seq = 10, read_pair_used = 5000000, min_mapQ = 20, device = 0, n_ranks = 1;
 	double min_map_rate = 0.9;
-	string dump_lookups;
-	bool device_inflate = device_inflate_default();
+	string dump_lookups; // -J
+	bool device_inflate = device_inflate_default(), verify_crc = false;
 	vector<int> devices;
-	PhaseTimer pt;
+	string normal_bam_file, clipped_file, tumor_file, somatic_file;
+};
+
+static SomaticOptions parse_somatic(int argc, char **argv)
+{
+	SomaticOptions o;
+	int c;
+	optind = 0;
 	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:")) >= 0) {
 		switch (c) {
-		case 't': min_map_rate = atof(optarg); break;
-		case 'q': min_mapQ = atoi(optarg); break;
-		case 'l': offset = atoi(optarg); break;
-		case 'm': min_len_of_clipped_seq = atoi(optarg); break;
-		case 'n': read_pair_used = atoi(optarg); break;
-		case 'G': devices = parse_devices(optarg); device = devices.empty() ? 0 : devices[0]; break;
-		case 'Z': device_inflate = true; break;
-		case 'C': g_verify_crc = true; break;
-		case 'N': n_ranks = atoi(optarg); break;
-		case 'J': dump_lookups = optarg; break; // test hook: the host look-ups only (no BAM pass, no GPU), one line per output row
+		case 't': o.min_map_rate = atof(optarg); break;
+		case 'q': o.min_mapQ = atoi(optarg); break;
+		case 'l': o.offset = atoi(optarg); break;
+		case 'm': o.min_len_of_clipped_seq = atoi(optarg); break;
+		case 'n': o.read_pair_used = atoi(optarg); break;
+		case 'G': o.devices = parse_devices(optarg); o.device = o.devices.empty() ? 0 : o.devices[0]; break;
+		case 'Z': o.device_inflate = true; break;
+		case 'C': o.verify_crc = true; break;
+		case 'N': o.n_ranks = atoi(optarg); break;
+		case 'J': o.dump_lookups = optarg; break; // test hook: the host look-ups only (no BAM pass, no GPU), one line per output row
 		}
 	}
-	if (n_ranks < 1) usage_somatic();
+	if (o.n_ranks < 1) usage_somatic();
 	if (argc != optind + 4) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
-	else if (offset >= 90 || offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
-	const string normal_bam_file = argv[optind++], clipped_file = argv[optind++], tumor_file = argv[optind++], somatic_file = argv[optind++];
+	else if (o.offset >= 90 || o.offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
+	o.normal_bam_file = argv[optind]; o.clipped_file = argv[optind + 1]; o.tumor_file = argv[optind + 2]; o.somatic_file = argv[optind + 3];
+	return o;
+}
 
+static int somatic_main(const SomaticOptions &o)
+{
+	PhaseTimer pt;
+	if (o.verify_crc) g_verify_crc = true;
 	// The normal sample's clusters (all host threads: inflate + parse of a 30x sample's 5.5 M rows) are read BESIDE the GPU's work: what a row of the
 	// tumor's table asks of the BAM (somatic.cpp:111,142: whether FindDiscordantReadPairs runs for it) depends on the insert size only, not on the look-ups.
 	NormalClusters normal;
 	string load_warnings, load_err;
-	auto load = [&] { load_err = load_normal_clusters(clipped_file, min_len_of_clipped_seq, normal, load_warnings); };
-	if (!dump_lookups.empty()) {
+	auto load = [&] { load_err = load_normal_clusters(o.clipped_file, o.min_len_of_clipped_seq, normal, load_warnings); };
+	if (!o.dump_lookups.empty()) {
 		load();
 		if (!load_err.empty()) die(load_err);
 		cerr << load_warnings;
 		pt.lap("normal_clusters");
 		vector<SomaticRow> rows;
-		string err = scan_tumor_table(tumor_file, normal.clip3, normal.clip5, offset, min_map_rate, 1, rows);
+		string err = scan_tumor_table(o.tumor_file, normal.clip3, normal.clip5, o.offset, o.min_map_rate, 1, rows);
 		if (!err.empty()) die(err);
-		ofstream jd(dump_lookups.c_str());
+		ofstream jd(o.dump_lookups.c_str());
 		for (auto &row : rows) {
 			if (row.kind == SomaticRow::HEADER) jd << row.text << '\n';
 			else if (row.kind == SomaticRow::MESSAGE) cerr << row.text << endl;
@@ -1876,24 +1930,24 @@ static int cmd_somatic(int argc, char **argv)
 	std::thread loader(load);
 	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{loader}; // (die() leaves through _exit; a return must not leave the thread behind)
 	ssv_ctx *ctx = nullptr;
-	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(device); return ctx; }; // (main() started it)
+	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(o.device, nullptr); return ctx; }; // (main() started it)
 	int mean_insert_size = 0, deviation = 0;
 	IsizeCarry carry;
 	string isize_report; // ReadsClipReads' warnings come first on the reference's stderr (seeksv.cpp:392-398): the lines wait for the loader
 	// -N n: the tally over the normal BAM is split like `getsv -N`'s (SSV_GROUP_RCCL_ONE=1: `-N 1` takes that path too, through a one-rank RCCL communicator);
 	// the insert-size pass stays on rank 0, and leaves no open source behind - the ranks read their own ranges
-	const bool ranks_path = n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
-	if (read_pair_used >= 100000) insert_size_pass(get_ctx, normal_bam_file, device_inflate, min_mapQ, read_pair_used, mean_insert_size, deviation, ranks_path ? nullptr : &carry, &isize_report);
+	const bool ranks_path = o.n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
+	if (o.read_pair_used >= 100000) insert_size_pass(get_ctx, o.normal_bam_file, o.device_inflate, o.min_mapQ, o.read_pair_used, mean_insert_size, deviation, ranks_path ? nullptr : &carry, nullptr, &isize_report);
 	get_ctx();
 	pt.lap("isize_pass (+ what was left of the context's start-up)");
 
-	ofstream fout(somatic_file.c_str());
-	if (!fout) die("Error: Cannot open output file " + somatic_file);
+	ofstream fout(o.somatic_file.c_str());
+	if (!fout) die("Error: Cannot open output file " + o.somatic_file);
 	ssvh_bam *bam = nullptr;
-	if (ssvh_bam_open(normal_bam_file.c_str(), &bam) != 0) die("[main_samview] fail to open file for reading.");
+	if (ssvh_bam_open(o.normal_bam_file.c_str(), &bam) != 0) die("[main_samview] fail to open file for reading.");
 	vector<SomaticRow> rows;
 	{
-		string err = parse_tumor_table(tumor_file, mean_insert_size, rows);
+		string err = parse_tumor_table(o.tumor_file, mean_insert_size, rows);
 		if (!err.empty()) { loader.join(); if (!load_err.empty()) die(load_err); cerr << load_warnings << isize_report; die(err); }
 	}
 	pt.lap("tumor_table");
@@ -1914,54 +1968,25 @@ static int cmd_somatic(int argc, char **argv)
 		int64_t nj;
 		const ssv_junction *dj = ssvh_plan_junctions(plan, &nj);
 		vector<int32_t> counts((size_t)nj + 1, 0);
-		ssv_getsv_params gp;
-		memset(&gp, 0, sizeof(gp));
-		gp.junctions = dj; gp.n_junctions = nj;
-		gp.mean = mean_insert_size; gp.sd = deviation; gp.times = times; gp.disc_min_mapq = min_mapQ;
-		gp.n_windows = 0; gp.depth_min_mapq = min_mapQ;
-		gp.n_targets = ssvh_bam_n_targets(bam); gp.target_len = ssvh_bam_target_lens(bam);
-		if (ranks_path) { // file ranges, counts only: no windows, hence nothing to replay
-			vector<ssvh_bam_part> parts((size_t)n_ranks);
-			if (ssvh_bam_partition(normal_bam_file.c_str(), n_ranks, 0, parts.data()) != 0) die(string("[seeksv] ") + ssvh_partition_last_error());
-			RanksTally T;
-			T.bam_path = normal_bam_file; T.parts = &parts;
-			T.ctxs.assign((size_t)n_ranks, nullptr);
-			T.ctxs[0] = ctx;
-			for (int r = 1; r < n_ranks; ++r) if (ssv_ctx_create(device_of_rank(r, devices), &T.ctxs[(size_t)r]) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
-			T.device_inflate = device_inflate;
-			T.gp = gp;
-			T.n_counts = (size_t)nj; T.counts = counts.data();
-			ranks_tally(T);
-			for (int r = 1; r < n_ranks; ++r) ssv_ctx_destroy(T.ctxs[(size_t)r]);
-		} else {
-			if (ssv_getsv_begin(ctx, &gp) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-			auto scan = [&](const ssv_batch_t &b) { if (ssv_getsv_scan(ctx, &b) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx)); };
-			if (carry.usable) { // the insert-size pass left its source open behind the chunks it read, whose batches are still valid: ONE reading of the file
-				for (auto &k : carry.kept) { scan(k); if (carry.owned) ssv_batch_release(ctx, &k); }
-				carry.kept.clear();
-				carry.src.pump(0, [](const ssv_batch_t &) {}, scan);
-				carry.src.close();
-				carry.usable = false;
-			} else {
-				BatchSource src; // a second handle: `bam` keeps serving the header
-				src.open(normal_bam_file, ctx, device_inflate, "[main_samview] fail to open file for reading.");
-				src.pump(0, [](const ssv_batch_t &) {}, scan);
-				src.close();
-			}
-			int32_t maxd = 0;
-			if (ssv_getsv_finish(ctx, counts.data(), nullptr, 0, nullptr, nullptr, 0, nullptr, &maxd) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(ctx));
-		}
+		RanksTally T; // counts only: no windows, hence nothing to replay
+		T.bam_path = o.normal_bam_file; T.device_inflate = o.device_inflate;
+		memset(&T.gp, 0, sizeof(T.gp));
+		T.gp.junctions = dj; T.gp.n_junctions = nj;
+		T.gp.mean = mean_insert_size; T.gp.sd = deviation; T.gp.times = times; T.gp.disc_min_mapq = o.min_mapQ;
+		T.gp.n_windows = 0; T.gp.depth_min_mapq = o.min_mapQ;
+		T.gp.n_targets = ssvh_bam_n_targets(bam); T.gp.target_len = ssvh_bam_target_lens(bam);
+		T.n_counts = (size_t)nj; T.counts = counts.data();
+		tally_records(ctx, T, ranks_path ? o.n_ranks : 0, o.devices, carry, nullptr);
 		vector<int32_t> prev(J.size() + 1, 0); // a row whose left contig is not in the normal's header reports 0
 		ssvh_plan_fold(plan, counts.data(), prev.data(), nullptr, nullptr, abnormal.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
 		ssvh_plan_destroy(plan);
-	}
-	if (carry.usable) { if (carry.owned) for (auto &k : carry.kept) ssv_batch_release(ctx, &k); carry.kept.clear(); carry.src.close(); carry.usable = false; }
+	} else carry.drop(ctx);
 	pt.lap("discordant_pass");
 	loader.join();
 	if (!load_err.empty()) die(load_err);
 	cerr << load_warnings << isize_report;
 	pt.lap("normal_clusters (wait: read beside the passes)");
-	probe_normal_clusters(rows, normal.clip3, normal.clip5, offset, min_map_rate);
+	probe_normal_clusters(rows, normal.clip3, normal.clip5, o.offset, o.min_map_rate);
 	pt.lap("cluster_lookups");
 	pt.lap("discordant_pass");
 	size_t k = 0;
@@ -1979,11 +2004,13 @@ static int cmd_somatic(int argc, char **argv)
 		fout << row.text << '\t' << row.normal_left_reads << '\t' << row.normal_right_reads << '\t' << normal_abnormal << endl;
 	}
 	pt.lap("output");
-	release_ctx(ctx);
+	release_ctx(ctx, nullptr);
 	ssvh_bam_close(bam);
 	pt.lap("teardown");
 	return 0;
 }
+
+static int cmd_somatic(int argc, char **argv) { return somatic_main(parse_somatic(argc, argv)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // seeksv realign: prefix.clip.fq.gz -> prefix.clip.bam.  The reference's pipeline runs an external aligner here
@@ -2014,27 +2041,35 @@ static int parse_max_occ(const char *arg)
 	return (end != arg && *end == 0 && v >= 1 && v <= 65535) ? (int)v : 0;
 }
 
-// realign's options, for `seeksv realign` itself and for the words of `seeksv run -a` (split == nullptr: -P is not one of them); *gpu stays as it is
-// without -G.  -> index of the first operand
-static int parse_realign_options(int argc, char **argv, int *gpu, int *max_occ, bool *gapped, int *max_alt, bool *split = nullptr)
+// for_run: the words of `seeksv run -a` - -P is not one of them (it is run's own), and no operands
+struct RealignOptions {
+	int gpu = 0, max_occ = 0, max_alt = 0; // -c: 0 = the hash index; -S: 0 = no secondary records
+	bool gpu_given = false, gapped = false, split = false;
+	string fasta, fq, out_bam;
+};
+
+static RealignOptions parse_realign(int argc, char **argv, bool for_run = false)
 {
+	RealignOptions o;
 	int c;
-	optind = 1;
+	optind = 0;
 	while ((c = getopt(argc, argv, "G:c:gS:P")) != -1) {
-		if (c == 'G') *gpu = atoi(optarg);
-		else if (c == 'g') *gapped = true;
-		else if (c == 'P') { if (!split) usage_realign(); *split = true; }
-		else if (c == 'S') { // 0 = no secondary records
+		if (c == 'G') { o.gpu = atoi(optarg); o.gpu_given = true; }
+		else if (c == 'g') o.gapped = true;
+		else if (c == 'P') { if (for_run) usage_realign(); o.split = true; }
+		else if (c == 'S') {
 			char *end = nullptr;
 			const long v = strtol(optarg, &end, 10);
 			if (end == optarg || *end != 0 || v < 1 || v > 16) usage_realign();
-			*max_alt = (int)v;
+			o.max_alt = (int)v;
 		}
-		else if (c == 'c') { if (!(*max_occ = parse_max_occ(optarg))) usage_realign(); }
+		else if (c == 'c') { if (!(o.max_occ = parse_max_occ(optarg))) usage_realign(); }
 		else usage_realign();
 	}
-	if (split && *split && (*gapped || *max_alt > 0)) usage_realign();
-	return optind;
+	if (o.split && (o.gapped || o.max_alt > 0)) usage_realign();
+	if (argc - optind != (for_run ? 0 : 3)) usage_realign();
+	if (!for_run) { o.fasta = argv[optind]; o.fq = argv[optind + 1]; o.out_bam = argv[optind + 2]; }
+	return o;
 }
 
 static bool gz_getline(gzFile f, string &line)
@@ -2143,27 +2178,19 @@ static bool parse_fasta_parallel(const string &path, vector<string> &names, vect
 	return true;
 }
 
-// `seeksv run`: the reference is read (and packed to 2 bits) by a thread of its own while getclip runs
-struct PrereadFasta {
-	string path;
-	std::thread th;
-	bool ok = false;
-	vector<string> names; vector<int32_t> lens; vector<int64_t> offs; vector<uint64_t> words;
-};
-static PrereadFasta &g_preread = *new PrereadFasta; // (never destroyed: die() may exit while its thread runs)
-
 // the reference: names, lengths, 2-bit bases (anything but ACGT becomes a position-dependent pseudo-random base, like bwa's index)
 struct Reference { vector<string> names; vector<int32_t> lens; vector<int64_t> offs = vector<int64_t>(1, 0); vector<uint64_t> words; };
-static void read_reference(const string &fasta, Reference &R)
+// (pre: `seeksv run` started reading this file beside getclip - the thread is joined and what it parsed is taken)
+static void read_reference(const string &fasta, Reference &R, PrereadFasta *pre = nullptr)
 {
 	vector<string> &names = R.names; vector<int32_t> &lens = R.lens; vector<int64_t> &offs = R.offs; vector<uint64_t> &words = R.words;
 	const bool fasta_check = getenv("SSV_FASTA_CHECK") != nullptr; // (tests: the serial reader runs too and must agree)
 	vector<string> p_names; vector<int32_t> p_lens; vector<int64_t> p_offs(1, 0); vector<uint64_t> p_words;
 	bool parsed;
-	if (g_preread.th.joinable() && g_preread.path == fasta) { // `seeksv run` read the reference beside getclip
-		g_preread.th.join();
-		parsed = g_preread.ok;
-		p_names.swap(g_preread.names); p_lens.swap(g_preread.lens); p_offs.swap(g_preread.offs); p_words.swap(g_preread.words);
+	if (pre && pre->th.joinable()) {
+		pre->th.join();
+		parsed = pre->ok;
+		p_names.swap(pre->names); p_lens.swap(pre->lens); p_offs.swap(pre->offs); p_words.swap(pre->words);
 	} else parsed = parse_fasta_parallel(fasta, p_names, p_lens, p_offs, p_words);
 	if (parsed && !fasta_check) { names.swap(p_names); lens.swap(p_lens); offs.swap(p_offs); words.swap(p_words); }
 	else {
@@ -2378,49 +2405,47 @@ static string realign_summary(const AlignedRecords &A, int64_t dropped, int max_
 	return t;
 }
 
-static void resident_alignments(seeksv::AlnRecords &R)
+static void resident_alignments(const RunSession &run, seeksv::AlnRecords &R)
 {
-	const AlignedRecords &A = *g_resident.aln.rec;
+	const AlignedRecords &A = *run.aln.rec;
 	R.n = A.size(); R.tid = A.tid.data(); R.pos = A.pos.data(); R.flag = A.flag.data(); R.n_cigar = A.ncig.data(); R.mapq = A.mapq.data();
-	R.cigar_off = A.cig_off.data(); R.cigar = A.cig.data(); R.qname = A.qn.data(); R.target_names = g_resident.aln.names;
+	R.cigar_off = A.cig_off.data(); R.cigar = A.cig.data(); R.qname = A.qn.data(); R.target_names = run.aln.names;
 }
 
 static void read_fastq_lines(const string &fq, string &text, vector<Line> &seqs, vector<Line> &quals, vector<Line> *names_out);
 
-static int cmd_realign(int argc, char **argv)
+static int realign_main(const RealignOptions &o)
 {
-	int gpu = 0, max_occ = 0, max_alt = 0;
-	bool gapped = false, split = false;
-	if (argc - parse_realign_options(argc, argv, &gpu, &max_occ, &gapped, &max_alt, &split) != 3) usage_realign();
-	const string fasta = argv[optind], fq = argv[optind + 1], out_bam = argv[optind + 2];
 	PhaseTimer pt;
 	Reference R;
-	read_reference(fasta, R);
+	read_reference(o.fasta, R);
 	pt.lap("read reference");
 	// ---- clipped sequences: the FASTQ file (its gzip members inflated side by side), cut into lines in place (the newline behind a line becomes its
 	//      terminator: the sequences are the read names of the BAM records below) ----
 	vector<Line> seqs, quals, names; // (names: -P only)
 	string text;
-	read_fastq_lines(fq, text, seqs, quals, split ? &names : nullptr);
+	read_fastq_lines(o.fq, text, seqs, quals, o.split ? &names : nullptr);
 	pt.lap("read fastq");
-	ssv_ctx *ctx = acquire_ctx(gpu);
+	ssv_ctx *ctx = acquire_ctx(o.gpu, nullptr);
 	int64_t dropped = 0;
-	build_realign_index(ctx, R, max_occ, &dropped);
+	build_realign_index(ctx, R, o.max_occ, &dropped);
 	pt.lap("index");
 	AlignedRecords A;
-	align_lines(ctx, seqs, quals, A, gapped, max_alt, split ? &names : nullptr);
+	align_lines(ctx, seqs, quals, A, o.gapped, o.max_alt, o.split ? &names : nullptr);
 	pt.lap("align");
 	A.seqqual.resize(A.seqqual.size() + 16, 0);
 	// clip.bam is read back once, by getsv's join: its BGZF blocks are literal-only Huffman blocks (huff_gz.h: 4 x the speed of zlib level 1 on these
 	// records, 1.6 x the bytes) unless SSV_BGZF_LEVEL asks for zlib
 	setenv("SSV_BGZF_LEVEL", "-1", 0);
-	write_clip_bam(out_bam, R, A);
+	write_clip_bam(o.out_bam, R, A);
 	pt.lap("write bam");
-	cerr << realign_summary(A, dropped, max_occ, gapped, max_alt, split) << endl;
+	cerr << realign_summary(A, dropped, o.max_occ, o.gapped, o.max_alt, o.split) << endl;
 	ssv_realign_free(ctx);
-	release_ctx(ctx);
+	release_ctx(ctx, nullptr);
 	return 0;
 }
+
+static int cmd_realign(int argc, char **argv) { return realign_main(parse_realign(argc, argv)); }
 
 // A FASTQ file (its gzip members inflated side by side) as one text, cut into lines in place (the newline behind a line becomes its terminator); names != nullptr (-P):
 // the reads' names too.  `seeksv realign` and the aligner step of `seeksv run -N` read prefix.clip.fq.gz through this.
@@ -2465,7 +2490,7 @@ struct RunAligner {
 	std::thread th;
 	std::mutex mu;
 	std::condition_variable cv;
-	struct Work { vector<ResidentBam::Piece *> pass; vector<Line> seqs, quals; }; // a pass of getclip's pieces, or (`run -N`) lines cut out of the finished FASTQ file
+	struct Work { vector<RunSession::Piece *> pass; vector<Line> seqs, quals; }; // a pass of getclip's pieces, or (`run -N`) lines cut out of the finished FASTQ file
 	std::deque<Work> todo;
 	bool done = false;
 	Reference R;
@@ -2477,14 +2502,14 @@ struct RunAligner {
 	bool keep_index = false; // `seeksv run -P`: context and index outlive the thread, for the split leg (release_index)
 	ssv_ctx *kept_ctx = nullptr;
 	double t_index = 0, t_align = 0, t_wait_ref = 0;
-	void start(int device, const string &fasta)
+	void start(int device, const string &fasta, PrereadFasta *pre)
 	{
-		th = std::thread([this, device, fasta] {
+		th = std::thread([this, device, fasta, pre] {
 			auto now = [] { return std::chrono::steady_clock::now(); };
 			auto t0 = now();
 			ssv_ctx *ctx = nullptr;
 			if (ssv_ctx_create(device, &ctx) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(nullptr));
-			read_reference(fasta, R);
+			read_reference(fasta, R, pre);
 			t_wait_ref = std::chrono::duration<double>(now() - t0).count();
 			t0 = now();
 			build_realign_index(ctx, R, max_occ, &dropped);
@@ -2500,9 +2525,9 @@ struct RunAligner {
 				}
 				t0 = now();
 				vector<Line> &seqs = work.seqs, &quals = work.quals;
-				for (ResidentBam::Piece *p : work.pass) {
+				for (RunSession::Piece *p : work.pass) {
 					char *base = p->fq.empty() ? nullptr : &p->fq[0];
-					for (const ResidentBam::FqRef &r : p->reads) {
+					for (const RunSession::FqRef &r : p->reads) {
 						base[r.seq_off + r.seq_len] = 0; base[r.qual_off + r.qual_len] = 0; // (the newline behind a line becomes its terminator: the file is written)
 						seqs.push_back(Line{base + r.seq_off, (int)r.seq_len}); quals.push_back(Line{base + r.qual_off, (int)r.qual_len});
 					}
@@ -2523,7 +2548,7 @@ struct RunAligner {
 		if (kCleanExit) ssv_ctx_destroy(kept_ctx); else ssv_sync(kept_ctx);
 		kept_ctx = nullptr;
 	}
-	void submit(const vector<ResidentBam::Piece *> &pass)
+	void submit(const vector<RunSession::Piece *> &pass)
 	{
 		{ std::lock_guard<std::mutex> lk(mu); todo.emplace_back(); todo.back().pass = pass; }
 		cv.notify_all();
@@ -2546,7 +2571,7 @@ struct RunAligner {
 // pieces of SSV_REALIGN_SPLIT_PIECE reads (1 << 22; tests make it small), ssv_realign_split_batch lays every piece's records out in HBM, and the -F pass of
 // the getsv context scans them there (same GPU, same process; the call has synchronised).  A read's two records lie in one piece.  Called by cmd_getsv
 // where it runs its -F pass; ssv_rt_finish and the fold into the junction map as there.
-static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, JunctionMap &junction2other)
+static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx, int min_mapq, JunctionMap &junction2other)
 {
 	ssv_ctx *actx = aligner.kept_ctx;
 	if (!actx) die("[seeksv] run -P: the aligner's index is gone");
@@ -2569,8 +2594,8 @@ static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, Ju
 		if (ssv_realign_split_batch(actx, reads.seqs.data(), reads.seq_off.data(), n, reads.quals.data(), reads.names.data(), reads.name_off.data(), hits.data(), mates.data(), &b, &nm) != SSV_OK)
 			die(string("[seeksv] realign query: ") + ssv_last_error(actx));
 		const auto t1 = now();
-		if (ssv_rt_scan(rt_ctx, &b, &nm) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx));
-		if (ssv_sync(rt_ctx) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx)); // (the next piece overwrites the batch)
+		check(rt_ctx, ssv_rt_scan(rt_ctx, &b, &nm));
+		check(rt_ctx, ssv_sync(rt_ctx)); // (the next piece overwrites the batch)
 		t_align += secs(t0, t1); t_scan += secs(t1, now());
 		for (int64_t i = 0; i < n; ++i) {
 			const ssv_realign_hit &h = hits[(size_t)i];
@@ -2582,7 +2607,7 @@ static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, Ju
 	};
 	// the texts are cut side by side, a group of them at a time (every one holds whole records), and put together into pieces in their order
 	vector<string *> texts;
-	for (auto &file : g_resident.unmapped) for (string &text : file) texts.push_back(&text);
+	for (auto &file : run->unmapped) for (string &text : file) texts.push_back(&text);
 	const size_t group = (size_t)std::max(1, std::min(ssv::effective_cpus(), 32));
 	for (size_t g = 0; g < texts.size(); g += group) {
 		const auto t0 = now();
@@ -2627,10 +2652,10 @@ static void run_split_leg(RunAligner &aligner, ssv_ctx *rt_ctx, int min_mapq, Ju
 			part[k] = seeksv::FastqReads();
 		}
 	}
-	for (auto &file : g_resident.unmapped) file.clear();
+	for (auto &file : run->unmapped) file.clear();
 	flush();
 	ssv_rt_result res;
-	if (ssv_rt_finish(rt_ctx, &res) != SSV_OK) die(string("[seeksv] ") + ssv_last_error(rt_ctx));
+	check(rt_ctx, ssv_rt_finish(rt_ctx, &res));
 	seeksv::apply_readthrough(res, aligner.R.names, junction2other);
 	cerr << realign_summary(S, aligner.dropped, aligner.max_occ, false, 0, true, n_reads) << endl;
 	if (getenv("SSV_TIMING")) cerr << "[timing] (run -P: " << n_reads << " reads, " << res.n_candidates << " candidates, " << res.n_pairs << " pairs; cutting the text " << t_cut << " s, split query + device rows "
@@ -2674,6 +2699,17 @@ static vector<string> split_words(const string &t)
 	return w;
 }
 
+// the words of run's -c / -v / -a through the step's own parser (words[0]: the step's name, as getopt prints it)
+template <class Options> static Options parse_words(const char *step, const string &text, Options (*parse)(int, char **, bool))
+{
+	vector<string> words = {step};
+	for (auto &x : split_words(text)) words.push_back(x);
+	vector<char *> av;
+	for (auto &w : words) av.push_back(const_cast<char *>(w.c_str()));
+	av.push_back(nullptr);
+	return parse((int)words.size(), av.data(), true);
+}
+
 static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
@@ -2692,87 +2728,54 @@ static int cmd_run(int argc, char **argv)
 	}
 	if (argc != optind + 3 || n_ranks < 1) usage_run();
 	const vector<int> devices = ranks_given ? parse_devices(device_list.c_str()) : vector<int>();
-	if (n_ranks > 1) device = device_of_rank(0, devices);
-	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
-	int max_occ = 0;
-	bool gapped = false;
-	int max_alt = 0;
-	vector<string> aln_words = {"realign"}; // (lives while getopt is used below: behind a flag without an argument - "-g" - getopt keeps a pointer into the word it read last)
-	{ // realign's options, parsed as `seeksv realign` parses them; the GPU is run's own -G
-		for (auto &x : split_words(aln_opts)) aln_words.push_back(x);
-		vector<char *> av;
-		for (auto &x : aln_words) av.push_back(const_cast<char *>(x.c_str()));
-		av.push_back(nullptr);
-		int aln_gpu = -1;
-		if (parse_realign_options((int)aln_words.size(), av.data(), &aln_gpu, &max_occ, &gapped, &max_alt) != (int)aln_words.size()) usage_realign();
-		if (aln_gpu != -1) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
-	}
-	{ // refused before anything is written
-		auto has_option = [](const string &opts, const char *optstring, int which) {
-			vector<string> w = {"x"};
-			for (auto &x : split_words(opts)) w.push_back(x);
-			vector<char *> av;
-			for (auto &x : w) av.push_back(const_cast<char *>(x.c_str()));
-			av.push_back(nullptr);
-			const int save = opterr;
-			opterr = 0; optind = 1;
-			bool found = false;
-			for (int o; (o = getopt((int)w.size(), av.data(), optstring)) >= 0;) found = found || o == which;
-			opterr = save; optind = 1;
-			return found;
-		};
-		const char *const sv_optstring = "F:B:t:l:q:Q:w:n:a:b:d:e:m:i:R:f:T:L:rDG:J:ZCN:", *const clip_optstring = "t:q:o:sG:ZCN:H:";
-		// -P: the pass has one source, and the ranks' getclip has another side channel
-		if (split && ranks_given && n_ranks > 1) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N is not supported with it");
-		if (split && has_option(sv_opts, sv_optstring, 'F')) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
-		if (split && has_option(clip_opts, clip_optstring, 'N')) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
-		// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
-		if (n_ranks > 1 && (has_option(clip_opts, clip_optstring, 'N') || has_option(clip_opts, clip_optstring, 'G') || has_option(sv_opts, sv_optstring, 'N') || has_option(sv_opts, sv_optstring, 'G')))
-			die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
-	}
-	PhaseTimer pt;
-	g_resident.ctx = acquire_ctx(device);
-	g_resident.path = bam;
-	// -N n: the ranks of getclip keep their own runs (RunRanks above); rank 0 is this process's context.  Until a file whose contigs come back sends the run down
-	// the one-GPU path (getclip_ranks), nothing is collected in g_resident.
 	const bool ranked = n_ranks > 1;
-	RunRanks &ranks = *new RunRanks; // (never destroyed: die() may exit while the ranks' threads run)
+	if (ranked) device = device_of_rank(0, devices);
+	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
+	// The three steps' options, each through the step's own parser: a usage error or a value out of range ends the run here with the step's usage text, before
+	// the GPU context is asked for and before any file exists.  The GPU of realign is run's own -G.
+	const RealignOptions aln = parse_words("realign", aln_opts, parse_realign);
+	if (aln.gpu_given) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
+	GetclipOptions clip = parse_words("getclip", clip_opts, parse_getclip);
+	GetsvOptions sv = parse_words("getsv", sv_opts, parse_getsv);
+	// refused before anything is written
+	// -P: the pass has one source, and the ranks' getclip has another side channel
+	if (split && ranked) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N is not supported with it");
+	if (split && !sv.connect_bam.empty()) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
+	if (split && clip.ranks_given) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
+	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
+	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
+		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
+	// ... and without it getclip is the single pass the aligner step and the junction stage take their input from (-v "-N n" is `getsv -N` over the file)
+	if (clip.ranks_given || clip.devices_given) die("seeksv run: -N or -G inside -c is not supported; the ranks of a run and their GPUs are run's own -N and -G");
+	// what run decides itself
+	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
+	clip.prefix = prefix; clip.bamfile = bam;
+	sv.device = device; sv.devices = vector<int>(1, device);
+	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
+
+	PhaseTimer pt;
+	RunSession *const run = new RunSession;
+	run->ctx = acquire_ctx(device, nullptr);
 	if (ranked) {
-		ranks.path = bam;
-		ranks.rank.resize((size_t)n_ranks);
-		for (int r = 0; r < n_ranks; ++r) ranks.rank[(size_t)r].device = device_of_rank(r, devices);
-		ranks.rank[0].ctx = g_resident.ctx;
-		g_run_ranks = &ranks;
+		run->ranks.rank.resize((size_t)n_ranks);
+		for (int r = 0; r < n_ranks; ++r) run->ranks.rank[(size_t)r].device = device_of_rank(r, devices);
+		run->ranks.rank[0].ctx = run->ctx;
 	}
-	g_resident.collect = !ranked;
+	run->collect = !ranked;
 	pt.lap("run: gpu_init");
-	g_preread.path = fasta; g_preread.offs.assign(1, 0);
-	g_preread.th = std::thread([] { g_preread.ok = parse_fasta_parallel(g_preread.path, g_preread.names, g_preread.lens, g_preread.offs, g_preread.words); });
+	PrereadFasta &pre = run->preread;
+	pre.th = std::thread([&pre, fasta] { pre.ok = parse_fasta_parallel(fasta, pre.names, pre.lens, pre.offs, pre.words); });
 	RunAligner &aligner = *new RunAligner; // (never destroyed: die() may exit while its thread runs)
-	aligner.max_occ = max_occ; aligner.gapped = gapped; aligner.max_alt = max_alt;
-	aligner.keep_index = split; g_resident.keep_unmapped = split;
-	aligner.start(device, fasta);
-	g_resident.on_pass = [&aligner](const vector<ResidentBam::Piece *> &pass) { aligner.submit(pass); };
-	auto call = [&](int (*fn)(int, char **), vector<string> words) {
-		vector<char *> av;
-		for (auto &w : words) av.push_back(const_cast<char *>(w.c_str()));
-		av.push_back(nullptr);
-		optind = 1;
-		return fn((int)words.size(), av.data());
-	};
-	vector<string> a = {"getclip"};
-	for (auto &w : split_words(clip_opts)) a.push_back(w);
-	if (ranked) { // (without -G the ranks take the machine's GPUs in order, as under `getclip -N`)
-		a.insert(a.end(), {"-Z", "-N", to_string(n_ranks)});
-		if (!device_list.empty()) a.insert(a.end(), {"-G", device_list});
-		a.insert(a.end(), {"-o", prefix, bam});
-	} else a.insert(a.end(), {"-Z", "-G", to_string(device), "-o", prefix, bam});
-	int rc = call(cmd_getclip, a);
-	g_resident.collect = false;
-	g_resident.on_pass = nullptr;
+	aligner.max_occ = aln.max_occ; aligner.gapped = aln.gapped; aligner.max_alt = aln.max_alt;
+	aligner.keep_index = split; run->keep_unmapped = split;
+	aligner.start(device, fasta, &pre);
+	run->on_pass = [&aligner](const vector<RunSession::Piece *> &pass) { aligner.submit(pass); };
+	int rc = getclip_main(clip, run);
+	run->collect = false;
+	run->on_pass = nullptr;
 	pt.lap("run: getclip (decode once, records kept in HBM)");
-	const bool by_ranks = ranked && !ranks.fell_back; // (fell back: from here on this is `seeksv run` without -N)
-	if (!by_ranks) g_run_ranks = nullptr;
+	const RunRanks &ranks = run->ranks;
+	const bool by_ranks = run->ranked(); // (fell back: from here on this is `seeksv run` without -N)
 	if (by_ranks && pt.on)
 		for (int r = 0; r < n_ranks; ++r)
 			cerr << "[timing] (run -N rank " << r << "/" << n_ranks << ": device " << ranks.rank[(size_t)r].device << ", " << ranks.rank[(size_t)r].kept << " records kept, "
@@ -2785,52 +2788,45 @@ static int cmd_run(int argc, char **argv)
 	}
 	aligner.finish();
 	pt.lap("run: realign (what was left of it behind getclip)");
+	// clip.bam's BGZF blocks are literal-only Huffman blocks (huff_gz.h) unless SSV_BGZF_LEVEL asks for zlib; it is written under a temporary name and renamed
+	// when it is whole: a run that dies in getsv must not leave half a clip.bam where `seeksv getsv` would find it
+	setenv("SSV_BGZF_LEVEL", "-1", 0);
+	const string clip_bam = sv.clip_bam;
+	auto aligner_lines = [&] {
+		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
+		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
+	};
 	if (by_ranks && rc == 0) {
-		// the junction stage of getsv reads prefix.clip.gz and prefix.clip.bam back as files: clip.bam is written whole first (under a temporary name, renamed when it
-		// is whole), then the getsv step runs over the ranks' records where they lie
-		setenv("SSV_BGZF_LEVEL", "-1", 0);
-		const string clip_bam = prefix + ".clip.bam";
+		// the junction stage of getsv reads prefix.clip.gz and prefix.clip.bam back as files: clip.bam is written whole first, then the getsv step runs over the
+		// ranks' records where they lie
 		write_clip_bam(clip_bam + ".tmp", aligner.R, aligner.A);
 		if (rename((clip_bam + ".tmp").c_str(), clip_bam.c_str()) != 0) die("Cannot write file " + clip_bam);
 		pt.lap("run: clip.bam written");
-		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
-		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
-		a = {"getsv"};
-		for (auto &w : split_words(sv_opts)) a.push_back(w);
-		a.insert(a.end(), {"-Z", "-N", to_string(n_ranks)});
-		if (!device_list.empty()) a.insert(a.end(), {"-G", device_list});
-		a.insert(a.end(), {clip_bam, bam, prefix + ".clip.gz", prefix + ".sv.txt", prefix + ".unmapped.clip.fq"});
-		rc = call(cmd_getsv, a);
+		aligner_lines();
+		sv.device_inflate = true; sv.n_ranks = n_ranks; sv.devices = devices;
+		rc = getsv_main(sv, run);
 	} else if (rc == 0) {
-		// clip.bam is read back by nobody in this process (getsv's join takes the records from memory): it is written beside getsv, by a thread that is joined below;
-		// its BGZF blocks are literal-only Huffman blocks (huff_gz.h) unless SSV_BGZF_LEVEL asks for zlib
-		setenv("SSV_BGZF_LEVEL", "-1", 0);
-		g_resident.aln.bam_path = prefix + ".clip.bam"; g_resident.aln.rec = &aligner.A; g_resident.aln.names = aligner.R.names;
-		// (written under a temporary name and renamed when it is whole: a run that dies in getsv must not leave half a clip.bam where `seeksv getsv` would find it)
-		g_resident.bam_writer = std::thread([&aligner] { write_clip_bam(g_resident.aln.bam_path + ".tmp", aligner.R, aligner.A); });
-		cerr << realign_summary(aligner.A, aligner.dropped, aligner.max_occ, aligner.gapped, aligner.max_alt) << endl;
-		if (pt.on) cerr << "[timing] (aligner beside getclip: context + reference " << aligner.t_wait_ref << " s, index " << aligner.t_index << " s, align " << aligner.t_align << " s)" << endl;
-		if (split) g_run_split_leg = [&aligner](ssv_ctx *rt_ctx, int min_mapq, JunctionMap &jm) { run_split_leg(aligner, rt_ctx, min_mapq, jm); };
-		a = {"getsv"};
-		for (auto &w : split_words(sv_opts)) a.push_back(w);
-		a.insert(a.end(), {"-G", to_string(device), prefix + ".clip.bam", bam, prefix + ".clip.gz", prefix + ".sv.txt", prefix + ".unmapped.clip.fq"});
-		rc = call(cmd_getsv, a);
-		g_run_split_leg = nullptr;
+		// clip.bam is read back by nobody in this process (getsv's join takes the records from memory): it is written beside getsv, by a thread that is joined below
+		run->aln.rec = &aligner.A; run->aln.names = aligner.R.names;
+		run->bam_writer = std::thread([&aligner, clip_bam] { write_clip_bam(clip_bam + ".tmp", aligner.R, aligner.A); });
+		aligner_lines();
+		if (split) run->split_leg = [&aligner, run](ssv_ctx *rt_ctx, int min_mapq, JunctionMap &jm) { run_split_leg(aligner, run, rt_ctx, min_mapq, jm); };
+		rc = getsv_main(sv, run);
+		run->split_leg = nullptr;
 	}
 	aligner.release_index(); // (run -P whose getsv did not get as far as the leg)
 	pt.lap("run: getsv (records in HBM)");
-	if (g_resident.bam_writer.joinable()) {
-		g_resident.bam_writer.join();
-		if (rename((g_resident.aln.bam_path + ".tmp").c_str(), g_resident.aln.bam_path.c_str()) != 0) die("Cannot write file " + g_resident.aln.bam_path);
+	if (run->bam_writer.joinable()) {
+		run->bam_writer.join();
+		if (rename((clip_bam + ".tmp").c_str(), clip_bam.c_str()) != 0) die("Cannot write file " + clip_bam);
 		pt.lap("run: clip.bam written");
 	}
-	ssv_ctx *ctx = g_resident.ctx;
-	g_run_ranks = nullptr;
-	if (kCleanExit) ranks.release(); // (the ranks' batches, and every context but rank 0's - which is `ctx`)
+	ssv_ctx *ctx = run->ctx;
+	if (kCleanExit) run->ranks.release(); // (the ranks' batches, and every context but rank 0's - which is `ctx`)
 	else for (size_t r = 1; r < ranks.rank.size(); ++r) if (ranks.rank[r].ctx) ssv_sync(ranks.rank[r].ctx);
 	if (kCleanExit) {
-		for (auto &b : g_resident.batches) ssv_batch_release(ctx, &b);
-		g_resident.ctx = nullptr;
+		for (auto &b : run->batches) ssv_batch_release(ctx, &b);
+		run->ctx = nullptr;
 		ssv_ctx_destroy(ctx);
 	} else ssv_sync(ctx);
 	return rc;

@@ -38,3 +38,43 @@ def test_zero_ranks_print_the_usage_text(tmp_path):
             r = subprocess.run([SEEKSV, cmd, "-N", n] + operands, capture_output=True, text=True)
             assert r.returncode == 1 and f"Usage: seeksv {cmd}" in r.stderr, (cmd, n)
     assert os.listdir(str(tmp_path)) == []
+
+
+def _run(tmp_path, *options):
+    """`seeksv run <options> a.bam ref.fa <tmp>/p` from inside the empty directory; no input exists: the command line is judged before anything is opened."""
+    return subprocess.run([SEEKSV, "run", *options, "a.bam", "ref.fa", str(tmp_path / "p")], capture_output=True, text=True, cwd=str(tmp_path))
+
+
+def _one_line(r):
+    lines = r.stderr.splitlines()
+    assert r.returncode == 1 and len(lines) == 1 and lines[0].startswith("seeksv run: "), r.stderr
+    return lines[0]
+
+
+def test_ranks_or_devices_inside_c_without_runs_own_N_are_refused(tmp_path):
+    # (getclip's ranks would bypass what the aligner step and the junction stage take from the single pass; -v "-N n" stays `getsv -N` over the file)
+    for words in ("-N 2", "-G 1"):
+        assert "-c" in _one_line(_run(tmp_path, "-c", words)), words
+    assert os.listdir(str(tmp_path)) == []
+
+
+def test_errors_inside_the_step_options_end_the_run_before_anything_is_written(tmp_path):
+    r = _run(tmp_path, "-v", "-l 95")  # getsv's range check
+    assert r.returncode == 1 and r.stderr.startswith("Usage: seeksv getsv"), r.stderr
+    r = _run(tmp_path, "-c", "-x")
+    assert r.returncode == 1 and "Usage: seeksv getclip" in r.stderr and "invalid option" in r.stderr, r.stderr
+    for words in ("-m -1", "-N 0"):
+        r = _run(tmp_path, "-v", words)
+        assert r.returncode == 1 and r.stderr.startswith("Usage: seeksv getsv"), (words, r.stderr)
+    r = _run(tmp_path, "-a", "-c 0")  # as `seeksv realign -c 0`
+    alone = subprocess.run([SEEKSV, "realign", "-c", "0", "ref.fa", "p.clip.fq.gz", "p.clip.bam"], capture_output=True, text=True, cwd=str(tmp_path))
+    assert alone.returncode == 1 and alone.stderr.startswith("Usage: seeksv realign")
+    assert (r.returncode, r.stdout, r.stderr) == (alone.returncode, alone.stdout, alone.stderr)
+    assert os.listdir(str(tmp_path)) == []
+
+
+def test_the_refusals_of_P_and_N_need_no_gpu(tmp_path):
+    assert "-P" in _one_line(_run(tmp_path, "-N", "2", "-P"))
+    assert "-N or -G inside -c or -v" in _one_line(_run(tmp_path, "-N", "2", "-c", "-N 2"))
+    assert "-N or -G inside -c or -v" in _one_line(_run(tmp_path, "-N", "2", "-v", "-G 1"))
+    assert os.listdir(str(tmp_path)) == []
