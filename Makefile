@@ -14,12 +14,13 @@ CLI_SRC  = seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp see
 CLI_DEPS = seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.h
 HIP_DEPS = $(wildcard seeksv_amd/csrc/*.h) $(wildcard seeksv_amd/csrc/*.inc) $(wildcard seeksv_amd/csrc/*.hip) include/seeksv_hip.h
 
-all: host hip synth cli
+all: host hip synth cli primcheck
 
 host: $(LIBDIR)/libseeksv_host.so
 hip: $(LIBDIR)/libseeksv_hip.so
 synth: $(LIBDIR)/libseeksv_synth.so $(LIBDIR)/libseeksv_synth_cpu.so
 cli: seeksv_amd/bin/seeksv
+primcheck: $(LIBDIR)/libseeksv_primcheck.so
 
 $(LIBDIR)/libseeksv_host.so: $(HOST_SRC) $(wildcard seeksv_amd/host/*.h) include/seeksv_host.h include/seeksv_hip.h
 	mkdir -p $(LIBDIR)
@@ -43,6 +44,11 @@ $(LIBDIR)/libseeksv_synth.so: seeksv_amd/csrc/synth.hip seeksv_amd/csrc/synth_co
 $(LIBDIR)/libseeksv_synth_cpu.so: seeksv_amd/csrc/synth_cpu.cpp seeksv_amd/csrc/synth_core.h
 	mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -shared -o $@ seeksv_amd/csrc/synth_cpu.cpp
+
+# tests only: scan.h, radix_sort.h and tile_sort.h behind C entry points of their own (tests/test_primitives_gpu.py); not part of libseeksv_hip.so
+$(LIBDIR)/libseeksv_primcheck.so: tests/native/prim_check.hip seeksv_amd/csrc/scan.h seeksv_amd/csrc/radix_sort.h seeksv_amd/csrc/tile_sort.h seeksv_amd/csrc/common.h
+	mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -Iseeksv_amd/csrc -shared -o $@ tests/native/prim_check.hip
 
 oracle:
 	$(MAKE) -C oracle liboracle.so
@@ -77,4 +83,4 @@ wire-check:
 clean:
 	rm -rf $(LIBDIR) && $(MAKE) -C oracle clean
 
-.PHONY: all host hip synth cli oracle oracle-ref asan wire-check clean
+.PHONY: all host hip synth cli primcheck oracle oracle-ref asan wire-check clean

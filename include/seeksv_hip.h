@@ -349,7 +349,9 @@ int ssv_clip_table_wait_prev(ssv_ctx *ctx, ssv_cluster_table *out);
 /* ---- getsv pass 1: replaces CalculateInsertsizeDeviation (cluster.cpp:15-83) ---------------- */
 
 int ssv_isize_begin(ssv_ctx *ctx, int32_t min_mapq, int64_t max_pairs);
-/* *done is set to 1 once max_pairs qualifying records have been seen (the reference breaks there). */
+/* *done is set to 1 once max_pairs qualifying records have been seen (the reference breaks there).  The reference compares the count
+   with max_pairs for EQUALITY after every record it does not skip (cluster.cpp:68): max_pairs < 0 is no limit, and max_pairs == 0 ends the
+   pass at the first such record when that one does not qualify and is no limit when it does. */
 int ssv_isize_accumulate(ssv_ctx *ctx, const ssv_batch_t *b, int32_t *done);
 /* Returns n_pairs==0 exactly when the reference returns 1 and leaves mean/sd untouched. */
 int ssv_isize_finish(ssv_ctx *ctx, int64_t *n_pairs, int32_t *mean, int32_t *sd);

@@ -58,6 +58,17 @@ __global__ __launch_bounds__(BLOCK) void k_isize_count(DevBatch b, int min_mapq,
 	if (threadIdx.x == 0) tile_cnt[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
+// read_pair_used == 0 only (ssv_isize_accumulate): the first record of the batch that is not skipped before cluster.cpp:68 (MAPQ, hard clip) as
+// 2 * index + (it qualifies) in *first, which the caller set to ~0
+__global__ __launch_bounds__(BLOCK) void k_isize_first_compared(DevBatch b, int min_mapq, unsigned long long *__restrict__ first)
+{
+	const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+	if (i >= b.n) return;
+	const RecLine r = rec_load(b.rec, i);
+	if (r.mapq() < min_mapq || is_hard_clip(b, r)) return;
+	atomicMin(first, (unsigned long long)i * 2 + (isize_qualifies(b, r, min_mapq) ? 1 : 0));
+}
+
 // pass B: the qualifying record with file-order ordinal o < max_pairs stores its isize at vals[o]
 __global__ __launch_bounds__(BLOCK) void k_isize_collect(const int32_t *__restrict__ val, int64_t n, const uint32_t *__restrict__ tile_base, int64_t count_before, int64_t max_pairs,
                                                          int32_t *__restrict__ vals)

@@ -1,7 +1,7 @@
 // isize_api.inc - C ABI of the insert-size statistics (included by seeksv_hip.hip; kernels in getsv_kernels.h)
 
 struct ssv_isize_state {
-	bool active = false;
+	bool active = false, undecided = false;
 	int min_mapq = 0;
 	int64_t max = 0, count = 0;
 	DBuf vals, acc, tmp;
@@ -13,7 +13,9 @@ int ssv_isize_begin(ssv_ctx *c, int32_t min_mapq, int64_t max_pairs)
 	ssv_isize_state &Z = *c->isz;
 	HIPCHECK(c, hipSetDevice(c->device));
 	c->pf.clear();
-	Z.active = true; Z.min_mapq = min_mapq; Z.max = max_pairs; Z.count = 0;
+	// cluster.cpp:68 ends the pass when the count EQUALS read_pair_used, after every record that is not skipped: a negative value is never
+	// met (no cap), and 0 only by the first such record, when that one does not qualify (ssv_isize_accumulate decides it there)
+	Z.active = true; Z.min_mapq = min_mapq; Z.max = max_pairs < 0 ? INT64_MAX : max_pairs; Z.count = 0; Z.undecided = max_pairs == 0;
 	return SSV_OK;
 }
 
@@ -23,10 +25,24 @@ int ssv_isize_accumulate(ssv_ctx *c, const ssv_batch_t *b, int32_t *done)
 	ssv_isize_state &Z = *c->isz;
 	if (!Z.active) { c->err = "ssv_isize_accumulate before ssv_isize_begin"; return SSV_E_STATE; }
 	HIPCHECK(c, hipSetDevice(c->device));
-	// the reference tests `read_pair_number == read_pair_used` after every record (cluster.cpp:68): with max_pairs == 0 it stops at once
-	if (Z.count >= Z.max || b->n == 0) { if (done) *done = Z.count >= Z.max; return SSV_OK; }
+	if ((Z.count >= Z.max && !Z.undecided) || b->n == 0) { if (done) *done = Z.count >= Z.max && !Z.undecided; return SSV_OK; }
 	DevBatch d;
 	CHECK(stage_batch(c, b, d));
+	if (Z.undecided) {
+		// read_pair_used == 0: the first record that reaches the comparison of cluster.cpp:68 ends the pass with no pair when it does not
+		// qualify; when it does, the count is 1 there and never 0 again: every qualifying record of the file is taken
+		CHECK(ensure(c, c->totals, 64)); CHECK(ensure_host(c, c->h_totals, 64));
+		HIPCHECK(c, hipMemsetAsync(c->totals.p, 0xff, 8, c->st));
+		k_isize_first_compared<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, Z.min_mapq, P<unsigned long long>(c->totals));
+		HIPCHECK(c, hipGetLastError());
+		HIPCHECK(c, hipMemcpyAsync(c->h_totals.p, c->totals.p, 8, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+		const unsigned long long first = *P<unsigned long long>(c->h_totals);
+		if (first == ~0ull) { if (done) *done = 0; return SSV_OK; } // every record skipped: the next batch decides
+		Z.undecided = false;
+		if (!(first & 1)) { if (done) *done = 1; return SSV_OK; }  // (Z.count == Z.max == 0 from here on)
+		Z.max = INT64_MAX;
+	}
 	ProfScope ps(c, P_ISIZE, d.n);
 	const int64_t ntiles = (d.n + ISZ_TILE - 1) / ISZ_TILE;
 	CHECK(ensure(c, c->tile_cnt, ntiles * 4)); CHECK(ensure(c, c->tile_base, ntiles * 4));

@@ -35,10 +35,13 @@ __global__ __launch_bounds__(BLOCK) void k_scan_reduce(const TIn *__restrict__ i
 // padded by one slot so that the walks of a wavefront's lanes fall into different banks), one block-level scan, coalesced write-back.
 // This kernel runs once per device-wide scan, ~25 times per pass of the path: walking the runs in global memory (a dependent load per
 // element) took 13-40 us per call, 0.2 ms per pass.
+constexpr int SCAN_SUMS_PER = 16;
+constexpr int SCAN_SUMS_CHUNK = BLOCK * SCAN_SUMS_PER; // 4096 sums per trip through LDS
+
 template <typename TOut>
 __device__ __forceinline__ void scan_sums_body(TOut *__restrict__ sums, int64_t m, TOut carry_in, TOut *__restrict__ total)
 {
-	constexpr int PER = 16, CH = BLOCK * PER;
+	constexpr int PER = SCAN_SUMS_PER, CH = SCAN_SUMS_CHUNK;
 	__shared__ TOut buf[CH + BLOCK];
 	__shared__ TOut lds[WAVES_PER_BLOCK + 1];
 	TOut carry = carry_in;

@@ -4,17 +4,20 @@
 // The right-clip ('3') events of a coordinate-sorted BAM come out in record order, i.e. by start position, while their bin key is the
 // alignment END (start + reference span): the list is sorted up to displacements of a few places (events whose reads start within one read span
 // of each other: ~3 places at 300x).  A full LSD radix sort of it (five passes over keys and values) was 0.33 ms of the 0.6 ms event sort; two
-// passes of 2048-element bitonic sorts in LDS still 0.22 ms (66 barrier stages each).  If no element is WS_W or more places from its sorted
-// position the ranks are exact; that is CHECKED, not assumed (every output slot written once, the result strictly increasing): long
-// reference skips or pathological depth fall back to the radix sort.  Order is by (key, value): values are the events' ordinals, so equal keys
-// keep BAM order like a stable sort.
+// passes of 2048-element bitonic sorts in LDS still 0.22 ms (66 barrier stages each).  The ranks are exact if every INVERTED PAIR (an earlier
+// element greater than a later one) is at most WS_W places apart: then every element sees all the elements it has to pass.  A bound on how far an
+// element stands from its sorted position does not give that: two elements each displaced by less than WS_W can be inverted 50 places apart
+// (tests/primitives_model.py:ws_displacement_counter_example, maximum displacement 31).  So exactness is CHECKED, not assumed: n stores into n
+// slots with none left unwritten are a permutation, and a strictly increasing permutation of the input is the sorted list; anything else - long
+// reference skips, pathological depth - raises the flag and falls back to the radix sort.  Order is by (key, value): values are the events'
+// ordinals, so equal keys keep BAM order like a stable sort (a value of 0xffffffff reads as an unwritten slot and raises the flag).
 #pragma once
 
 #include "common.h"
 
 namespace ssv {
 
-constexpr int WS_W = 32;      // window: displacements below this are repaired (the pass is bound by its LDS reads: 2 W pairs per element)
+constexpr int WS_W = 32;      // window: inverted pairs up to this many places apart are repaired (the pass is bound by its LDS reads: 2 W pairs per element)
 constexpr int WS_TILE = 1024; // elements per workgroup (4 per thread)
 
 __device__ __forceinline__ bool ts_greater(uint64_t ka, uint32_t va, uint64_t kb, uint32_t vb) { return ka > kb || (ka == kb && va > vb); }
