@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
+                             v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
                              v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
                              v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
                              v9 (additive, same version): ssv_realign_query_gapped, ssv_realign_gap (`seeksv realign -g`).
@@ -566,6 +567,22 @@ int ssv_samdec_decode(ssv_ctx *ctx, const void *text, size_t bytes, int mem, int
  * off[i] = where line i starts.  Valid as long as that batch. */
 int ssv_samdec_names(ssv_ctx *ctx, ssv_names_t *out);
 int ssv_samdec_last(ssv_ctx *ctx, ssv_samdec_info *info);
+/* A coordinate-sorted ORIGINAL as SAM text (what getclip and `seeksv run` read; clip_reads.h:363-384 opens every name without ".bam" as text).  Between
+ * ssv_samdec_begin and the first ssv_samdec_decode, else SSV_E_ARG; without it every call behaves as described above.  With it each batch is, bit for bit, what
+ * ssv_bamdec_decode(keep_all_seq) gives for the BAM of the same records:
+ *   keep_all_seq == 0: a record ships ceil(l / 2) + l bytes of bases + qualities when its first or last CIGAR operation is S and nothing otherwise
+ *     (seq_off = SSV_NO_SEQ), xc is set for soft-clipped records only, the record lines say the same;
+ *   tid_runs / n_tid_runs of the batch are filled (up to 64 runs);
+ *   more than 65536 contig changes among a chunk's mapped-pair records: SSV_E_ARG, the text is not coordinate sorted.
+ * Consequence: a QUAL byte below 33 is refused only in lines whose qualities are read - lines that ship and UNMAP|MUNMAP lines (libbam refuses none).  The SEQ /
+ * QUAL / CIGAR length checks hold for every line. */
+int ssv_samdec_sorted(ssv_ctx *ctx, int keep_all_seq);
+/* ... and the lists of the last decoded chunk, in the BAM decoder's struct: n_records, last_tid (contigs carried across chunks, 0 before the first record),
+ * n_tid_runs / tid_run_index / tid_run_tid, and unmapped_raw / unmapped_bytes: every line whose flag as decoded (a '*' CIGAR sets 4) has UNMAP or MUNMAP, as
+ * a BAM record in file order - block_size, the 32 core bytes (bin = 0), name and NUL, CIGAR operations, packed bases, qualities (QUAL '*': 0xff), no optional
+ * fields - which ssvh_raw_record_fastq reads like the BAM decoder's.  inflated_bytes: the bytes of text the call was given; tail_offset, repaired_blocks: 0.
+ * Lifetimes as for ssv_bamdec_last (unmapped_raw: two page-locked buffers in turn, valid until the decode after the next one).  SSV_E_STATE without the mode. */
+int ssv_samdec_lists(ssv_ctx *ctx, ssv_bamdec_info *out);
 
 /* ---- the clipped-sequence re-alignments of `getsv` out of a decoded batch (getsv.h:437-446 opens every name without ".bam" as SAM text) ----
  * What the host join (InputSoftInfoStoreBreakpoint + GetAlignInfo, getsv.h:423-541, getsv.cpp:25-71) reads of every record of clip.bam / clip.sam: tid, pos, flag,

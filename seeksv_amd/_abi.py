@@ -410,6 +410,8 @@ def hip_lib():
         lib.ssv_samdec_decode.argtypes = [V, V, C.c_size_t, C.c_int, C.c_int, C.POINTER(Batch)]
         lib.ssv_samdec_names.argtypes = [V, C.POINTER(Names)]
         lib.ssv_samdec_last.argtypes = [V, C.POINTER(SamdecInfo)]
+        lib.ssv_samdec_sorted.argtypes = [V, C.c_int]
+        lib.ssv_samdec_lists.argtypes = [V, C.POINTER(BamdecInfo)]
         lib.ssv_aln_pack.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(AlnCols)]
         lib._typed = True
     return lib

@@ -13,12 +13,12 @@ struct ssv_bamdec_state {
 	bool any_order = false;       // ssv_bamdec_any_order: chunks with more contig changes than the list holds go through without the list
 	DBuf crc_tab;
 	uint64_t expect_inflated = 0; // ssv_bamdec_expect: the largest chunk that will come (buffers are sized for it by the first, smaller one)
-	DBuf inf_scratch, inf_dbg, tokens, tok_off, n_tok, carrybuf, comp, blocks, u_off, stream, status, chain, count, base, rec_off, stitch, tile_last, tile_prev, runs, small;
-	DBuf raw_runs; HBuf h_raw_runs; std::vector<ssv_tid_run> tid_runs; // the batch's tid column as runs (ssv_batch_t.tid_runs)
+	DBuf inf_scratch, inf_dbg, tokens, tok_off, n_tok, carrybuf, comp, blocks, u_off, stream, status, chain, count, base, rec_off, stitch, small;
+	TidLists tl; // the contig changes, and the batch's tid column as runs (ssv_batch_t.tid_runs)
 	DBuf tlen; bool have_tlen = false; // contig lengths (optional: ssv_bamdec_target_lens)
 	DecodedColumns cols; // the batch handed out
 	DBuf rel, stash, seq_list, raw_bytes, raw_off, raw;
-	HBuf h_stage[3], h_small, h_raw[2], h_runs, h_status; // h_raw: two in turn - a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded (a thread beside the decoder pairs them up)
+	HBuf h_stage[3], h_small, h_raw[2], h_status; // h_raw: two in turn - a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded (a thread beside the decoder pairs them up)
 	int raw_flip = 0;
 	// chunks announced ahead (ssv_bamdec_prefetch): their compressed bytes travel on the upload stream into one of two slots while the chunk before is inflated
 	struct CompSlot {
@@ -363,12 +363,7 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 	CHECK(ensure_up(d.rec_off, N * 8 + 16));
 	CHECK(d.cols.reserve(c, N, up));
 	CHECK(ensure_up(d.stash, N * 8 + 16)); CHECK(ensure_up(d.seq_list, N * 4 + 16)); CHECK(ensure_up(d.raw_bytes, N * 4 + 16)); CHECK(ensure_up(d.raw_off, N * 8 + 16));
-	const int64_t n_tiles = (n + BLOCK - 1) / BLOCK;
-	CHECK(ensure_up(d.tile_last, (size_t)n_tiles * 4)); CHECK(ensure_up(d.tile_prev, (size_t)n_tiles * 4));
-	const uint32_t run_cap = 1u << 16;
-	CHECK(ensure_up(d.runs, (size_t)run_cap * sizeof(ssv::TidRun)));
-	constexpr uint32_t RAW_RUN_CAP = 64;
-	CHECK(ensure_up(d.raw_runs, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun))); CHECK(ensure_host(c, d.h_raw_runs, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun)));
+	CHECK(d.tl.reserve(c, n, up));
 	// d.small: [0] max_span i32, [1] bad u32, [2] n_runs u32, [3] last_tid i32, [4..5] cigar total u32 (+pad), [6..7] seq total u64, [8..9] raw total u64, [10] records on the bases / XC list
 	HIPCHECK(c, hipMemsetAsync(d.small.p, 0, 256, st));
 	uint32_t *sm = P<uint32_t>(d.small);
@@ -397,49 +392,28 @@ int ssv_bamdec_decode(ssv_ctx *c, const void *comp, size_t comp_bytes, const ssv
 		hipLaunchKernelGGL(ssv::k_record_seqs, dim3((unsigned)std::min<int64_t>((n * 16 + BLOCK - 1) / BLOCK, 2048)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off),
 		                   col.n_cigar, col.seq_bytes, col.seq_off, P<uint32_t>(d.seq_list), sm + 10, col.seqqual, col.xc);
 		hipLaunchKernelGGL(ssv::k_raw_copy, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, P<uint32_t>(d.raw_bytes), P<uint64_t>(d.raw_off), P<uint8_t>(d.raw));
-		hipLaunchKernelGGL(ssv::k_tid_tile_last, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, col.flag, n, P<int32_t>(d.tile_last));
-		hipLaunchKernelGGL(ssv::k_tid_tile_carry, dim3(1), dim3(WAVE), 0, st, P<int32_t>(d.tile_last), n_tiles, d.prev_tid, P<int32_t>(d.tile_prev), reinterpret_cast<int32_t *>(sm + 3));
-		hipLaunchKernelGGL(ssv::k_tid_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, col.flag, n, P<int32_t>(d.tile_prev), P<ssv::TidRun>(d.runs), run_cap, sm + 2);
-		hipLaunchKernelGGL(ssv::k_tid_raw_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, col.tid, n, P<ssv::TidRun>(d.raw_runs), RAW_RUN_CAP, sm + 11);
-		HIPCHECK(c, hipMemcpyAsync(d.h_raw_runs.p, d.raw_runs.p, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun), hipMemcpyDeviceToHost, st));
+		CHECK(d.tl.launch(c, st, col.tid, col.flag, n, d.prev_tid, sm + 2, reinterpret_cast<int32_t *>(sm + 3), sm + 11));
 	}
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
 	const uint32_t *hs = P<uint32_t>(d.h_small);
 	uint32_t n_runs = hs[2];
-	if (n_runs > run_cap) {
+	if (n_runs > TidLists::RUN_CAP) {
 		if (!d.any_order) { c->err = "more than 65536 contig changes in one chunk: the BAM is not coordinate sorted"; return SSV_E_ARG; }
 		n_runs = 0; // (ssv_bamdec_any_order: the list is incomplete - not handed out; the kernel wrote no more than run_cap entries)
 	}
 	d.prev_tid = (int32_t)hs[3];
 	// the small host-side lists
-	CHECK(ensure_host(c, d.h_runs, (size_t)n_runs * sizeof(ssv::TidRun) + 64 + (size_t)n_runs * 8));
 	HBuf &h_raw = d.h_raw[d.raw_flip ^= 1];
 	CHECK(ensure_host(c, h_raw, (size_t)raw_total + 64));
-	if (n_runs) HIPCHECK(c, hipMemcpyAsync(d.h_runs.p, d.runs.p, (size_t)n_runs * sizeof(ssv::TidRun), hipMemcpyDeviceToHost, st));
+	CHECK(d.tl.fetch(c, st, n_runs));
 	if (raw_total) HIPCHECK(c, hipMemcpyAsync(h_raw.p, d.raw.p, (size_t)raw_total, hipMemcpyDeviceToHost, st));
 	if (n_runs || raw_total) HIPCHECK(c, hipStreamSynchronize(st));
-	{ // atomics gave the runs no order: sort by record index, then split into the two arrays of the info struct (behind the pairs)
-		ssv::TidRun *r = P<ssv::TidRun>(d.h_runs);
-		std::sort(r, r + n_runs, [](const ssv::TidRun &a, const ssv::TidRun &b) { return a.index < b.index; });
-		uint32_t *idx = reinterpret_cast<uint32_t *>(P<uint8_t>(d.h_runs) + (((size_t)n_runs * sizeof(ssv::TidRun) + 63) & ~(size_t)63));
-		int32_t *tv = reinterpret_cast<int32_t *>(idx + n_runs);
-		for (uint32_t k = 0; k < n_runs; ++k) { idx[k] = r[k].index; tv[k] = r[k].tid; }
-		d.info.n_tid_runs = n_runs; d.info.tid_run_index = idx; d.info.tid_run_tid = tv;
-	}
+	d.tl.changes(n_runs, d.info);
 	d.info.unmapped_raw = P<uint8_t>(h_raw); d.info.unmapped_bytes = raw_total; d.info.last_tid = d.prev_tid;
 	d.cols.fill(out, n, (int64_t)cigar_total, (int64_t)seq_total);
 	out->max_ref_span = (int32_t)hs[0] > 0 ? (int32_t)hs[0] : 1;
-	{ // the tid column as runs (atomics gave them no order: sorted by record index); more than the list holds: not handed out
-		const uint32_t nr = hs[11];
-		d.tid_runs.clear();
-		if (nr >= 1 && nr <= RAW_RUN_CAP) {
-			const ssv::TidRun *r = P<ssv::TidRun>(d.h_raw_runs);
-			for (uint32_t k = 0; k < nr; ++k) d.tid_runs.push_back(ssv_tid_run{(int64_t)r[k].index, r[k].tid, 0});
-			std::sort(d.tid_runs.begin(), d.tid_runs.end(), [](const ssv_tid_run &a, const ssv_tid_run &b) { return a.first < b.first; });
-			out->tid_runs = d.tid_runs.data(); out->n_tid_runs = (int64_t)nr;
-		}
-	}
+	d.tl.batch_runs(hs[11], out);
 	return SSV_OK;
 }
 

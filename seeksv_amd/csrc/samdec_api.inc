@@ -1,6 +1,9 @@
 // samdec_api.inc - host side of the device SAM-text decoder (included by seeksv_hip.hip inside extern "C"); kernels in samdec_kernels.h.
 // Per chunk: [carried line | text] in one buffer -> k_sam_count -> scans of the tile sums -> (sync: separators, lines) -> k_sam_marks -> k_sam_sizes ->
 // scans -> (sync: totals) -> k_sam_fields, k_sam_seqqual, the unfinished line to the side buffer -> (sync: refusals) -> device batch + names.
+// After ssv_samdec_sorted (a coordinate-sorted original: what getclip and `seeksv run` read) the same two synchronisations carry more: k_sam_sizes_sorted also
+// sizes the list of the lines that ship bases + qualities and the side channel's records (two more scans); behind k_sam_fields_sorted come k_sam_seqqual_list,
+// k_sam_raw and the four k_tid_* kernels the BAM decoder runs (TidLists); the small host-side lists follow the refusal word (ssv_samdec_lists).
 
 struct ssv_samdec_state {
 	enum { IDLE, ACTIVE, ENDED, FAILED } phase = IDLE;
@@ -18,6 +21,14 @@ struct ssv_samdec_state {
 	bool have_batch = false;
 	uint64_t text_bytes = 0;
 	ssv_samdec_info info{};
+	// ssv_samdec_sorted: a coordinate-sorted original
+	bool sorted = false, keep_all_seq = false, decoded = false, have_lists = false;
+	int32_t prev_tid = 0; // contig of the last mapped-pair record so far (clip_reads.h:407: starts at 0)
+	DBuf ship, ship_idx, seq_list, raw_bytes, raw_off, raw;
+	HBuf h_raw[2]; // two in turn, as the BAM decoder's: a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded
+	int raw_flip = 0;
+	TidLists tl;
+	ssv_bamdec_info lists{};
 };
 
 static const char *const kSamReasons[ssv::SAM_E_COUNT] = {
@@ -47,6 +58,8 @@ int ssv_samdec_begin(ssv_ctx *c, const ssv_samdec_params *p)
 		if (any) HIPCHECK(c, hipStreamSynchronize(c->st_h2d));
 	}
 	d.n_targets = p->n_targets; d.first_line = p->first_line; d.lines_done = 0; d.carry = 0; d.have_batch = false;
+	d.sorted = d.keep_all_seq = d.decoded = d.have_lists = false; d.prev_tid = 0;
+	memset(&d.lists, 0, sizeof(d.lists));
 	memset(&d.info, 0, sizeof(d.info));
 	// the contig names as a hash table: FNV-1a, linear probing, at most half full; the first of two equal names wins
 	uint32_t size = 16;
@@ -104,6 +117,22 @@ int ssv_samdec_prefetch(ssv_ctx *c, const void *text, size_t bytes)
 	return SSV_OK;
 }
 
+int ssv_samdec_sorted(ssv_ctx *c, int keep_all_seq)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->sd || c->sd->phase != ssv_samdec_state::ACTIVE || c->sd->decoded) { c->err = "ssv_samdec_sorted belongs between ssv_samdec_begin and the first ssv_samdec_decode"; return SSV_E_ARG; }
+	c->sd->sorted = true; c->sd->keep_all_seq = keep_all_seq != 0;
+	return SSV_OK;
+}
+
+// a chunk without a finished line: empty lists
+static void samdec_no_lists(ssv_samdec_state &d, uint64_t text_bytes)
+{
+	memset(&d.lists, 0, sizeof(d.lists));
+	d.lists.inflated_bytes = text_bytes; d.lists.last_tid = d.prev_tid;
+	d.have_lists = d.sorted;
+}
+
 static int samdec_refuse(ssv_ctx *c, unsigned long long word)
 {
 	ssv_samdec_state &d = *c->sd;
@@ -127,7 +156,7 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	hipStream_t st = c->st;
 	memset(out, 0, sizeof(*out));
 	out->mem = SSV_MEM_DEVICE;
-	d.have_batch = false;
+	d.have_batch = false; d.have_lists = false; d.decoded = true;
 	d.info.n_records = 0;
 	const uint64_t total = d.carry + bytes;
 	CHECK(ensure(c, d.text, (size_t)total + 128));
@@ -152,6 +181,7 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 		d.info.carried_bytes = 0;
 		if (last) d.phase = ssv_samdec_state::ENDED;
 		d.have_batch = true;
+		samdec_no_lists(d, bytes);
 		return SSV_OK;
 	}
 	// a last line without its newline gets one (the kernels count it unless a newline stands in front of it)
@@ -160,7 +190,8 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	const int64_t n_tiles = (len + ssv::SAM_TILE - 1) / ssv::SAM_TILE;
 	CHECK(ensure(c, d.tile_sep, (size_t)n_tiles * 4 + 16)); CHECK(ensure(c, d.tile_nl, (size_t)n_tiles * 4 + 16));
 	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n_tiles) * 8 + 64));
-	// d.small: [0..1] the smallest refused (line << 8 | reason) u64, [2] separators, [3] lines, [4] CIGAR operations, [6..7] seqqual bytes u64, [8] max span i32
+	// d.small: [0..1] the smallest refused (line << 8 | reason) u64, [2] separators, [3] lines, [4] CIGAR operations, [6..7] seqqual bytes u64, [8] max span i32;
+	// sorted originals: [9] lines that ship, [10..11] side-channel bytes u64, [12] contig changes, [13] last contig i32, [14] runs of the tid column
 	uint32_t *sm = P<uint32_t>(d.small);
 	unsigned long long *errw = P<unsigned long long>(d.small);
 	HIPCHECK(c, hipMemsetAsync(d.small.p, 0, 256, st));
@@ -180,6 +211,7 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 		HIPCHECK(c, hipStreamSynchronize(st));
 		d.carry = total; d.info.carried_bytes = total;
 		d.have_batch = true;
+		samdec_no_lists(d, bytes);
 		return SSV_OK;
 	}
 	const size_t N = (size_t)n;
@@ -188,9 +220,20 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	CHECK(ensure(c, d.name_off, N * 8 + 16)); CHECK(ensure(c, d.rec, N * sizeof(ssv_record) + 64));
 	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n) * 8 + 64)); CHECK(ensure(c, c->scan_scratch64, (size_t)scan_scratch_elems(n) * 8 + 64));
 	k_sam_marks<<<(unsigned)n_tiles, BLOCK, 0, st>>>(tx, len, virt_at, P<uint32_t>(d.tile_sep), P<uint32_t>(d.tile_nl), (uint32_t)n, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), errw);
-	k_sam_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, d.cols.view(), errw);
+	ssv::SamSortedCols srt{};
+	if (d.sorted) {
+		CHECK(ensure(c, d.ship, N * 4 + 16)); CHECK(ensure(c, d.ship_idx, N * 4 + 16)); CHECK(ensure(c, d.raw_bytes, N * 4 + 16)); CHECK(ensure(c, d.raw_off, N * 8 + 16));
+		CHECK(d.tl.reserve(c, n, 1.0));
+		srt = ssv::SamSortedCols{P<uint32_t>(d.ship), P<uint32_t>(d.raw_bytes), P<uint32_t>(d.ship_idx), nullptr, d.keep_all_seq ? 1 : 0};
+		k_sam_sizes_sorted<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, d.cols.view(), srt, errw);
+	} else
+		k_sam_sizes<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, d.cols.view(), errw);
 	HIPCHECK(c, hipGetLastError());
 	d.cols.layout(st, n, P<uint32_t>(c->scan_scratch), P<uint64_t>(c->scan_scratch64), sm + 4, reinterpret_cast<uint64_t *>(sm + 6));
+	if (d.sorted) {
+		exclusive_scan<uint32_t, uint32_t>(st, srt.ship, P<uint32_t>(d.ship_idx), n, 0u, P<uint32_t>(c->scan_scratch), sm + 9);
+		exclusive_scan<uint32_t, uint64_t>(st, srt.raw_bytes, P<uint64_t>(d.raw_off), n, 0ull, P<uint64_t>(c->scan_scratch64), reinterpret_cast<uint64_t *>(sm + 10));
+	}
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 16, P<uint32_t>(d.nlidx) + (n - 1), 4, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
@@ -200,27 +243,63 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	uint64_t seq_total;
 	memcpy(&seq_total, hs + 6, 8);
 	CHECK(d.cols.reserve_variable(c, cigar_total, (size_t)seq_total, 1.0));
+	const uint32_t n_ship = d.sorted ? hs[9] : 0u;
+	uint64_t raw_total = 0;
+	if (d.sorted) {
+		memcpy(&raw_total, hs + 10, 8);
+		CHECK(ensure(c, d.seq_list, (size_t)n_ship * 4 + 16)); CHECK(ensure(c, d.raw, (size_t)raw_total + 64));
+		srt.list = P<uint32_t>(d.seq_list);
+	}
 	const ssv::DecodedCols col = d.cols.view();
 	const ssv::SamLineCols lines{P<uint64_t>(d.name_off), P<ssv_record>(d.rec)};
 	ssv::SamRefTable T{P<uint32_t>(d.ref_slots), d.ref_mask, P<uint32_t>(d.ref_off), P<uint8_t>(d.ref_blob)};
 	// where the last finished line ends (k_sam_fields puts NULs over the first tabs of finished lines only: the unfinished one is carried as it is)
 	HIPCHECK(c, hipMemcpyAsync(P<uint32_t>(d.h_small) + 17, P<uint32_t>(d.sep) + last_nl_sep, 4, hipMemcpyDeviceToHost, st));
-	k_sam_fields<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, lines, reinterpret_cast<int32_t *>(sm + 8), errw);
-	k_sam_seqqual<<<(unsigned)std::min<int64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col.l_qseq, col.seq_off,
-	                                                                                                                 col.seqqual, errw);
+	if (d.sorted) {
+		k_sam_fields_sorted<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, lines, srt, reinterpret_cast<int32_t *>(sm + 8), errw);
+		if (n_ship)
+			k_sam_seqqual_list<<<(unsigned)std::min<int64_t>(((int64_t)n_ship + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), srt.list, n_ship,
+			                                                                                                                                col.l_qseq, col.seq_off, col.seqqual, errw);
+		if (raw_total) k_sam_raw<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col, srt.raw_bytes, P<uint64_t>(d.raw_off), P<uint8_t>(d.raw), errw);
+		HIPCHECK(c, hipGetLastError());
+		CHECK(d.tl.launch(c, st, col.tid, col.flag, n, d.prev_tid, sm + 12, reinterpret_cast<int32_t *>(sm + 13), sm + 14));
+	} else {
+		k_sam_fields<<<grid_for(n, BLOCK), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, T, col, lines, reinterpret_cast<int32_t *>(sm + 8), errw);
+		k_sam_seqqual<<<(unsigned)std::min<int64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192), BLOCK, 0, st>>>(tx, P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, col.l_qseq, col.seq_off,
+		                                                                                                                 col.seqqual, errw);
+	}
 	HIPCHECK(c, hipGetLastError());
 	HIPCHECK(c, hipMemcpyAsync(d.h_small.p, d.small.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCHECK(c, hipStreamSynchronize(st));
 	memcpy(&werr, d.h_small.p, 8);
 	if (werr != ssv::SAM_NO_ERROR) return samdec_refuse(c, werr);
+	const uint32_t n_runs = d.sorted ? hs[12] : 0u, n_raw_runs = d.sorted ? hs[14] : 0u;
+	const int32_t last_tid = (int32_t)hs[13];
+	if (n_runs > TidLists::RUN_CAP) {
+		c->err = "more than 65536 contig changes in one chunk: the SAM text is not coordinate sorted";
+		d.phase = ssv_samdec_state::FAILED;
+		return SSV_E_ARG;
+	}
 	// the unfinished last line: kept aside, moved in front of the next chunk's bytes by the next decode
 	const uint64_t consumed = last ? total : (uint64_t)hs[17] + 1u;
 	const uint64_t carry = total - consumed;
 	if (carry) {
 		CHECK(ensure(c, d.carrybuf, (size_t)carry + 64));
 		HIPCHECK(c, hipMemcpyAsync(d.carrybuf.p, tx + consumed, carry, hipMemcpyDeviceToDevice, st));
-		HIPCHECK(c, hipStreamSynchronize(st));
 	}
+	if (d.sorted) { // the small host-side lists
+		HBuf &h_raw = d.h_raw[d.raw_flip ^= 1];
+		CHECK(ensure_host(c, h_raw, (size_t)raw_total + 64));
+		CHECK(d.tl.fetch(c, st, n_runs));
+		if (raw_total) HIPCHECK(c, hipMemcpyAsync(h_raw.p, d.raw.p, (size_t)raw_total, hipMemcpyDeviceToHost, st));
+		if (carry || n_runs || raw_total) HIPCHECK(c, hipStreamSynchronize(st));
+		memset(&d.lists, 0, sizeof(d.lists));
+		d.prev_tid = last_tid;
+		d.tl.changes(n_runs, d.lists);
+		d.lists.n_records = n; d.lists.inflated_bytes = bytes; d.lists.last_tid = last_tid;
+		d.lists.unmapped_raw = P<uint8_t>(h_raw); d.lists.unmapped_bytes = raw_total;
+		d.have_lists = true;
+	} else if (carry) HIPCHECK(c, hipStreamSynchronize(st));
 	d.carry = carry;
 	d.lines_done += (uint64_t)n;
 	d.info.n_records = n; d.info.lines_consumed = d.lines_done; d.info.carried_bytes = carry;
@@ -230,6 +309,7 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	out->max_ref_span = (int32_t)hs[8] > 0 ? (int32_t)hs[8] : 1;
 	out->rec = lines.rec;
 	out->tid_runs = nullptr; out->n_tid_runs = 0;
+	if (d.sorted) d.tl.batch_runs(n_raw_runs, out);
 	return SSV_OK;
 }
 
@@ -248,5 +328,13 @@ int ssv_samdec_last(ssv_ctx *c, ssv_samdec_info *info)
 	if (!c || !info) return SSV_E_ARG;
 	if (!c->sd || c->sd->phase == ssv_samdec_state::IDLE) { c->err = "ssv_samdec_last before ssv_samdec_begin"; return SSV_E_STATE; }
 	*info = c->sd->info;
+	return SSV_OK;
+}
+
+int ssv_samdec_lists(ssv_ctx *c, ssv_bamdec_info *out)
+{
+	if (!c || !out) return SSV_E_ARG;
+	if (!c->sd || !c->sd->have_lists) { c->err = "ssv_samdec_lists before a successful ssv_samdec_decode behind ssv_samdec_sorted"; return SSV_E_STATE; }
+	*out = c->sd->lists;
 	return SSV_OK;
 }

@@ -589,6 +589,61 @@ struct DecodedColumns {
 	}
 };
 
+// The contig lists of a decoded chunk, for both decoders (ssv_bamdec_decode, ssv_samdec_decode in its mode for sorted originals): the changes of contig among
+// the records that are not UNMAP|MUNMAP (ssv_bamdec_info.tid_run_*: getclip's flush sequence) and the tid column as runs (ssv_batch_t.tid_runs).
+struct TidLists {
+	static constexpr uint32_t RUN_CAP = 1u << 16, RAW_RUN_CAP = 64;
+	DBuf tile_last, tile_prev, runs, raw_runs;
+	HBuf h_raw_runs, h_runs;
+	std::vector<ssv_tid_run> tid_runs;
+	int reserve(ssv_ctx *c, int64_t n, double grow)
+	{
+		const size_t n_tiles = (size_t)((n + BLOCK - 1) / BLOCK);
+		CHECK(ensure(c, tile_last, grown(n_tiles * 4, grow))); CHECK(ensure(c, tile_prev, grown(n_tiles * 4, grow)));
+		CHECK(ensure(c, runs, grown((size_t)RUN_CAP * sizeof(ssv::TidRun), grow)));
+		CHECK(ensure(c, raw_runs, grown((size_t)RAW_RUN_CAP * sizeof(ssv::TidRun), grow)));
+		return ensure_host(c, h_raw_runs, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun));
+	}
+	// the four kernels over the decoded tid / flag columns; the counts and the last contig go to device words of the caller's (zeroed by it), read back with its small block
+	int launch(ssv_ctx *c, hipStream_t st, const int32_t *tid, const uint16_t *flag, int64_t n, int32_t prev_tid, uint32_t *n_runs, int32_t *last_tid, uint32_t *n_raw_runs)
+	{
+		const int64_t n_tiles = (n + BLOCK - 1) / BLOCK;
+		hipLaunchKernelGGL(ssv::k_tid_tile_last, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tid, flag, n, P<int32_t>(tile_last));
+		hipLaunchKernelGGL(ssv::k_tid_tile_carry, dim3(1), dim3(WAVE), 0, st, P<int32_t>(tile_last), n_tiles, prev_tid, P<int32_t>(tile_prev), last_tid);
+		hipLaunchKernelGGL(ssv::k_tid_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tid, flag, n, P<int32_t>(tile_prev), P<ssv::TidRun>(runs), RUN_CAP, n_runs);
+		hipLaunchKernelGGL(ssv::k_tid_raw_runs, dim3((unsigned)n_tiles), dim3(BLOCK), 0, st, tid, n, P<ssv::TidRun>(raw_runs), RAW_RUN_CAP, n_raw_runs);
+		HIPCHECK(c, hipMemcpyAsync(h_raw_runs.p, raw_runs.p, (size_t)RAW_RUN_CAP * sizeof(ssv::TidRun), hipMemcpyDeviceToHost, st));
+		return SSV_OK;
+	}
+	// once the caller has read n_runs (<= RUN_CAP): the changes on their way to the host (the caller synchronises when n_runs > 0)
+	int fetch(ssv_ctx *c, hipStream_t st, uint32_t n_runs)
+	{
+		CHECK(ensure_host(c, h_runs, (size_t)n_runs * sizeof(ssv::TidRun) + 64 + (size_t)n_runs * 8));
+		if (n_runs) HIPCHECK(c, hipMemcpyAsync(h_runs.p, runs.p, (size_t)n_runs * sizeof(ssv::TidRun), hipMemcpyDeviceToHost, st));
+		return SSV_OK;
+	}
+	// atomics gave the runs no order: sort by record index, then split into the two arrays of the info struct (behind the pairs)
+	void changes(uint32_t n_runs, ssv_bamdec_info &info)
+	{
+		ssv::TidRun *r = P<ssv::TidRun>(h_runs);
+		std::sort(r, r + n_runs, [](const ssv::TidRun &a, const ssv::TidRun &b) { return a.index < b.index; });
+		uint32_t *idx = reinterpret_cast<uint32_t *>(P<uint8_t>(h_runs) + (((size_t)n_runs * sizeof(ssv::TidRun) + 63) & ~(size_t)63));
+		int32_t *tv = reinterpret_cast<int32_t *>(idx + n_runs);
+		for (uint32_t k = 0; k < n_runs; ++k) { idx[k] = r[k].index; tv[k] = r[k].tid; }
+		info.n_tid_runs = n_runs; info.tid_run_index = idx; info.tid_run_tid = tv;
+	}
+	// the tid column as runs (sorted by record index); more than the list holds: not handed out
+	void batch_runs(uint32_t nr, ssv_batch_t *out)
+	{
+		tid_runs.clear();
+		if (nr < 1 || nr > RAW_RUN_CAP) return;
+		const ssv::TidRun *r = P<ssv::TidRun>(h_raw_runs);
+		for (uint32_t k = 0; k < nr; ++k) tid_runs.push_back(ssv_tid_run{(int64_t)r[k].index, r[k].tid, 0});
+		std::sort(tid_runs.begin(), tid_runs.end(), [](const ssv_tid_run &a, const ssv_tid_run &b) { return a.first < b.first; });
+		out->tid_runs = tid_runs.data(); out->n_tid_runs = (int64_t)nr;
+	}
+};
+
 // The one set of rules for an ssv_names_t argument (`what`: the entry point, for the message): a batch with records needs its names, and names that are
 // given say where they lie.
 int check_names(ssv_ctx *c, const ssv_names_t *nm, int64_t n, const char *what)

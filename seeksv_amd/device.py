@@ -135,6 +135,25 @@ class Context:
         arr = (C.c_int32 * max(1, len(lens)))(*[int(x) for x in lens])
         self._check(self._lib.ssv_bamdec_target_lens(self._h, arr), "ssv_bamdec_target_lens")
 
+    @staticmethod
+    def _info_dict(info, hl):
+        """an ssv_bamdec_info (ssv_bamdec_last, ssv_samdec_lists) as a dict: the contig changes as (record, contig) pairs, the side channel's records as they
+        lie there (unmapped_raw) and as ssvh_raw_record_fastq reads them (unmapped: name, bases, qualities, first of pair)"""
+        d = dict(n_records=info.n_records, inflated_bytes=info.inflated_bytes, repaired_blocks=info.repaired_blocks, last_tid=info.last_tid)
+        k = info.n_tid_runs
+        d["tid_runs"] = list(zip(np.ctypeslib.as_array((C.c_uint32 * k).from_address(info.tid_run_index)).tolist(), np.ctypeslib.as_array((C.c_int32 * k).from_address(info.tid_run_tid)).tolist())) if k else []
+        d["unmapped_raw"] = C.string_at(info.unmapped_raw, info.unmapped_bytes) if info.unmapped_bytes else b""
+        unm, off = [], 0
+        q, sq, ql, r1 = C.c_char_p(), C.c_char_p(), C.c_char_p(), C.c_int()
+        while info.unmapped_bytes:
+            nxt = hl.ssvh_raw_record_fastq(info.unmapped_raw, info.unmapped_bytes, off, C.byref(q), C.byref(sq), C.byref(ql), C.byref(r1))
+            if nxt == 0:
+                break
+            unm.append((q.value.decode(), sq.value.decode(), ql.value.decode(), bool(r1.value)))
+            off = nxt
+        d["unmapped"] = unm
+        return d
+
     def bamdec_names(self):
         """ssv_bamdec_names: where the read names of the batch bam_batches handed out last lie in HBM (valid as long as that batch)"""
         n = _abi.Names()
@@ -183,18 +202,8 @@ class Context:
                 return
             info = _abi.BamdecInfo()
             self._check(self._lib.ssv_bamdec_last(self._h, C.byref(info)), "ssv_bamdec_last")
-            d = dict(n_records=info.n_records, inflated_bytes=info.inflated_bytes, repaired_blocks=info.repaired_blocks, last_tid=info.last_tid, n_blocks=nb.value, compressed_bytes=nbytes.value)
-            k = info.n_tid_runs
-            d["tid_runs"] = list(zip(np.ctypeslib.as_array((C.c_uint32 * k).from_address(info.tid_run_index)).tolist(), np.ctypeslib.as_array((C.c_int32 * k).from_address(info.tid_run_tid)).tolist())) if k else []
-            unm, off = [], 0
-            q, sq, ql, r1 = C.c_char_p(), C.c_char_p(), C.c_char_p(), C.c_int()
-            while info.unmapped_bytes:
-                nxt = hl.ssvh_raw_record_fastq(info.unmapped_raw, info.unmapped_bytes, off, C.byref(q), C.byref(sq), C.byref(ql), C.byref(r1))
-                if nxt == 0:
-                    break
-                unm.append((q.value.decode(), sq.value.decode(), ql.value.decode(), bool(r1.value)))
-                off = nxt
-            d["unmapped"] = unm
+            d = self._info_dict(info, hl)
+            d.update(n_blocks=nb.value, compressed_bytes=nbytes.value)
             yield b, d
 
     # ---- device-side SAM text decode (getsv -F on `bwa bwasw` output) ----
@@ -210,6 +219,17 @@ class Context:
         buf = C.create_string_buffer(text, len(text)) if len(text) else None
         self._check(self._lib.ssv_samdec_decode(self._h, buf, len(text), _abi.MEM_HOST, int(bool(last)), C.byref(b)), "ssv_samdec_decode")
         return b
+
+    def samdec_sorted(self, keep_all_seq=False):
+        """ssv_samdec_sorted, between samdec_begin and the first samdec_decode: the text is a coordinate-sorted original - batches as bam_batches gives them for
+        the BAM of the same records, and samdec_lists() behind every decode"""
+        self._check(self._lib.ssv_samdec_sorted(self._h, int(bool(keep_all_seq))), "ssv_samdec_sorted")
+
+    def samdec_lists(self):
+        """ssv_samdec_lists: the contig changes and the UNMAP|MUNMAP records of the chunk decoded last, as bam_batches' info dict has them"""
+        info = _abi.BamdecInfo()
+        self._check(self._lib.ssv_samdec_lists(self._h, C.byref(info)), "ssv_samdec_lists")
+        return self._info_dict(info, _abi.host_lib())
 
     def samdec_names(self):
         """ssv_samdec_names: where the read names of the batch decoded last lie in HBM (valid as long as that batch)"""

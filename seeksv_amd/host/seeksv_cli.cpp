@@ -37,6 +37,7 @@
 #include <condition_variable>
 #include <map>
 #include <mutex>
+#include <shared_mutex>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -87,8 +88,19 @@ struct PhaseTimer {
 // A fatal error: the reference's message and exit status 1.  Reader, emitter and rank threads may be running (and the HIP context coming up on its own
 // thread): the process leaves through _exit - no static destructor pulls a buffer away under a thread that is still copying into it - after everything
 // written so far has been flushed.
+// getclip on SAM text: a line in the middle of the text can be refused when passes before it have been written, and every piece a .gz output gets is a whole
+// gzip member.  The outputs of such a command are emptied when it dies, so that none is left looking complete; appends hold the lock shared.
+static std::shared_mutex g_outputs_mu;
+static vector<string> g_outputs_unfinished;
+static bool g_dying = false;
+
 [[noreturn]] static void die(const string &msg)
 {
+	{
+		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
+		g_dying = true;
+		for (const string &p : g_outputs_unfinished) if (truncate(p.c_str(), 0) != 0) {} // (nothing more can be done about it here)
+	}
 	cerr << msg << endl;
 	cout.flush(); cerr.flush(); fflush(nullptr);
 	_exit(1);
@@ -117,6 +129,9 @@ static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv]
 [[noreturn]] static void usage_getclip()
 {
 	cerr << "Usage: seeksv getclip [options] <input.sorted.bam>\n\n"
+	     << "<input> whose name does not end in .bam is SAM text (plain or gzip; - is standard input, e.g. `samtools view -h in.cram | seeksv getclip -`):\n"
+	     << "it is read once and always decoded on the GPU (-Z and -C change nothing for it), and -N above 1 is refused.  The original alignments as SAM\n"
+	     << "text for `getsv` and `somatic` run as commands of their own are not supported (a pipe cannot be read twice): use `seeksv run`.\n\n"
 	     << "Options: -t <double>           Threshold of match rate while combining two soft-clipped reads [0.9]\n"
 	     << "         -q <int>              Minimum mapping quality of soft-clipped reads [1]\n"
 	     << "         -s                    Save the low quality sequence clipped before alignment by bwa.\n"
@@ -190,7 +205,13 @@ struct GzOut {
 	void flush(bool final)
 	{
 		if (buf.empty() && (started || !final)) return;
-		if (ssvh_gz_append(path.c_str(), buf.data(), buf.size(), started ? 1 : 0) != 0) die(string("[seeksv] ") + ssvh_last_error());
+		int rc;
+		{
+			std::shared_lock<std::shared_mutex> lk(g_outputs_mu);
+			if (g_dying) return;
+			rc = ssvh_gz_append(path.c_str(), buf.data(), buf.size(), started ? 1 : 0);
+		}
+		if (rc != 0) die(string("[seeksv] ") + ssvh_last_error());
 		started = true;
 		buf.clear();
 	}
@@ -201,7 +222,13 @@ struct GzOut {
 		vector<const char *> ptr; vector<size_t> len;
 		for (auto &s : parts) if (!s.empty()) { ptr.push_back(s.data()); len.push_back(s.size()); }
 		if (ptr.empty()) return;
-		if (ssvh_gz_append_v(path.c_str(), ptr.data(), len.data(), (int)ptr.size(), started ? 1 : 0) != 0) die(string("[seeksv] ") + ssvh_last_error());
+		int rc;
+		{
+			std::shared_lock<std::shared_mutex> lk(g_outputs_mu);
+			if (g_dying) return;
+			rc = ssvh_gz_append_v(path.c_str(), ptr.data(), len.data(), (int)ptr.size(), started ? 1 : 0);
+		}
+		if (rc != 0) die(string("[seeksv] ") + ssvh_last_error());
 		started = true;
 	}
 	void close() { flush(true); }
@@ -318,6 +345,9 @@ struct RunSession {
 	bool ranked() const { return !ranks.rank.empty() && !ranks.fell_back; }
 	void fall_back() { ranks.release(); ranks.fell_back = true; collect = true; } // from here on the run is `seeksv run` on the first device: one context, which keeps every record
 	PrereadFasta preread;        // the reference, handed to the aligner step that reads it
+	// the run's input is SAM text (a name without ".bam": plain, gzip or "-"), which can be read once: its @SQ list, kept by getclip for the getsv step's header
+	bool text_input = false;
+	vector<string> text_names; vector<int32_t> text_lens;
 };
 
 static void release_ctx(ssv_ctx *ctx, const RunSession *run)
@@ -443,6 +473,90 @@ static void stage_to_pool(StageBuf &b)
 	b = StageBuf();
 }
 
+static bool is_bam_name(const string &path) { return path.size() >= 4 && path.rfind(".bam") == path.size() - 4; }
+
+static void *sam_stage_alloc(size_t bytes) { void *p = nullptr; return ssv_host_alloc(bytes, &p) == SSV_OK ? p : nullptr; }
+static void sam_stage_free(void *p) { ssv_host_free(p); }
+
+// A SAM text file through the device decoder: the header on the host, the records' text to the GPU as it is, in chunks cut anywhere (SSV_SAM_CHUNK_KB: their
+// size, 256 MB by default); a reader thread fills page-locked buffers ahead, and chunk k + 1 crosses the host link under chunk k's kernels
+// (ssv_samdec_prefetch).  open(): the header, with libbam's [samopen] line; begin(): the decoder and the reader thread - sorted: a coordinate-sorted original
+// (ssv_samdec_sorted: batches as the BAM decoder gives them, and the chunk's lists); next(): the next chunk's batch and names, valid until the call after.
+// The one loop behind the -F pass, the pass over the clipped-sequence re-alignments (sam_text_pass) and the original alignments of getclip and run (BatchSource).
+struct SamTextDecoder {
+	seeksv::SamTextReader rd;
+	ssv_ctx *ctx = nullptr;
+	bool ended = false, over = false, sorted = false;
+	ssv_names_t names{};
+	void open(const string &path, const char *open_error)
+	{
+		string err;
+		if (!rd.open(path, err)) die(open_error);
+		if (rd.target_names().empty()) { // (the reference goes on and aborts at its first record: "[sam_read1] missing header? Abort!")
+			cerr << "[samopen] no @SQ lines in the header." << endl;
+			die(open_error);
+		}
+		cerr << "[samopen] SAM header is present: " << rd.target_names().size() << " sequences." << endl;
+	}
+	void begin(ssv_ctx *c, bool sorted_original)
+	{
+		ctx = c; sorted = sorted_original;
+		vector<const char *> cnames;
+		for (const string &s : rd.target_names()) cnames.push_back(s.c_str());
+		ssv_samdec_params sp;
+		memset(&sp, 0, sizeof(sp));
+		sp.n_targets = (int32_t)cnames.size(); sp.target_names = cnames.data(); sp.first_line = rd.first_record_line();
+		check(ctx, ssv_samdec_begin(ctx, &sp));
+		if (sorted) check(ctx, ssv_samdec_sorted(ctx, 0));
+		const char *e = getenv("SSV_SAM_CHUNK_KB");
+		const size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) << 10 : (size_t)256 << 20;
+		rd.start(chunk, sam_stage_alloc, sam_stage_free);
+	}
+	void decode(const void *text, size_t bytes, int last, ssv_batch_t *b)
+	{
+		if (ssv_samdec_decode(ctx, text, bytes, SSV_MEM_HOST, last, b) != SSV_OK) {
+			const string m = ssv_last_error(ctx);
+			die(m.compare(0, 11, "Parse error") == 0 ? m : "[seeksv] " + m);
+		}
+		check(ctx, ssv_samdec_names(ctx, &names));
+	}
+	// false: the file is over (every chunk has been decoded)
+	bool next(ssv_batch_t *b)
+	{
+		if (over) return false;
+		seeksv::SamTextReader::Chunk ck, nx;
+		string err;
+		if (rd.next(ck, err)) {
+			if (!ck.last && rd.ready_behind(nx)) check(ctx, ssv_samdec_prefetch(ctx, nx.data, nx.bytes));
+			decode(ck.data, ck.bytes, ck.last ? 1 : 0, b);
+			ended = ck.last;
+			return true;
+		}
+		if (!err.empty()) die(err);
+		over = true;
+		if (ended) return false;
+		decode(nullptr, 0, 1, b);
+		ended = true;
+		return true;
+	}
+	void close()
+	{
+		if (ctx) check(ctx, ssv_sync(ctx)); // (the staging buffers go with the reader)
+		rd.close();
+	}
+};
+
+// The one place a text input's contigs come from: the @SQ SN: / LN: list of its header behind the handle every step asks for names and lengths
+// (ssvh_bam_target_name, ssvh_bam_target_lens, ssvh_plan_create) - a handle with no file behind it
+static ssvh_bam *text_header_handle(const vector<string> &names, const vector<int32_t> &lens)
+{
+	vector<const char *> z;
+	for (const string &n : names) z.push_back(n.c_str());
+	ssvh_bam *h = nullptr;
+	if (ssvh_bam_from_header(z.data(), lens.data(), (int32_t)z.size(), &h) != 0) die(string("[seeksv] ") + ssvh_last_error());
+	return h;
+}
+
 struct BatchSource {
 	ssvh_bam *bam = nullptr;
 	ssv_ctx *ctx = nullptr;
@@ -482,6 +596,15 @@ struct BatchSource {
 	bool at_end = false, end_pending = false;
 	uint64_t file_bytes = 0;
 	ssv_bamdec_info info{};
+	// ---- SAM text (a name without ".bam"): always decoded on the GPU, in the decoder's mode for coordinate-sorted originals - `info` is ssv_samdec_lists' ----
+	SamTextDecoder *text = nullptr;
+	// the header of a text input before anything is created (the reference's samopen: its [samopen] line, a missing file, a header without @SQ); open() goes on from it
+	void open_text_header(const string &path, const char *open_error)
+	{
+		text = new SamTextDecoder;
+		text->open(path, open_error);
+		bam = text_header_handle(text->rd.target_names(), text->rd.target_lens());
+	}
 
 	// a run of records [start, end) of the file instead of all of it (virtual offsets of ssvh_bam_partition); before open()
 	bool ranged = false;
@@ -497,6 +620,21 @@ struct BatchSource {
 	void open(const string &path, const std::function<ssv_ctx *()> &get_ctx, bool device_inflate, const char *open_error, const RunSession *run = nullptr)
 	{
 		on_device = device_inflate;
+		if (!is_bam_name(path)) {
+			on_device = true;
+			if (ranged) die("[seeksv] SAM text is read from its start to its end: runs of records (-N) need a BAM");
+			if (run && !run->collect) { // a step behind the run's getclip: the records are in HBM, the text is gone
+				ctx = get_ctx();
+				if (!run->text_input || run->ctx != ctx || run->batches.empty()) die("[seeksv] the original alignments as SAM text are read once, by `seeksv run`; this step would read them again");
+				bam = text_header_handle(run->text_names, run->text_lens);
+				resident = run;
+				return;
+			}
+			if (!text) open_text_header(path, open_error);
+			ctx = get_ctx();
+			text->begin(ctx, true);
+			return;
+		}
 		if (ssvh_bam_open(path.c_str(), &bam) != 0) die(open_error);
 		if (run || !on_device) ctx = get_ctx();
 		if (run && !ranged && !run->collect && ctx && run->ctx == ctx && !run->batches.empty()) { resident = run; on_device = true; return; }
@@ -619,6 +757,13 @@ struct BatchSource {
 			if (ssvh_bam_read_batch(bam, host_batch_records(), keep_all_seq, b) != 0) die(string("[seeksv] ") + ssvh_last_error());
 			return b->n != 0;
 		}
+		if (text) {
+			while (text->next(b)) {
+				check(ctx, ssv_samdec_lists(ctx, &info));
+				if (b->n) return true; // (a chunk can hold only the middle of one long line)
+			}
+			return false;
+		}
 		for (;;) {
 			if (at_end) return false;
 			if (end_pending) { // the last chunk has been handed out: tell the decoder the input is over (an unfinished record is an error)
@@ -714,6 +859,7 @@ struct BatchSource {
 		}
 		if (announced >= cur && ctx) ssv_bamdec_prefetch_drop(ctx); // a chunk on its way that nobody will decode: its copy must have left the host pages
 		for (Slot &S : slot) { if (S.reg_base) { ssv_host_unregister(S.reg_base); S.reg_base = nullptr; } stage_to_pool(S.stage); }
+		if (text) { if (text->ctx) text->close(); delete text; text = nullptr; }
 		if (bam) ssvh_bam_close(bam);
 		bam = nullptr;
 	}
@@ -938,20 +1084,28 @@ static ssv_clip_params clip_params(const GetclipOptions &o)
 static int getclip_single(const GetclipOptions &o, RunSession *run)
 {
 	PhaseTimer pt;
-	{ // like the reference: complain about the input before anything is created
+	BatchSource src;
+	const bool text_input = !is_bam_name(o.bamfile);
+	// like the reference: complain about the input before anything is created (a text input's header is read here, and libbam's [samopen] line printed)
+	if (text_input) src.open_text_header(o.bamfile, "[main_samview] fail to open file for reading.");
+	else {
 		ssvh_bam *probe = nullptr;
 		if (ssvh_bam_open(o.bamfile.c_str(), &probe) != 0) die("[main_samview] fail to open file for reading.");
 		ssvh_bam_close(probe);
 	}
 	ClipOutputs out(o.prefix);
+	if (text_input) {
+		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
+		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_unfinished.push_back(g->path);
+	}
 
-	BatchSource src;
 	src.open(o.bamfile, [&] { return acquire_ctx(o.device, run); }, o.device_inflate, "[main_samview] fail to open file for reading.", run);
 	ssv_ctx *ctx = src.ctx;
 	ssv_clip_params p = clip_params(o);
 	check(ctx, ssv_clip_begin(ctx, &p));
 	ssv_clip_table_format(ctx, table_format_default()); // the compact table over PCIe; expanded by the formatting threads below
 	ssvh_bam *bam = src.bam;
+	if (run && text_input) { run->text_input = true; run->text_names = src.text->rd.target_names(); run->text_lens = src.text->rd.target_lens(); }
 	pt.lap("open+gpu_init");
 
 	// unmapped-pair side channel, StoreUnmapSeqAndQual (clip_reads.h:172-219): paired up, turned into FASTQ text and compressed by threads of its own
@@ -1035,7 +1189,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		if (last) { emitter.join(); pt.lap("wait for the last pass's output"); }
 	};
 	src.pump(0, [&](const ssv_batch_t &b) {
-		pt.lap(o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
+		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
 		{ const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
 		changes_of.emplace_back();
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
@@ -1068,6 +1222,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	cerr << "[GetSClipReads] finished!" << endl;
 	unmapped.finish();
 	out.close();
+	{ std::unique_lock<std::shared_mutex> lk(g_outputs_mu); g_outputs_unfinished.clear(); }
 	pt.lap("gzip");
 	if (pt.on) cerr << "[timing] (unmapped side channel, beside the reading: " << unmapped.records() << " records, " << unmapped.pairs() << " pairs written, its thread busy " << unmapped.busy_seconds() << " s)" << endl;
 	if (pt.on) cerr << "[timing] (format, all passes, beside the reading: " << emit_format_s << " s; gzip: " << emit_gzip_s << " s)" << endl;
@@ -1234,6 +1389,7 @@ static int getclip_ranks(const GetclipOptions &o, RunSession *run)
 static int getclip_main(const GetclipOptions &o, RunSession *run)
 {
 	if (o.verify_crc) g_verify_crc = true;
+	if (o.n_ranks > 1 && !is_bam_name(o.bamfile)) die("seeksv getclip: -N cuts a BAM into runs of records; SAM text is read once, from its start to its end, by one GPU");
 	return o.n_ranks > 1 ? getclip_ranks(o, run) : getclip_single(o, run);
 }
 
@@ -1335,59 +1491,18 @@ static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx
 	check(ctx, ssv_rt_begin(ctx, &rp));
 }
 
-static void *sam_stage_alloc(size_t bytes) { void *p = nullptr; return ssv_host_alloc(bytes, &p) == SSV_OK ? p : nullptr; }
-static void sam_stage_free(void *p) { ssv_host_free(p); }
-
-// A SAM text file through the device decoder: the header on the host, the records' text to the GPU as it is, in chunks cut anywhere (SSV_SAM_CHUNK_KB: their
-// size, 256 MB by default); a reader thread fills page-locked buffers ahead, and chunk k + 1 crosses the host link under chunk k's kernels
-// (ssv_samdec_prefetch).  begin(): once, behind the header; on_batch(): every decoded batch with its names, valid until the call returns.  Shared by the -F pass
-// and by the pass over the clipped-sequence re-alignments: they differ in what they do with a batch.
 static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &names, const std::function<void()> &begin,
                           const std::function<void(const ssv_batch_t &, const ssv_names_t &)> &on_batch)
 {
-	seeksv::SamTextReader rd;
-	string err;
-	if (!rd.open(path, err)) die(kRtOpenError);
-	names = rd.target_names();
-	if (names.empty()) { // (the reference goes on and aborts at its first record: "[sam_read1] missing header? Abort!")
-		cerr << "[samopen] no @SQ lines in the header." << endl;
-		die(kRtOpenError);
-	}
-	cerr << "[samopen] SAM header is present: " << names.size() << " sequences." << endl;
+	SamTextDecoder d;
+	d.open(path, kRtOpenError);
+	names = d.rd.target_names();
 	begin();
-	vector<const char *> cnames;
-	for (const string &s : names) cnames.push_back(s.c_str());
-	ssv_samdec_params sp;
-	memset(&sp, 0, sizeof(sp));
-	sp.n_targets = (int32_t)names.size(); sp.target_names = cnames.data(); sp.first_line = rd.first_record_line();
-	check(ctx, ssv_samdec_begin(ctx, &sp));
-	const char *e = getenv("SSV_SAM_CHUNK_KB");
-	const size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) << 10 : (size_t)256 << 20;
-	rd.start(chunk, sam_stage_alloc, sam_stage_free);
-	seeksv::SamTextReader::Chunk ck, nx;
-	bool ended = false;
+	d.begin(ctx, false);
 	ssv_batch_t b;
-	auto decode = [&](const void *text, size_t bytes, int last) {
-		if (ssv_samdec_decode(ctx, text, bytes, SSV_MEM_HOST, last, &b) != SSV_OK) {
-			const string m = ssv_last_error(ctx);
-			die(m.compare(0, 11, "Parse error") == 0 ? m : "[seeksv] " + m);
-		}
-		ssv_names_t nm;
-		check(ctx, ssv_samdec_names(ctx, &nm));
-		if (b.n) on_batch(b, nm);
-	};
-	while (rd.next(ck, err)) {
-		if (!ck.last && rd.ready_behind(nx)) check(ctx, ssv_samdec_prefetch(ctx, nx.data, nx.bytes));
-		decode(ck.data, ck.bytes, ck.last ? 1 : 0);
-		ended = ck.last;
-	}
-	if (!err.empty()) die(err);
-	if (!ended) decode(nullptr, 0, 1);
-	check(ctx, ssv_sync(ctx)); // (the staging buffers go with the reader)
-	rd.close();
+	while (d.next(&b)) if (b.n) on_batch(b, d.names);
+	d.close();
 }
-
-static bool is_bam_name(const string &path) { return path.size() >= 4 && path.rfind(".bam") == path.size() - 4; }
 
 // the -F file as SAM text
 static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
@@ -1742,7 +1857,9 @@ static int getsv_main(const GetsvOptions &opt, RunSession *run)
 
 	pt.lap("junction_stage");
 	ssvh_bam *bam = nullptr;
-	if (ssvh_bam_open(opt.original_bam.c_str(), &bam) != 0) die("[main_samview] fail to open file " + opt.original_bam + "for reading.");
+	if (run && run->text_input) { // `seeksv run` on SAM text: the header getclip read (the text itself is gone, its records are in HBM)
+		bam = text_header_handle(run->text_names, run->text_lens);
+	} else if (ssvh_bam_open(opt.original_bam.c_str(), &bam) != 0) die("[main_samview] fail to open file " + opt.original_bam + "for reading.");
 	ssv_ctx *ctx = rt_ctx;
 	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(opt.device, run); return ctx; }; // (main() started it before the junction stage)
 
@@ -2673,7 +2790,9 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "The three steps of the pipeline in one process on one GPU: `getclip` (prefix.clip.gz, prefix.clip.fq.gz, prefix.unmapped_[12].fq.gz),\n"
 	     << "`realign` in the place of `bwa mem` (prefix.clip.bam), `getsv` (prefix.sv.txt, prefix.unmapped.clip.fq; filtered junctions on stdout).\n"
 	     << "Every file is what the three commands write one after the other; the BAM is read, inflated and decoded ONCE, on the GPU, and its\n"
-	     << "records stay in HBM for the getsv passes (80 bytes a record).\n\n"
+	     << "records stay in HBM for the getsv passes (80 bytes a record).  An input whose name does not end in .bam is SAM text (plain or gzip; - is\n"
+	     << "standard input, e.g. `samtools view -h in.cram | seeksv run - ref.fa out`): read once, decoded on the GPU, kept the same way; not with -N.\n"
+	     << "(`getsv` and `somatic` as commands of their own do not take the original alignments as SAM text.)\n\n"
 	     << "Options: -c <string>           options handed to getclip, e.g. -c \"-q 5 -s\"\n"
 	     << "         -v <string>           options handed to getsv, e.g. -v \"-b 5 -L 100\"\n"
 	     << "         -a <string>           options handed to realign, e.g. -a \"-c 500 -g -S 8\" (the GPU is chosen by -G here)\n"
@@ -2739,6 +2858,7 @@ static int cmd_run(int argc, char **argv)
 	GetsvOptions sv = parse_words("getsv", sv_opts, parse_getsv);
 	// refused before anything is written
 	// -P: the pass has one source, and the ranks' getclip has another side channel
+	if (ranked && !is_bam_name(bam)) die("seeksv run: -N cuts a BAM into runs of records; SAM text is read once, from its start to its end, by one GPU");
 	if (split && ranked) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N is not supported with it");
 	if (split && !sv.connect_bam.empty()) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
 	if (split && clip.ranks_given) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
@@ -2774,6 +2894,12 @@ static int cmd_run(int argc, char **argv)
 	run->collect = false;
 	run->on_pass = nullptr;
 	pt.lap("run: getclip (decode once, records kept in HBM)");
+	if (pt.on && !run->batches.empty()) { // what stays resident: the same three counts give the same bytes, whichever decoder made the batches
+		int64_t n = 0, ops = 0, sq = 0;
+		for (const ssv_batch_t &b : run->batches) { n += b.n; ops += b.n_cigar_total; sq += b.seqqual_bytes; }
+		cerr << "[timing] (run: " << n << " records kept in " << run->batches.size() << " batches, " << ops << " CIGAR operations, " << sq << " bytes of bases + qualities: "
+		     << (n ? (double)(n * 64 + ops * 4 + sq) / (double)n : 0.0) << " bytes a record in lines, operations and bases)" << endl;
+	}
 	const RunRanks &ranks = run->ranks;
 	const bool by_ranks = run->ranked(); // (fell back: from here on this is `seeksv run` without -N)
 	if (by_ranks && pt.on)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summary of a `rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv` run of `seeksv getsv -F <SAM text>`: per k_sam_* kernel the
+"""Summary of a `rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv` run of `seeksv getsv -F <SAM text>` (or `seeksv getclip <SAM text>`): per k_sam_* kernel the
 number of launches and the total time, their sum per chunk (launches of k_sam_count = chunks), and next to it the host-to-device copies of the same run
 (bytes, time, GB/s) - the time the text takes to cross the host link.
 
@@ -35,6 +35,9 @@ def main():
         print(f"{k:16s} {v[0]:5d} launches {v[1]:9.3f} ms  {v[1] / chunks:8.3f} ms/chunk")
     scans = sum(v[1] for k, v in kern.items() if k.startswith("k_scan_"))
     print(f"k_sam_* sum      {total:9.3f} ms over {chunks} chunks = {total / chunks:.3f} ms/chunk   (all k_scan_* of the run, the -F kernels' included: {scans:.3f} ms)")
+    tid = {k: v for k, v in kern.items() if k.startswith("k_tid_")}  # (a coordinate-sorted original, ssv_samdec_sorted: the contig lists behind the decode)
+    if tid:
+        print(f"k_tid_* sum      {sum(v[1] for v in tid.values()):9.3f} ms over {chunks} chunks = {sum(v[1] for v in tid.values()) / chunks:.3f} ms/chunk")
     rt = sum(v[1] for k, v in kern.items() if k.startswith("k_rt_"))
     print(f"k_rt_* sum       {rt:9.3f} ms")
     dirs = {}
