@@ -397,6 +397,15 @@ def test_pileup_read_cap_across_batch_boundaries(ctx, batch_records):
     assert int(folded["up_depth"].max()) == 7999
 
 
+def discordant_depth_and_max(ctx, batches, plan, mean, sd, min_mapq, target_lens):
+    """Context.discordant_and_depth with the fourth output of ssv_getsv_finish kept: -> counts, range sums, point depths, max_depth (the third value of
+    O.depth: the deepest column of any window, after the read cap)"""
+    ctx.getsv_begin(plan.junctions, plan.windows, mean, sd, target_lens, 4, min_mapq, min_mapq)
+    for b in batches:
+        ctx.getsv_scan(b)
+    return ctx.getsv_finish(plan.ranges, plan.points)
+
+
 def test_pileup_read_cap_synthetic_12000x(ctx):
     """a synthetic sample at 12000x (the regime of a viral contig or chrM in a deep sample): every record is a "deep" record, the one-wavefront
     sweep runs over the whole batch and over batch boundaries; depths, flank sums and discordant tallies equal the oracle's (whose cap is
@@ -411,14 +420,15 @@ def test_pileup_read_cap_synthetic_12000x(ctx):
     ors, opd, omax = O.depth([hb], plan.windows, plan.ranges, plan.points, 20)
     assert 7800 < int(opd.max()) < 8100             # capped: ~10,400 reads per column pass the filter
     db, keep = w.generate_device(0, w.n_total, 0)
-    c, r, p = ctx.discordant_and_depth([db], plan, stats[2], stats[3], 20, hdr.target_lens)
+    c, r, p, mx = discordant_depth_and_max(ctx, [db], plan, stats[2], stats[3], 20, hdr.target_lens)
     assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd)
+    assert mx == omax and 7800 < omax < 8100        # the cap binds: the correction pass has taken the dropped reads out before k_depth_prefix looks for the maximum
     # the same in host batches cut at awkward places
     from test_oracle_golden import split_batch
     cuts = [0, 5000, 5000 + 12345, w.n_total // 2 + 7, w.n_total]
     hbs = [split_batch(hb, cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
-    c2, r2, p2 = ctx.discordant_and_depth(hbs, plan, stats[2], stats[3], 20, hdr.target_lens)
-    assert np.array_equal(c2, oc) and np.array_equal(r2, ors) and np.array_equal(p2, opd)
+    c2, r2, p2, mx2 = discordant_depth_and_max(ctx, hbs, plan, stats[2], stats[3], 20, hdr.target_lens)
+    assert np.array_equal(c2, oc) and np.array_equal(r2, ors) and np.array_equal(p2, opd) and mx2 == omax
     plan.close()
     hdr.close()
 
@@ -453,8 +463,8 @@ def test_pileup_ring_grows_with_a_later_long_read(ctx):
     ors, opd, omax = O.depth([hb2], plan.windows, plan.ranges, plan.points, 20)
     a, b = split_batch(hb2, 0, cut), split_batch(hb2, cut, w.n_total)
     a["max_ref_span"], b["max_ref_span"] = 158, 20150
-    c, r, p = ctx.discordant_and_depth([a, b], plan, stats[2], stats[3], 20, hdr.target_lens)
-    assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd)
+    c, r, p, mx = discordant_depth_and_max(ctx, [a, b], plan, stats[2], stats[3], 20, hdr.target_lens)
+    assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and mx == omax
     assert 7800 < int(opd.max()) < 8100
     plan.close()
     hdr.close()

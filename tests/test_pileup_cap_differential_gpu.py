@@ -14,6 +14,7 @@ import bamio
 import oracle_lib as O
 import pileup_cap_inputs as P
 from seeksv_amd import _abi, host
+from test_hip_golden import discordant_depth_and_max
 from test_oracle_golden import split_batch
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ def loaded(bam_dir, name, q):
         stats = O.isize_stats([hb], q, 5000000)
         cols = [(c.names[t], col) for t, pos in c.stacks for col in range(max(1, pos - 150), min(c.lens[t], pos + 300) + 1)]
         plan = host.Plan(hdr, c.junctions, stats[2], stats[3], extra_points=sorted(set(cols)))   # windows over every stack, a point per column
-        want = (O.discordant([hb], plan.junctions, stats[2], stats[3], 4, q),) + O.depth([hb], plan.windows, plan.ranges, plan.points, q)[:2]
+        want = (O.discordant([hb], plan.junctions, stats[2], stats[3], 4, q),) + O.depth([hb], plan.windows, plan.ranges, plan.points, q)
         assert int(want[2].max()) > (7900 if P.KIND[name] != "control" else 3000)
         _cache[name, q] = (plan, stats, want)
     return (c, hb, span, hdr) + _cache[name, q]
@@ -83,9 +84,11 @@ def stack_cuts(c):
     return out
 
 
-def assert_equal(got, want, what):
+def assert_equal(got, want, what, max_too=True):
     for k, label in enumerate(("counts", "range sums", "point depths")):
         assert np.array_equal(got[k], want[k]), (what, label, np.flatnonzero(got[k] != want[k])[:8])
+    if max_too:
+        assert len(got) == len(want) == 4 and got[3] == want[3], (what, "max_depth", got[3], want[3])
 
 
 @pytest.mark.parametrize("q", QS)
@@ -98,7 +101,7 @@ def test_cap_kernels_equal_the_oracle_however_the_file_is_cut(ctx, bam_dir, name
     runs.append(("cut at the tiles", [m + d for m in range(P.TILE, n, P.TILE) for d in (-1, 1)]))
     runs += [(f"batches of {k}", list(range(k, n, k))) for k in (1000, 4096, 8192)]
     for what, cuts in runs:
-        got = ctx.discordant_and_depth(cut(hb, span, cuts), plan, stats[2], stats[3], q, hdr.target_lens)
+        got = discordant_depth_and_max(ctx, cut(hb, span, cuts), plan, stats[2], stats[3], q, hdr.target_lens)
         assert_equal(got, want, what)
 
 
@@ -127,12 +130,13 @@ def test_primed_context_continues_the_pileup(ctx, bam_dir, name, q):
     for where, k in (("before", max(1, s - 300)), ("inside", s + m * 5 // 8), ("behind", s + m + 300)):
         assert 0 < k < n
         head, tail = cut(hb, span, [k])
-        a = ctx.discordant_and_depth([head], plan, stats[2], stats[3], q, hdr.target_lens)
+        a = discordant_depth_and_max(ctx, [head], plan, stats[2], stats[3], q, hdr.target_lens)
         ctx.getsv_begin(plan.junctions, plan.windows, stats[2], stats[3], hdr.target_lens, 4, q, q)
         prime(ctx, head)                   # (from the file's first record: exact whatever it answers)
         ctx.getsv_scan(tail)
-        b = ctx.getsv_finish(plan.ranges, plan.points)[:3]
-        assert_equal(tuple(x.astype(np.int64) + y.astype(np.int64) for x, y in zip(a, b)), want, where)
+        b = ctx.getsv_finish(plan.ranges, plan.points)
+        assert_equal(tuple(x.astype(np.int64) + y.astype(np.int64) for x, y in zip(a[:3], b[:3])), want, where, max_too=False)
+        assert max(a[3], b[3]) <= want[3] <= a[3] + b[3], where     # (every column's depth is the two runs' sum: the maximum is not additive, only bounded)
     # a replayed batch that begins inside the stack and is shorter than 16,384 records cannot tell: the caller must replay a longer run
     for length in (9000, 13000):
         lo = s + 50

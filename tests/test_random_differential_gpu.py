@@ -8,7 +8,7 @@ import pytest
 
 import oracle_lib as O
 from seeksv_amd import host
-from test_hip_golden import assert_tables_equal
+from test_hip_golden import assert_tables_equal, discordant_depth_and_max
 from test_oracle_golden import split_batch
 
 pytestmark = pytest.mark.gpu
@@ -168,10 +168,10 @@ def test_random_sample_hip_equals_oracle(ctx, seed):
     plan = host.Plan(hdr, juncs, mean, sd, flank_length=int(rng.choice([1, 50, 200])))
     for q in (20, 0):
         oc = O.discordant([b], plan.junctions, mean, sd, 4, q)
-        ors, opd, _ = O.depth([b], plan.windows, plan.ranges, plan.points, q)
+        ors, opd, omax = O.depth([b], plan.windows, plan.ranges, plan.points, q)
         for bs in ([b], parts):
-            c, r, p = ctx.discordant_and_depth(bs, plan, mean, sd, q, hdr.target_lens)
-            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd)
+            c, r, p, mx = discordant_depth_and_max(ctx, bs, plan, mean, sd, q, hdr.target_lens)
+            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and mx == omax
     plan.close()
     hdr.close()
 
@@ -246,11 +246,11 @@ def test_dense_candidates_hip_equals_oracle(ctx, seed):
         assert max(int(((wb >= x) & (wb < x + 4096)).sum()) for x in wb) > 32
     for q in (20, 0):
         oc = O.discordant([b], plan.junctions, 300, 40, 4, q)
-        ors, opd, _ = O.depth([b], plan.windows, plan.ranges, plan.points, q)
-        assert oc.sum() > 0 and ors.sum() > 0
+        ors, opd, omax = O.depth([b], plan.windows, plan.ranges, plan.points, q)
+        assert oc.sum() > 0 and ors.sum() > 0 and omax > 0
         for bs in ([b], parts):
-            c, r, p = ctx.discordant_and_depth(bs, plan, 300, 40, q, hdr.target_lens)
-            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd)
+            c, r, p, mx = discordant_depth_and_max(ctx, bs, plan, 300, 40, q, hdr.target_lens)
+            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and mx == omax
     plan.close()
     hdr.close()
 
@@ -275,10 +275,10 @@ def test_sparse_records_with_tid_runs_hip_equals_oracle(ctx, seed, n):
     parts = [split_batch(b, cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
     for q in (20, 0):
         oc = O.discordant([b], plan.junctions, 300, 40, 4, q)
-        ors, opd, _ = O.depth([b], plan.windows, plan.ranges, plan.points, q)
+        ors, opd, omax = O.depth([b], plan.windows, plan.ranges, plan.points, q)
         for bs in ([b], parts):
-            c, r, p = ctx.discordant_and_depth(bs, plan, 300, 40, q, hdr.target_lens)
-            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd)
+            c, r, p, mx = discordant_depth_and_max(ctx, bs, plan, 300, 40, q, hdr.target_lens)
+            assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and mx == omax
     assert ors.sum() > 0
     plan.close()
     hdr.close()
@@ -300,9 +300,9 @@ def test_scan_with_an_empty_first_contig(ctx):
     hdr = host.Header(names, lens)
     plan = host.Plan(hdr, juncs, 300, 40, flank_length=50)
     oc = O.discordant([b], plan.junctions, 300, 40, 4, 20)
-    ors, opd, _ = O.depth([b], plan.windows, plan.ranges, plan.points, 20)
-    c, r, p = ctx.discordant_and_depth([b], plan, 300, 40, 20, hdr.target_lens)
-    assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and ors.sum() > 0
+    ors, opd, omax = O.depth([b], plan.windows, plan.ranges, plan.points, 20)
+    c, r, p, mx = discordant_depth_and_max(ctx, [b], plan, 300, 40, 20, hdr.target_lens)
+    assert np.array_equal(c, oc) and np.array_equal(r, ors) and np.array_equal(p, opd) and ors.sum() > 0 and mx == omax
     plan.close()
     hdr.close()
 
