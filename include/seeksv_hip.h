@@ -347,6 +347,37 @@ int ssv_clip_table_wait(ssv_ctx *ctx, ssv_cluster_table *out);
 /* The table of the call before the most recent ssv_clip_cluster[_async] (pipelined drivers: cluster k+1, then collect table k). */
 int ssv_clip_table_wait_prev(ssv_ctx *ctx, ssv_cluster_table *out);
 
+/* ---- somatic: the tumor rows' look-ups among the normal's clusters, on the table where it lies (v9, additive; `seeksv somatic -K`) ----
+ * What ReadTumorFileAndOutputSomaticInfo (somatic.cpp:58-427) asks of the normal sample's clusters is two look-ups per row; a look-up is a probe.  A cluster is
+ * (tid, pos, side, seq_left, seq_right, support); its clipped side is seq_left for side '5' and seq_right for side '3'.  A probe sees the clusters of its own
+ * tid and side whose clipped side has at least min_clipped_len characters (unsigned compare, somatic.h:54), in the table's order (by position, ties in creation
+ * order), and the FIRST that matches gives the hit:
+ *   begin(x, y): n = min(|x|, |y|), m = the i < n with x[i] == y[i]; true iff n > 0 and (double)m / n >= match_rate.  end(x, y): the same from the last characters.
+ *   mode 0 (exact):    candidates with pos == lo; match iff begin(b, seq_right) && end(a, seq_left)
+ *   mode 1 / 2 (anchored): candidates with lo <= pos <= hi; (s1, s2, s3, s4) = (seq_left, seq_right, a, b) in mode 1, (a, b, seq_left, seq_right) in mode 2;
+ *                      no match if |s2| < 10; h = the FIRST occurrence of s2[0..10) in s4 (none: no match; a later one is never tried);
+ *                      match iff end(s1, s3 + s4[0..h)) && begin(s2, s4[h..))          (Compare, clip_reads.cpp:333-370)
+ * Over passes (a BAM is several; a contig may come back in a later one) the order is that of the reference's multimap over the whole file: smaller position
+ * first, equal positions in pass order - a later pass's match replaces the stored hit only when its pos is strictly smaller (an exact probe: only when there is none). */
+typedef struct {
+	int32_t tid;            /* contig id in the scanned batches' header; < 0: not in the header, the probe finds nothing */
+	int32_t lo, hi;         /* 1-based breakpoint positions, inclusive; an exact probe has lo == hi; lo may be <= 0 */
+	uint8_t side;           /* '3' or '5' */
+	uint8_t mode;           /* 0 exact, 1 anchored (cluster first), 2 anchored (probe first) */
+	uint8_t pad[2];
+	uint32_t a_off, a_len, b_off, b_len;   /* the probe's two strings, in `text` */
+} ssv_clip_probe;
+typedef struct { int32_t support, pos, pass, pad; int64_t cluster; } ssv_clip_probe_hit;   /* support 0: no cluster matched; pass: 0-based count of clustered passes since the set; cluster: index in that pass's table */
+
+/* Copies probes and text to the device and zeroes the hits.  The probes stay set across ssv_clip_begin calls until a set with n == 0, the next set or
+ * ssv_ctx_destroy; while they are set, every ssv_clip_cluster[_async] runs them against that pass's table (timing group `somatic_probe`) - the table must
+ * be format 0: a format-3 cluster call returns SSV_E_ARG.  NULL arguments with n > 0, a side other than '3' / '5', a mode above 2, an offset plus length
+ * beyond text_bytes: SSV_E_ARG, and nothing is changed. */
+int ssv_clip_probe_set(ssv_ctx *ctx, const ssv_clip_probe *probes, int64_t n, const char *text, uint64_t text_bytes,
+                       double match_rate, uint32_t min_clipped_len);
+/* Synchronises; the hits accumulated over all passes clustered since the set, and how many passes that was. */
+int ssv_clip_probe_get(ssv_ctx *ctx, ssv_clip_probe_hit *hits /* [n] */, int64_t *passes);
+
 /* ---- getsv pass 1: replaces CalculateInsertsizeDeviation (cluster.cpp:15-83) ---------------- */
 
 int ssv_isize_begin(ssv_ctx *ctx, int32_t min_mapq, int64_t max_pairs);

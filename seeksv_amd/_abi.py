@@ -333,6 +333,11 @@ RA_F_ALT_CUT = 4  # ssv_realign_query_alts: more loci qualified than max_alt
 REALIGN_GAP = [("q_at", "<i4"), ("len", "<i4")]  # ssv_realign_gap
 
 
+CLIP_PROBE_DTYPE = np.dtype([("tid", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("side", "u1"), ("mode", "u1"), ("pad", "u1", (2,)),
+                             ("a_off", "<u4"), ("a_len", "<u4"), ("b_off", "<u4"), ("b_len", "<u4")])  # ssv_clip_probe
+CLIP_PROBE_HIT_DTYPE = np.dtype([("support", "<i4"), ("pos", "<i4"), ("pass", "<i4"), ("pad", "<i4"), ("cluster", "<i8")])  # ssv_clip_probe_hit
+
+
 class RealignIndexStats(C.Structure):  # ssv_realign_index_stats
     _fields_ = [("n_indexed", C.c_int64), ("n_distinct", C.c_int64), ("occ_max", C.c_int64), ("n_over_cap", C.c_int64)]
 
@@ -413,5 +418,7 @@ def hip_lib():
         lib.ssv_samdec_sorted.argtypes = [V, C.c_int]
         lib.ssv_samdec_lists.argtypes = [V, C.POINTER(BamdecInfo)]
         lib.ssv_aln_pack.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(AlnCols)]
+        lib.ssv_clip_probe_set.argtypes = [V, V, C.c_int64, V, C.c_uint64, C.c_double, C.c_uint32]
+        lib.ssv_clip_probe_get.argtypes = [V, V, C.POINTER(C.c_int64)]
         lib._typed = True
     return lib

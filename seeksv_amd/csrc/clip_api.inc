@@ -830,11 +830,15 @@ static int table_presize(ssv_ctx *c, const TableSet &T, TableSet &O)
 	return SSV_OK;
 }
 
+static bool probes_set(const ssv_ctx *c);                // probe_api.inc: ssv_clip_probe_set has left probes
+static int probe_after_pack(ssv_ctx *c, TableSet &T);   // ... which look at every pass's table where it lies
+
 int ssv_clip_cluster_async(ssv_ctx *c, int64_t *n_clusters, int64_t *n_events)
 {
 	if (!c) return SSV_E_ARG;
 	ssv_clip_state &C = *c->clip;
 	if (!C.active) { c->err = "ssv_clip_cluster before ssv_clip_begin"; return SSV_E_STATE; }
+	if (probes_set(c) && C.table_mode != 0) { c->err = "ssv_clip_cluster: the probes of ssv_clip_probe_set read the ASCII table (ssv_clip_table_format 0), not format 3"; return SSV_E_ARG; }
 	HIPCHECK(c, hipSetDevice(c->device));
 	// take the table set that is not the most recent one; its previous copy (two calls ago) must have landed
 	const int s_ = C.tab_cur ^ 1;
@@ -846,7 +850,7 @@ int ssv_clip_cluster_async(ssv_ctx *c, int64_t *n_clusters, int64_t *n_events)
 	table_begin(C, T, E);
 	if (n_events) *n_events = E;
 	if (n_clusters) *n_clusters = 0;
-	if (E == 0) { HIPCHECK(c, hipStreamSynchronize(c->st)); return SSV_OK; }
+	if (E == 0) { if (probes_set(c)) CHECK(probe_after_pack(c, T)); HIPCHECK(c, hipStreamSynchronize(c->st)); return SSV_OK; } // (an empty pass is a pass: the probes count it)
 	CHECK(ensure(c, c->totals, 128)); CHECK(ensure_host(c, c->h_totals, 128));
 	CHECK(ensure(c, C.qual_seen, 32)); CHECK(ensure(c, C.qual_lut, 256)); CHECK(ensure_host(c, C.h_qual_lut, 256));
 	CHECK(ensure(c, C.pair_lut, 16384)); CHECK(ensure_host(c, C.h_pair_lut, 16384)); // (pairs: 4096 halves; triples: 4096 dwords)
@@ -856,6 +860,7 @@ int ssv_clip_cluster_async(ssv_ctx *c, int64_t *n_clusters, int64_t *n_events)
 	CHECK(cluster_bins(c, cur, ca));
 	CHECK(cluster_pack(c, T, ca));
 	if (n_clusters) *n_clusters = T.n_clusters;
+	if (probes_set(c)) CHECK(probe_after_pack(c, T));
 	if (T.n_clusters == 0) return SSV_OK;
 	CHECK(table_copy_out(c, s_));
 	if (!C.tab[s_ ^ 1].in_flight) CHECK(table_presize(c, T, C.tab[s_ ^ 1]));

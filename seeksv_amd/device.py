@@ -369,6 +369,31 @@ class Context:
         tables.append(self.clip_cluster())
         return tables[0] if len(tables) == 1 else concat_tables(tables)
 
+    # ---- somatic: look-ups among a pass's clusters where they lie ----
+    def clip_probe_set(self, probes, match_rate=0.9, min_clipped_len=10):
+        """probes: dicts (tid, lo, hi, side, mode, a, b) or tuples in that order; side '3' / '5' (or its code), a / b str or bytes.  They stay set - every
+        clip_cluster runs them against its table (format 0) - until a set with no probes, the next set, or the context's end (ssv_clip_probe_set)."""
+        keys = ("tid", "lo", "hi", "side", "mode", "a", "b")
+        arr = np.zeros(len(probes), dtype=_abi.CLIP_PROBE_DTYPE)
+        text = bytearray()
+        for i, p in enumerate(probes):
+            tid, lo, hi, side, mode, a, b = (p[k] for k in keys) if isinstance(p, dict) else p
+            a, b = (x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in (a, b))
+            side = ord(side) if isinstance(side, (str, bytes)) else int(side)
+            arr[i] = (tid, lo, hi, side, mode, (0, 0), len(text), len(a), len(text) + len(a), len(b))
+            text += a + b
+        buf = (C.c_char * max(len(text), 1)).from_buffer_copy(bytes(text) or b"\0")
+        self._check(self._lib.ssv_clip_probe_set(self._h, arr.ctypes.data if len(arr) else None, len(arr), C.addressof(buf), len(text), float(match_rate), int(min_clipped_len) & 0xffffffff),
+                    "ssv_clip_probe_set")
+        self._n_probes = len(arr)
+
+    def clip_probe_get(self):
+        """-> (hits: structured array support / pos / pass / cluster per probe, support 0 = no cluster matched; passes clustered since the set)"""
+        hits = np.zeros(getattr(self, "_n_probes", 0), dtype=_abi.CLIP_PROBE_HIT_DTYPE)
+        passes = C.c_int64()
+        self._check(self._lib.ssv_clip_probe_get(self._h, hits.ctypes.data if len(hits) else None, C.byref(passes)), "ssv_clip_probe_get")
+        return hits, passes.value
+
     # ---- getsv pass 1 ----
     def isize_stats(self, batches, min_mapq=20, max_pairs=5000000):
         """-> (rc, n_pairs, mean, sd); rc == 1 when no pair qualifies (the reference's return value)."""

@@ -41,6 +41,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "junction_stage.h"
@@ -175,7 +176,12 @@ static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv]
 
 [[noreturn]] static void usage_somatic()
 {
-	cerr << "Usage: seeksv somatic [options] <input normal original bam> <input normal soft-clipped reads file(*.clip.gz)> <input tumor SV file> <output somatic SV file>\n\n"
+	cerr << "Usage: seeksv somatic [options] <input normal original bam> <input normal soft-clipped reads file(*.clip.gz)> <input tumor SV file> <output somatic SV file>\n"
+	     << "       seeksv somatic -K [-c \"getclip options\"] [options] <input normal original bam> <input tumor SV file> <output somatic SV file>\n\n"
+	     << "         -K                    no clip.gz: the normal BAM is decoded once and stays in GPU memory, its soft-clip clusters are built there as `getclip` builds\n"
+	     << "                               them and looked up on the GPU; the output is that of `getclip` on the normal followed by `somatic`.  Writes no other file.\n"
+	     << "                               Not with -N above 1; the normal must be a BAM\n"
+	     << "         -c <string>           with -K: options of the clip pass, as `getclip` takes them (-t, -q, -s; not -N, -G, -o)\n"
 	     << "         -t <double>           Threshold of match rate while comparing two soft-clipped reads [0.9]\n"
 	     << "         -q <int>              Minimum mapping quality of discordant read pair [20]\n"
 	     << "         -l <int>              Maximum search length to find microhomology [30]\n"
@@ -330,6 +336,9 @@ struct RunSession {
 	struct Piece { string rows, fq; vector<seeksv::ClipRow> parsed; vector<FqRef> reads; bool clean = true; };
 	std::deque<Piece> pieces;    // (a deque: a piece never moves, the views stay good)
 	std::function<void(const vector<Piece *> &)> on_pass; // called by getclip's output thread with the pieces of the pass it has just written
+	// `seeksv somatic -K`: the pass exists for its records (kept, as above) and for the look-ups the library runs against every pass's table (ssv_clip_probe_set):
+	// no output file is opened, no row is formatted, the unmapped pairs are not collected, and getclip's own stderr lines are not printed
+	bool probe_only = false;
 	bool all_clean() const { for (const Piece &p : pieces) if (!p.clean) return false; return true; }
 	vector<seeksv::TextView> row_views() const { vector<seeksv::TextView> v; for (const Piece &p : pieces) v.push_back(seeksv::TextView{p.rows.data(), p.rows.size()}); return v; }
 	// what the aligner step made of the clipped sequences (clip.bam is written all the same); the read names point into the pieces' FASTQ text
@@ -1031,7 +1040,7 @@ static void index_piece(RunSession::Piece &p, const vector<RowAt> &ix)
 struct GetclipOptions {
 	double threshold = 0.9;
 	int min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
-	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false;
+	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false, prefix_given = false;
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1047,7 +1056,7 @@ static GetclipOptions parse_getclip(int argc, char **argv, bool for_run = false)
 		case 't': o.threshold = atof(optarg); break;
 		case 'q': o.min_mapQ = atoi(optarg); break;
 		case 's': o.save_low_quality = true; break;
-		case 'o': o.prefix = optarg; break;
+		case 'o': o.prefix = optarg; o.prefix_given = true; break;
 		case 'G': o.set_devices(optarg); o.devices_given = true; break;
 		case 'Z': o.device_inflate = true; break;
 		case 'C': o.verify_crc = true; break;
@@ -1064,8 +1073,9 @@ static GetclipOptions parse_getclip(int argc, char **argv, bool for_run = false)
 // getclip's four outputs, created in the reference's order with its messages
 struct ClipOutputs {
 	GzOut soft, fq, unmapped1, unmapped2;
-	explicit ClipOutputs(const string &prefix)
+	explicit ClipOutputs(const string &prefix, bool create = true) // (create == false: a pass that writes nothing - nothing is opened, and nothing may be written or closed)
 	{
+		if (!create) return;
 		const char *suffix[4] = {".clip.gz", ".clip.fq.gz", ".unmapped_1.fq.gz", ".unmapped_2.fq.gz"};
 		GzOut *out[4] = {&soft, &fq, &unmapped1, &unmapped2};
 		for (int k = 0; k < 4; ++k) if (!out[k]->open(prefix + suffix[k])) die("Cannot open file " + prefix + suffix[k]);
@@ -1093,7 +1103,8 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		if (ssvh_bam_open(o.bamfile.c_str(), &probe) != 0) die("[main_samview] fail to open file for reading.");
 		ssvh_bam_close(probe);
 	}
-	ClipOutputs out(o.prefix);
+	const bool probe_only = run && run->probe_only; // `somatic -K`, see RunSession
+	ClipOutputs out(o.prefix, !probe_only);
 	if (text_input) {
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_unfinished.push_back(g->path);
@@ -1103,7 +1114,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	ssv_ctx *ctx = src.ctx;
 	ssv_clip_params p = clip_params(o);
 	check(ctx, ssv_clip_begin(ctx, &p));
-	ssv_clip_table_format(ctx, table_format_default()); // the compact table over PCIe; expanded by the formatting threads below
+	ssv_clip_table_format(ctx, probe_only ? 0 : table_format_default()); // the compact table over PCIe; expanded by the formatting threads below (the probes read the ASCII table, and nobody reads its copy)
 	ssvh_bam *bam = src.bam;
 	if (run && text_input) { run->text_input = true; run->text_names = src.text->rd.target_names(); run->text_lens = src.text->rd.target_lens(); }
 	pt.lap("open+gpu_init");
@@ -1131,6 +1142,13 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	std::thread emitter;
 	double emit_format_s = 0, emit_gzip_s = 0;
 	auto emit_pass = [&](bool last) {
+		if (probe_only) { // the library runs the probes behind the table's kernels; the table itself is nobody's
+			check(ctx, ssv_clip_cluster_async(ctx, nullptr, nullptr));
+			pt.lap("gpu_cluster+probes");
+			pass_flushes.clear();
+			pass_records = 0;
+			return;
+		}
 		if (emitter.joinable()) emitter.join();
 		pt.lap("wait for the previous pass's output");
 		ssv_cluster_table t;
@@ -1190,14 +1208,17 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	};
 	src.pump(0, [&](const ssv_batch_t &b) {
 		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
-		{ const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
+		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
 		changes_of.emplace_back();
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
 		pt.lap("host_side_channel");
 	}, [&](const ssv_batch_t &decoded) {
 		ssv_batch_t b = decoded;
 		if (run && run->collect) { // `seeksv run`: the batch stays in HBM for the getsv passes
-			check(ctx, ssv_batch_retain(ctx, &decoded, &b));
+			const int rc = ssv_batch_retain(ctx, &decoded, &b);
+			if (rc == SSV_E_NOMEM && probe_only)
+				die("seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead");
+			check(ctx, rc);
 			run->batches.push_back(b);
 		}
 		int64_t lo = 0;
@@ -1219,9 +1240,9 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	});
 	pass_flushes.push_back(scan_last_tid);
 	emit_pass(true);
-	cerr << "[GetSClipReads] finished!" << endl;
+	if (!probe_only) cerr << "[GetSClipReads] finished!" << endl;
 	unmapped.finish();
-	out.close();
+	if (!probe_only) out.close();
 	{ std::unique_lock<std::shared_mutex> lk(g_outputs_mu); g_outputs_unfinished.clear(); }
 	pt.lap("gzip");
 	if (pt.on) cerr << "[timing] (unmapped side channel, beside the reading: " << unmapped.records() << " records, " << unmapped.pairs() << " pairs written, its thread busy " << unmapped.busy_seconds() << " s)" << endl;
@@ -1984,6 +2005,25 @@ static int cmd_getsv(int argc, char **argv) { return getsv_main(parse_getsv(argc
 // somatic (CallSomatic, seeksv.cpp:366-407; ReadTumorFileAndOutputSomaticInfo, somatic.cpp:14-427)
 // ---------------------------------------------------------------------------------------------------------------------
 
+static vector<string> split_words(const string &t)
+{
+	vector<string> w;
+	std::istringstream in(t);
+	for (string x; in >> x;) w.push_back(x);
+	return w;
+}
+
+// the words of run's -c / -v / -a through the step's own parser (words[0]: the step's name, as getopt prints it)
+template <class Options> static Options parse_words(const char *step, const string &text, Options (*parse)(int, char **, bool))
+{
+	vector<string> words = {step};
+	for (auto &x : split_words(text)) words.push_back(x);
+	vector<char *> av;
+	for (auto &w : words) av.push_back(const_cast<char *>(w.c_str()));
+	av.push_back(nullptr);
+	return parse((int)words.size(), av.data(), true);
+}
+
 struct SomaticOptions {
 	int offset = 30, min_len_of_clipped_seq = 10, read_pair_used = 5000000, min_mapQ = 20, device = 0, n_ranks = 1;
 	double min_map_rate = 0.9;
@@ -1991,6 +2031,8 @@ struct SomaticOptions {
 	bool device_inflate = device_inflate_default(), verify_crc = false;
 	vector<int> devices;
 	string normal_bam_file, clipped_file, tumor_file, somatic_file;
+	bool from_bam = false; // -K: no clip.gz - the normal's clusters come from its BAM, and the look-ups run on the GPU where the clusters lie
+	GetclipOptions clip;   // -K: the clip pass's options (-c: getclip's -t / -q / -s; the defaults are getclip's)
 };
 
 static SomaticOptions parse_somatic(int argc, char **argv)
@@ -1998,7 +2040,9 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	SomaticOptions o;
 	int c;
 	optind = 0;
-	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:")) >= 0) {
+	string clip_opts;
+	bool clip_opts_given = false;
+	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:")) >= 0) {
 		switch (c) {
 		case 't': o.min_map_rate = atof(optarg); break;
 		case 'q': o.min_mapQ = atoi(optarg); break;
@@ -2009,26 +2053,114 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 		case 'Z': o.device_inflate = true; break;
 		case 'C': o.verify_crc = true; break;
 		case 'N': o.n_ranks = atoi(optarg); break;
-		case 'J': o.dump_lookups = optarg; break; // test hook: the host look-ups only (no BAM pass, no GPU), one line per output row
+		case 'J': o.dump_lookups = optarg; break; // test hook: the look-ups only (no insert-size or tally pass; without -K no BAM pass and no GPU), one line per output row
+		case 'K': o.from_bam = true; break;
+		case 'c': clip_opts = optarg; clip_opts_given = true; break;
 		}
 	}
 	if (o.n_ranks < 1) usage_somatic();
-	if (argc != optind + 4) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
+	if (clip_opts_given && !o.from_bam) die("seeksv somatic: -c hands getclip's options to the clip pass of -K; without -K there is no such pass");
+	if (argc != optind + (o.from_bam ? 3 : 4)) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
 	else if (o.offset >= 90 || o.offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
-	o.normal_bam_file = argv[optind]; o.clipped_file = argv[optind + 1]; o.tumor_file = argv[optind + 2]; o.somatic_file = argv[optind + 3];
+	o.normal_bam_file = argv[optind];
+	if (!o.from_bam) { o.clipped_file = argv[optind + 1]; o.tumor_file = argv[optind + 2]; o.somatic_file = argv[optind + 3]; return o; }
+	o.tumor_file = argv[optind + 1]; o.somatic_file = argv[optind + 2];
+	// -K: refused before anything is written
+	o.clip = parse_words("getclip", clip_opts, parse_getclip);
+	if (o.clip.ranks_given || o.clip.devices_given || o.clip.prefix_given)
+		die("seeksv somatic -K: -N, -G or -o inside -c is not supported; the clip pass runs on somatic's own GPU (-G) and writes no file");
+	if (o.n_ranks > 1) die("seeksv somatic -K: -N above 1 is not supported; the look-ups run against one GPU's cluster tables");
+	if (!is_bam_name(o.normal_bam_file)) die("seeksv somatic -K: the normal must be a BAM (a name ending in .bam); SAM text is not supported");
+	o.clip.bamfile = o.normal_bam_file; o.clip.device = o.device; o.clip.devices = vector<int>(1, o.device); o.clip.n_ranks = 1;
+	o.clip.device_inflate = true; // (as `seeksv run`: decoded on the GPU, where the records stay)
+	if (o.verify_crc) o.clip.verify_crc = true;
 	return o;
+}
+
+static void dump_lookups(const string &path, const vector<SomaticRow> &rows)
+{
+	ofstream jd(path.c_str());
+	for (auto &row : rows) {
+		if (row.kind == SomaticRow::HEADER) jd << row.text << '\n';
+		else if (row.kind == SomaticRow::MESSAGE) cerr << row.text << endl;
+		else jd << row.text << '\t' << row.normal_left_reads << '\t' << row.normal_right_reads << '\n';
+	}
+}
+
+// `somatic -K`, first half: the tumor rows' look-ups as probes (build_cluster_probes), set in the library, and ONE getclip pass over the normal BAM through the session
+// machinery of `seeksv run` - its batches stay in HBM for the insert-size and tally passes, every pass's cluster table is probed on the GPU where it lies
+// (ssv_clip_cluster with probes set), nothing is written.  rows: the table's rows with both look-ups done.  Returns the session that holds the records.
+static RunSession *somatic_clip_pass(const SomaticOptions &o, vector<SomaticRow> &rows, PhaseTimer &pt)
+{
+	ssvh_bam *bam = nullptr;
+	if (ssvh_bam_open(o.normal_bam_file.c_str(), &bam) != 0) die("[main_samview] fail to open file for reading.");
+	{
+		const string err = parse_tumor_table(o.tumor_file, 1, rows); // (what a row asks of the clusters does not depend on the insert size; `tally` is set by the caller's own parse)
+		if (!err.empty()) die(err);
+	}
+	vector<seeksv::ClusterProbe> probes;
+	vector<pair<int, int>> of_row;
+	seeksv::build_cluster_probes(rows, o.offset, probes, of_row);
+	std::unordered_map<string, int32_t> tid_of; // contig names to ids by the normal's header (the first of equal names)
+	for (int32_t t = 0, nt = ssvh_bam_n_targets(bam); t < nt; ++t) { const char *nm = ssvh_bam_target_name(bam, t); tid_of.emplace(nm ? nm : "", t); }
+	ssvh_bam_close(bam);
+	vector<ssv_clip_probe> dp(probes.size());
+	string text;
+	for (size_t k = 0; k < probes.size(); ++k) {
+		const seeksv::ClusterProbe &p = probes[k];
+		ssv_clip_probe &d = dp[k];
+		memset(&d, 0, sizeof(d));
+		const auto it = tid_of.find(p.chr);
+		d.tid = it == tid_of.end() ? -1 : it->second;
+		d.lo = p.lo; d.hi = p.hi; d.side = (uint8_t)p.side; d.mode = (uint8_t)p.mode;
+		if (text.size() + p.a.size() + p.b.size() >= 0xffffffffull) die("seeksv somatic -K: the tumor table's sequences are 4 GB or more");
+		d.a_off = (uint32_t)text.size(); d.a_len = (uint32_t)p.a.size(); text += p.a;
+		d.b_off = (uint32_t)text.size(); d.b_len = (uint32_t)p.b.size(); text += p.b;
+	}
+	pt.lap("tumor_table+probes");
+	RunSession *const run = new RunSession; // (on the heap, never destroyed: see RunSession)
+	run->ctx = acquire_ctx(o.device, nullptr);
+	run->collect = true; run->probe_only = true;
+	if (pt.on) ssv_prof_enable(run->ctx, 1); // (SSV_TIMING: the probe kernel's own time, below)
+	check(run->ctx, ssv_clip_probe_set(run->ctx, dp.data(), (int64_t)dp.size(), text.data(), (uint64_t)text.size(), o.min_map_rate, (uint32_t)o.min_len_of_clipped_seq));
+	pt.lap("gpu_init+probe_set");
+	getclip_main(o.clip, run);
+	run->collect = false;
+	pt.lap("clip_pass (decode once, records kept in HBM, every pass's table probed)");
+	vector<ssv_clip_probe_hit> hits(dp.size());
+	int64_t passes = 0;
+	check(run->ctx, ssv_clip_probe_get(run->ctx, hits.data(), &passes));
+	check(run->ctx, ssv_clip_probe_set(run->ctx, nullptr, 0, nullptr, 0, o.min_map_rate, 0));
+	for (size_t r = 0; r < rows.size(); ++r) {
+		if (of_row[r].first >= 0) rows[r].normal_left_reads = hits[(size_t)of_row[r].first].support;
+		if (of_row[r].second >= 0) rows[r].normal_right_reads = hits[(size_t)of_row[r].second].support;
+	}
+	if (pt.on) {
+		ssv_prof_enable(run->ctx, 0);
+		double ms = 0; int64_t launches = 0, units = 0;
+		ssv_prof_get(run->ctx, "somatic_probe", &ms, &launches, &units);
+		cerr << "[timing] (somatic -K: " << dp.size() << " probes, " << text.size() << " bytes of text, " << passes << " passes; somatic_probe kernel time " << ms << " ms in " << launches << " launches)" << endl;
+	}
+	pt.lap("probes (get)");
+	return run;
 }
 
 static int somatic_main(const SomaticOptions &o)
 {
 	PhaseTimer pt;
 	if (o.verify_crc) g_verify_crc = true;
+	RunSession *run = nullptr;  // -K: the session that holds the normal's records ...
+	vector<SomaticRow> probed;  // ... and the rows with their look-ups done
+	if (o.from_bam) {
+		run = somatic_clip_pass(o, probed, pt);
+		if (!o.dump_lookups.empty()) { dump_lookups(o.dump_lookups, probed); ssv_sync(run->ctx); return 0; }
+	}
 	// The normal sample's clusters (all host threads: inflate + parse of a 30x sample's 5.5 M rows) are read BESIDE the GPU's work: what a row of the
 	// tumor's table asks of the BAM (somatic.cpp:111,142: whether FindDiscordantReadPairs runs for it) depends on the insert size only, not on the look-ups.
 	NormalClusters normal;
 	string load_warnings, load_err;
 	auto load = [&] { load_err = load_normal_clusters(o.clipped_file, o.min_len_of_clipped_seq, normal, load_warnings); };
-	if (!o.dump_lookups.empty()) {
+	if (!run && !o.dump_lookups.empty()) {
 		load();
 		if (!load_err.empty()) die(load_err);
 		cerr << load_warnings;
@@ -2036,25 +2168,23 @@ static int somatic_main(const SomaticOptions &o)
 		vector<SomaticRow> rows;
 		string err = scan_tumor_table(o.tumor_file, normal.clip3, normal.clip5, o.offset, o.min_map_rate, 1, rows);
 		if (!err.empty()) die(err);
-		ofstream jd(o.dump_lookups.c_str());
-		for (auto &row : rows) {
-			if (row.kind == SomaticRow::HEADER) jd << row.text << '\n';
-			else if (row.kind == SomaticRow::MESSAGE) cerr << row.text << endl;
-			else jd << row.text << '\t' << row.normal_left_reads << '\t' << row.normal_right_reads << '\n';
-		}
+		dump_lookups(o.dump_lookups, rows);
 		return 0;
 	}
-	std::thread loader(load);
+	std::thread loader;
+	if (!run) loader = std::thread(load);
 	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{loader}; // (die() leaves through _exit; a return must not leave the thread behind)
 	ssv_ctx *ctx = nullptr;
-	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(o.device, nullptr); return ctx; }; // (main() started it)
+	auto get_ctx = [&] { if (!ctx) ctx = acquire_ctx(o.device, run); return ctx; }; // (main() started it; -K: the session's)
 	int mean_insert_size = 0, deviation = 0;
 	IsizeCarry carry;
 	string isize_report; // ReadsClipReads' warnings come first on the reference's stderr (seeksv.cpp:392-398): the lines wait for the loader
 	// -N n: the tally over the normal BAM is split like `getsv -N`'s (SSV_GROUP_RCCL_ONE=1: `-N 1` takes that path too, through a one-rank RCCL communicator);
 	// the insert-size pass stays on rank 0, and leaves no open source behind - the ranks read their own ranges
-	const bool ranks_path = o.n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE");
-	if (o.read_pair_used >= 100000) insert_size_pass(get_ctx, o.normal_bam_file, o.device_inflate, o.min_mapQ, o.read_pair_used, mean_insert_size, deviation, ranks_path ? nullptr : &carry, nullptr, &isize_report);
+	// -K: both passes run over the session's batches where they lie, as getsv's do inside `seeksv run`
+	const bool ranks_path = !run && (o.n_ranks > 1 || getenv("SSV_GROUP_RCCL_ONE"));
+	const bool device_inflate = run ? true : o.device_inflate;
+	if (o.read_pair_used >= 100000) insert_size_pass(get_ctx, o.normal_bam_file, device_inflate, o.min_mapQ, o.read_pair_used, mean_insert_size, deviation, ranks_path ? nullptr : &carry, run, &isize_report);
 	get_ctx();
 	pt.lap("isize_pass (+ what was left of the context's start-up)");
 
@@ -2065,7 +2195,11 @@ static int somatic_main(const SomaticOptions &o)
 	vector<SomaticRow> rows;
 	{
 		string err = parse_tumor_table(o.tumor_file, mean_insert_size, rows);
-		if (!err.empty()) { loader.join(); if (!load_err.empty()) die(load_err); cerr << load_warnings << isize_report; die(err); }
+		if (!err.empty()) { if (loader.joinable()) loader.join(); if (!load_err.empty()) die(load_err); cerr << load_warnings << isize_report; die(err); }
+		if (run) { // the same file parsed again, now with the insert size: the look-ups are the clip pass's
+			if (rows.size() != probed.size()) die("seeksv somatic -K: the tumor table changed while it was read");
+			for (size_t r = 0; r < rows.size(); ++r) { rows[r].normal_left_reads = probed[r].normal_left_reads; rows[r].normal_right_reads = probed[r].normal_right_reads; }
+		}
 	}
 	pt.lap("tumor_table");
 
@@ -2086,24 +2220,24 @@ static int somatic_main(const SomaticOptions &o)
 		const ssv_junction *dj = ssvh_plan_junctions(plan, &nj);
 		vector<int32_t> counts((size_t)nj + 1, 0);
 		RanksTally T; // counts only: no windows, hence nothing to replay
-		T.bam_path = o.normal_bam_file; T.device_inflate = o.device_inflate;
+		T.bam_path = o.normal_bam_file; T.device_inflate = device_inflate;
 		memset(&T.gp, 0, sizeof(T.gp));
 		T.gp.junctions = dj; T.gp.n_junctions = nj;
 		T.gp.mean = mean_insert_size; T.gp.sd = deviation; T.gp.times = times; T.gp.disc_min_mapq = o.min_mapQ;
 		T.gp.n_windows = 0; T.gp.depth_min_mapq = o.min_mapQ;
 		T.gp.n_targets = ssvh_bam_n_targets(bam); T.gp.target_len = ssvh_bam_target_lens(bam);
 		T.n_counts = (size_t)nj; T.counts = counts.data();
-		tally_records(ctx, T, ranks_path ? o.n_ranks : 0, o.devices, carry, nullptr);
+		tally_records(ctx, T, ranks_path ? o.n_ranks : 0, o.devices, carry, run);
 		vector<int32_t> prev(J.size() + 1, 0); // a row whose left contig is not in the normal's header reports 0
 		ssvh_plan_fold(plan, counts.data(), prev.data(), nullptr, nullptr, abnormal.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
 		ssvh_plan_destroy(plan);
 	} else carry.drop(ctx);
 	pt.lap("discordant_pass");
-	loader.join();
+	if (loader.joinable()) loader.join();
 	if (!load_err.empty()) die(load_err);
 	cerr << load_warnings << isize_report;
 	pt.lap("normal_clusters (wait: read beside the passes)");
-	probe_normal_clusters(rows, normal.clip3, normal.clip5, o.offset, o.min_map_rate);
+	if (!run) probe_normal_clusters(rows, normal.clip3, normal.clip5, o.offset, o.min_map_rate);
 	pt.lap("cluster_lookups");
 	pt.lap("discordant_pass");
 	size_t k = 0;
@@ -2121,6 +2255,7 @@ static int somatic_main(const SomaticOptions &o)
 		fout << row.text << '\t' << row.normal_left_reads << '\t' << row.normal_right_reads << '\t' << normal_abnormal << endl;
 	}
 	pt.lap("output");
+	if (run && kCleanExit) for (auto &b : run->batches) ssv_batch_release(ctx, &b);
 	release_ctx(ctx, nullptr);
 	ssvh_bam_close(bam);
 	pt.lap("teardown");
@@ -2808,25 +2943,6 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               then take neither -N nor -G (-H inside -c sets the halo) [1]\n"
 	     << "         -G <int>[,<int>...]   GPU ordinal [0]; with -N: the ranks' GPUs [all GPUs of the machine in order]" << endl;
 	exit(1);
-}
-
-static vector<string> split_words(const string &t)
-{
-	vector<string> w;
-	std::istringstream in(t);
-	for (string x; in >> x;) w.push_back(x);
-	return w;
-}
-
-// the words of run's -c / -v / -a through the step's own parser (words[0]: the step's name, as getopt prints it)
-template <class Options> static Options parse_words(const char *step, const string &text, Options (*parse)(int, char **, bool))
-{
-	vector<string> words = {step};
-	for (auto &x : split_words(text)) words.push_back(x);
-	vector<char *> av;
-	for (auto &w : words) av.push_back(const_cast<char *>(w.c_str()));
-	av.push_back(nullptr);
-	return parse((int)words.size(), av.data(), true);
 }
 
 static int cmd_run(int argc, char **argv)

@@ -330,11 +330,81 @@ void probe_normal_clusters(std::vector<SomaticRow> &rows, const ClusterIndex &cl
 	}
 }
 
+// probe_normal_clusters' case analysis with nothing run: every branch above, operand for operand, as a probe
+void build_cluster_probes(const std::vector<SomaticRow> &rows, int offset, std::vector<ClusterProbe> &probes, std::vector<std::pair<int, int>> &of_row)
+{
+	of_row.assign(rows.size(), std::make_pair(-1, -1));
+	auto exact = [&](char side, const std::string &chr, int pos, const std::string &left, const std::string &right) {
+		probes.push_back(ClusterProbe{side, chr, pos, pos, 0, left, right});
+		return (int)probes.size() - 1;
+	};
+	auto range = [&](char side, const std::string &chr, int lo, int hi, bool cluster_first, const std::string &a, const std::string &b) {
+		probes.push_back(ClusterProbe{side, chr, lo, hi, cluster_first ? 1 : 2, a, b});
+		return (int)probes.size() - 1;
+	};
+	for (size_t r = 0; r < rows.size(); ++r) {
+		const SomaticRow &row = rows[r];
+		if (row.kind != SomaticRow::JUNCTION) continue;
+		const std::string &up_chr = row.up_chr, &down_chr = row.down_chr, &up_seq = row.up_seq, &down_seq = row.down_seq;
+		const int up_pos = row.up_pos, down_pos = row.down_pos, mh = row.microhomology;
+		const bool pp = row.up_strand == '+' && row.down_strand == '+', pm = row.up_strand == '+' && row.down_strand == '-';
+		std::string rc_up = up_seq, rc_down = down_seq;
+		reverse_complement(rc_up);
+		reverse_complement(rc_down);
+		int left = -1, right = -1;
+		if (mh != -1) {
+			if (pp) {
+				right = exact('5', down_chr, down_pos, up_seq, down_seq);
+				if (down_seq.length() >= (size_t)mh) // unsigned compare, somatic.cpp:92
+					left = exact('3', up_chr, up_pos + mh, up_seq + down_seq.substr(0, (size_t)mh), down_seq.substr((size_t)mh));
+			} else if (pm) {
+				left = exact('3', up_chr, up_pos + mh, up_seq + down_seq.substr(0, (size_t)mh), down_seq.substr((size_t)mh));
+				right = exact('3', down_chr, down_pos, rc_down, rc_up);
+			} else {
+				left = exact('5', up_chr, up_pos, rc_down, rc_up);
+				const size_t cut = up_seq.length() - (size_t)mh;
+				right = exact('5', down_chr, down_pos - mh, up_seq.substr(0, cut), up_seq.substr(cut) + down_seq);
+			}
+		} else if (row.up_reads == 0) {
+			if (pp) { right = exact('5', down_chr, down_pos, up_seq, down_seq); left = range('3', up_chr, up_pos, up_pos + offset, true, up_seq, down_seq); }
+			else if (pm) { right = exact('3', down_chr, down_pos, rc_down, rc_up); left = range('3', up_chr, up_pos, up_pos + offset, true, up_seq, down_seq); }
+			else { right = exact('5', down_chr, down_pos, up_seq, down_seq); left = range('5', up_chr, up_pos - offset, up_pos, false, rc_up, rc_down); }
+		} else {
+			if (pp) { left = exact('3', up_chr, up_pos, up_seq, down_seq); right = range('5', down_chr, down_pos - offset, down_pos, false, up_seq, down_seq); }
+			else if (pm) { left = exact('3', up_chr, up_pos, up_seq, down_seq); right = range('3', down_chr, down_pos, down_pos + offset, true, rc_down, rc_up); }
+			else { left = exact('5', up_chr, up_pos, rc_down, rc_up); right = range('5', down_chr, down_pos - offset, down_pos, false, up_seq, down_seq); }
+		}
+		of_row[r] = std::make_pair(left, right);
+	}
+}
+
+// the probes over the host's ClusterIndex: what the GPU's kernel does against a pass's table (SSV_SOMATIC_PROBES=host: the tests hold the case analysis above
+// against probe_normal_clusters with it)
+void run_cluster_probes_host(std::vector<SomaticRow> &rows, const ClusterIndex &clip3, const ClusterIndex &clip5, int offset, double rate)
+{
+	std::vector<ClusterProbe> probes;
+	std::vector<std::pair<int, int>> of_row;
+	build_cluster_probes(rows, offset, probes, of_row);
+	auto run = [&](int k) {
+		if (k < 0) return 0;
+		const ClusterProbe &p = probes[(size_t)k];
+		const ClusterIndex &m = p.side == '3' ? clip3 : clip5;
+		return p.mode == 0 ? exact_probe(m, p.chr, p.lo, p.a, p.b, rate) : range_probe(m, p.chr, p.lo, p.hi, p.mode == 1, p.a, p.b, rate);
+	};
+	for (size_t r = 0; r < rows.size(); ++r) {
+		if (rows[r].kind != SomaticRow::JUNCTION) continue;
+		rows[r].normal_left_reads = run(of_row[r].first); rows[r].normal_right_reads = run(of_row[r].second);
+	}
+}
+
 std::string scan_tumor_table(const std::string &tumor_sv_file, const ClusterIndex &clip3, const ClusterIndex &clip5, int offset, double rate, int mean_insert_size,
                              std::vector<SomaticRow> &rows)
 {
 	const std::string err = parse_tumor_table(tumor_sv_file, mean_insert_size, rows);
-	if (err.empty()) probe_normal_clusters(rows, clip3, clip5, offset, rate);
+	if (!err.empty()) return err;
+	const char *how = getenv("SSV_SOMATIC_PROBES"); // (tests) host: the look-ups as probes, built by build_cluster_probes and run over the same index
+	if (how && !strcmp(how, "host")) run_cluster_probes_host(rows, clip3, clip5, offset, rate);
+	else probe_normal_clusters(rows, clip3, clip5, offset, rate);
 	return err;
 }
 

@@ -67,6 +67,14 @@ struct SomaticRow {
 // wants the discordant tally: needs the insert size only) and the look-ups among the normal's clusters - so that the BAM pass need not wait for clip.gz.
 std::string parse_tumor_table(const std::string &tumor_sv_file, int mean_insert_size, std::vector<SomaticRow> &rows); // "" or an error text
 void probe_normal_clusters(std::vector<SomaticRow> &rows, const ClusterIndex &clip3, const ClusterIndex &clip5, int offset, double min_map_rate);
+// The look-ups of probe_normal_clusters as data: what a row asks, not yet asked (`somatic -K` sends them to the GPU, where the normal's clusters are).
+// side: which of the two maps; [lo, hi]: the positions looked at (an exact probe has lo == hi; lo may be zero or negative: up_pos - offset);
+// mode 0: exact (a = left, b = right), 1: anchored_compare(cluster.left, cluster.right, a, b), 2: anchored_compare(a, b, cluster.left, cluster.right).
+struct ClusterProbe { char side; std::string chr; int lo, hi; int mode; std::string a, b; };
+// of_row[r] = (left probe, right probe) of rows[r], -1 = none: the result stays 0
+void build_cluster_probes(const std::vector<SomaticRow> &rows, int offset, std::vector<ClusterProbe> &probes, std::vector<std::pair<int, int>> &of_row);
+// the probes run on the host over the index (tests: SSV_SOMATIC_PROBES=host sends scan_tumor_table this way)
+void run_cluster_probes_host(std::vector<SomaticRow> &rows, const ClusterIndex &clip3, const ClusterIndex &clip5, int offset, double min_map_rate);
 // both, one after the other
 std::string scan_tumor_table(const std::string &tumor_sv_file, const ClusterIndex &clip3, const ClusterIndex &clip5, int offset, double min_map_rate,
                              int mean_insert_size, std::vector<SomaticRow> &rows);
