@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
+                             v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
                              v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
                              v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
                              v9 (additive, same version): ssv_realign_query_alts, SSV_RA_F_ALT_CUT (`seeksv realign -S`).
@@ -797,6 +798,48 @@ typedef struct {
 int ssv_rt_begin(ssv_ctx *ctx, const ssv_rt_params *p);
 int ssv_rt_scan(ssv_ctx *ctx, const ssv_batch_t *b, const ssv_names_t *names);
 int ssv_rt_finish(ssv_ctx *ctx, ssv_rt_result *out);
+
+/* ---- duplicate read pairs marked while the sample is retained (v9, additive; `seeksv run -M`, `seeksv somatic -K -M`) ----------------------
+ * Every pass honours the duplicate flag 0x400; this stage sets it, in the retained copy only, before any pass reads a flag.  The rule is this library's own (it
+ * follows `samtools rmdup` where it can; no external duplicate marker was run or matched).  Records come in file order, coordinate sorted; a RUN is a maximal
+ * stretch of consecutive records with equal (tid, pos).
+ *   takes part  flag & 0x1 set, none of 0x4 | 0x8 | 0x100 | 0x800 | 0x400 set, tid >= 0 and mtid >= 0 (a record that arrives with 0x400 stays marked and takes
+ *               no part); every other record is never touched
+ *   head        takes part and (tid, pos) < (mtid, mpos), or the two are equal and flag & 0x40; every other record that takes part is a tail
+ *   group       heads with equal (tid, pos, mtid, mpos, flag & 0x10, flag & 0x20): inside one run
+ *   score       0 when l_qseq == 0 or the first quality byte is 0xff, else the sum of the quality bytes that are >= 15 (32 bits)
+ *   keeper      the group's highest score, among equal scores the earliest in the file; every other head of the group gets flag |= 0x400
+ *   digest      64-bit FNV-1a (offset 1469598103934665603, prime 1099511628211) over the read name's bytes without the NUL, then over four little-endian
+ *               int32: a head's (tid, pos, mtid, mpos), a tail's (mtid, mpos, tid, pos) - a tail computes its head's digest from its own fields
+ *   tail        gets flag |= 0x400 iff its digest equals that of some marked head whose run is not later than the tail's own run
+ * SSV_DUP_DIGEST_BITS=k in the environment at ssv_dup_begin keeps the digest's low k bits (tests: forced collisions follow the same rule).
+ * Limits: aligned pos / mpos, not unclipped 5' ends (two copies clipped differently are not found); single reads and pairs with an unmapped end are never
+ * marked; libraries (RG / LB) are not told apart; a pair is scored by its head alone.
+ *
+ * ssv_dup_retain takes the place of ssv_batch_retain for a stream of device batches in file order (names: the batch's read names, as ssv_rt_scan takes them).
+ * The last run of a batch may go on in the next one, and its keeper may lie there: the call holds back the batch's trailing run (the maximal suffix with the
+ * last record's (tid, pos); none when that record has tid < 0 - such records take no part) and puts it in front of the next call's records.  *out is a
+ * retained batch like ssv_batch_retain's (given back with ssv_batch_release): the *carried records held back before, then this batch's records up to its own
+ * trailing run - with last != 0 everything.  Every flag in *out is final on return; out->n may be 0; cigar_off / seq_off are those of *out's own arrays;
+ * max_ref_span covers both parts; tid_runs is NULL.  The concatenation of all *out is the input, record for record, with the rule's flags, however the stream
+ * was cut.  *out keeps bases + qualities only for records whose first or last CIGAR operation is S (the others get SSV_NO_SEQ): the input must carry the
+ * qualities of every record that takes part (decode with keep_all_seq).
+ * Errors leave everything as it was: NULL arguments, a host batch, a record that takes part without its qualities: SSV_E_ARG; (tid, pos) going down between two
+ * neighbouring records with tid >= 0 (the held-back run included): SSV_E_ARG "not coordinate sorted"; no ssv_dup_begin, or a call after `last`: SSV_E_STATE.
+ * SSV_DUP_SET_SLOTS=n (tests): the digest set starts with n slots (a power of two; it is kept at most half full and doubles).
+ * Timed as dup_select, dup_mark, dup_retain. */
+typedef struct {
+	int64_t records;      /* records handed out in all *out so far */
+	int64_t taking_part;  /* of them: records that take part */
+	int64_t groups;       /* groups that were looked at: those with a head in a run of two or more records */
+	int64_t heads_marked, tails_marked;
+	int64_t set_entries;  /* distinct digests in the set */
+	int64_t held_max;     /* the longest hold-back, in records */
+} ssv_dup_stats;
+int ssv_dup_begin(ssv_ctx *ctx);
+int ssv_dup_retain(ssv_ctx *ctx, const ssv_batch_t *device_batch, const ssv_names_t *names, int last, ssv_batch_t *out, int64_t *carried);
+/* Ends the stream (also one that was not ended with `last`: what is still held back is dropped) and hands the counts out. */
+int ssv_dup_finish(ssv_ctx *ctx, ssv_dup_stats *out);
 
 #ifdef __cplusplus
 }

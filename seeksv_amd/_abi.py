@@ -342,6 +342,10 @@ class RealignIndexStats(C.Structure):  # ssv_realign_index_stats
     _fields_ = [("n_indexed", C.c_int64), ("n_distinct", C.c_int64), ("occ_max", C.c_int64), ("n_over_cap", C.c_int64)]
 
 
+class DupStats(C.Structure):  # ssv_dup_stats
+    _fields_ = [(k, C.c_int64) for k in ("records", "taking_part", "groups", "heads_marked", "tails_marked", "set_entries", "held_max")]
+
+
 def hip_lib():
     """libseeksv_hip.so - raises when it is not built; creating a context raises when there is no GPU."""
     lib = _load("libseeksv_hip.so")
@@ -420,5 +424,9 @@ def hip_lib():
         lib.ssv_aln_pack.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(AlnCols)]
         lib.ssv_clip_probe_set.argtypes = [V, V, C.c_int64, V, C.c_uint64, C.c_double, C.c_uint32]
         lib.ssv_clip_probe_get.argtypes = [V, V, C.POINTER(C.c_int64)]
+        lib.ssv_dup_begin.argtypes = [V]
+        lib.ssv_dup_retain.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.c_int, C.POINTER(Batch), C.POINTER(C.c_int64)]
+        lib.ssv_dup_finish.argtypes = [V, C.POINTER(DupStats)]
+        lib.ssv_batch_lines_to_host.argtypes = [V, C.POINTER(Batch), V]
         lib._typed = True
     return lib

@@ -46,6 +46,7 @@
 #include "samdec_kernels.h"
 #include "alnpack_kernels.h"
 #include "probe_kernels.h"
+#include "dup_kernels.h"
 #include "scan.h"
 
 using namespace ssv;
@@ -55,9 +56,9 @@ namespace {
 thread_local std::string g_create_error; // (per thread: ssv_last_error(NULL) is asked by the thread whose call failed; rank and reader threads run side by side)
 
 // timed kernel groups (ssv_prof_*)
-enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_RT_SCAN, P_RT_FINISH, P_REALIGN_GAP, P_REALIGN_ALTS, P_REALIGN_ROWS, P_SOMATIC_PROBE, P_COUNT };
-const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve", "rt_scan", "rt_finish", "realign_gap", "realign_alts", "realign_rows", "somatic_probe"};
-const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve\nrt_scan\nrt_finish\nrealign_gap\nrealign_alts\nrealign_rows\nsomatic_probe";
+enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_RT_SCAN, P_RT_FINISH, P_REALIGN_GAP, P_REALIGN_ALTS, P_REALIGN_ROWS, P_SOMATIC_PROBE, P_DUP_SELECT, P_DUP_MARK, P_DUP_RETAIN, P_COUNT };
+const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve", "rt_scan", "rt_finish", "realign_gap", "realign_alts", "realign_rows", "somatic_probe", "dup_select", "dup_mark", "dup_retain"};
+const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve\nrt_scan\nrt_finish\nrealign_gap\nrealign_alts\nrealign_rows\nsomatic_probe\ndup_select\ndup_mark\ndup_retain";
 
 hipError_t pinned_delete(void *p);
 
@@ -176,6 +177,7 @@ struct ssv_rt_state;     // readthrough_api.inc
 struct ssv_samdec_state; // samdec_api.inc
 struct ssv_alnpack_state; // alnpack_api.inc
 struct ssv_probe_state;  // probe_api.inc
+struct ssv_dup_state;    // dup_api.inc
 
 struct ssv_ctx { // (created and deleted below the stage files only: the state structs are complete there)
 	int device = 0;
@@ -226,6 +228,7 @@ struct ssv_ctx { // (created and deleted below the stage files only: the state s
 	std::unique_ptr<ssv_samdec_state> sd;
 	std::unique_ptr<ssv_alnpack_state> ap;
 	std::unique_ptr<ssv_probe_state> probe;
+	std::unique_ptr<ssv_dup_state> dup;
 
 	// ---- profiling ----
 	int prof_mode = 0;
@@ -818,6 +821,45 @@ int stage_batch(ssv_ctx *c, const ssv_batch_t *b, DevBatch &d, bool keep_announc
 	return SSV_OK;
 }
 
+// `need` bytes (a multiple of 256: every batch starts 256-byte aligned) for a batch that stays (ssv_batch_retain, ssv_dup_retain): room in the newest arena,
+// or a new one - 256 MB first, doubling up to SSV_RETAIN_ARENA_MB (4 GB), never smaller than the batch.  The arena counts the slab as live; a caller that
+// fails afterwards takes it back (retain_slab_undo).
+int retain_slab(ssv_ctx *c, size_t need, ssv_ctx::RetainArena **arena_out, uint8_t **slab)
+{
+	ssv_ctx::RetainArena *arena = nullptr;
+	if (!c->arenas.empty() && c->arenas.back().cap - c->arenas.back().used >= need) arena = &c->arenas.back();
+	else {
+		static const size_t arena_max = []() { const char *e = getenv("SSV_RETAIN_ARENA_MB"); return (size_t)(e ? atoll(e) : 4096) << 20; }();
+		size_t cap = c->arenas.empty() ? std::min(arena_max, (size_t)256 << 20) : std::min(arena_max, c->arenas.back().cap * 2);
+		if (cap < need) cap = need;
+		ssv_ctx::RetainArena a;
+		// a spare one that is large enough (the smallest such), else a new one
+		size_t pick = c->spare_arenas.size();
+		for (size_t k = 0; k < c->spare_arenas.size(); ++k)
+			if (c->spare_arenas[k].cap >= need && (pick == c->spare_arenas.size() || c->spare_arenas[k].cap < c->spare_arenas[pick].cap)) pick = k;
+		if (pick < c->spare_arenas.size()) { a.base = c->spare_arenas[pick].base; cap = c->spare_arenas[pick].cap; c->spare_arenas.erase(c->spare_arenas.begin() + (long)pick); }
+		else {
+			size_t acap = 0;
+			if (uint8_t *b = arena_ahead_take(c, &acap)) { // the one asked for ahead - if this batch fits (else it waits among the spares)
+				if (acap >= need) { a.base = b; cap = acap; }
+				else c->spare_arenas.push_back({b, acap});
+			}
+			if (!a.base) HIPCHECK(c, dev_malloc(c, reinterpret_cast<void **>(&a.base), cap));
+		}
+		a.cap = cap;
+		c->arenas.push_back(a);
+		arena = &c->arenas.back();
+		// the next one, while this one fills (not when spares are waiting: a context that has been through a release has its memory)
+		if (c->spare_arenas.empty()) arena_ahead_start(c, std::min(arena_max, cap * 2));
+	}
+	*slab = arena->base + arena->used;
+	arena->slabs.push_back(arena->used);
+	arena->used += need; ++arena->live;
+	*arena_out = arena;
+	return SSV_OK;
+}
+inline void retain_slab_undo(ssv_ctx::RetainArena *arena, size_t need) { --arena->live; arena->used -= need; arena->slabs.pop_back(); }
+
 __global__ void k_max_span(DevBatch b, int *out)
 {
 	int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -966,39 +1008,10 @@ int ssv_batch_retain(ssv_ctx *c, const ssv_batch_t *b, ssv_batch_t *out)
 		memcpy(runs, b->tid_runs, (size_t)b->n_tid_runs * sizeof(ssv_tid_run));
 	}
 	ssv_ctx::RetainArena *arena = nullptr;
-	struct Guard { ssv_ctx::RetainArena *&arena; size_t need; ssv_tid_run *&runs; bool keep = false; ~Guard() { if (!keep) { if (arena) { --arena->live; arena->used -= need; arena->slabs.pop_back(); } free(runs); } } } guard{arena, off[7], runs};
+	struct Guard { ssv_ctx::RetainArena *&arena; size_t need; ssv_tid_run *&runs; bool keep = false; ~Guard() { if (!keep) { if (arena) retain_slab_undo(arena, need); free(runs); } } } guard{arena, off[7], runs};
 	static const bool timing = [] { const char *e = getenv("SSV_TIMING"); return e ? atoi(e) : 0; }() >= 2; // SSV_TIMING=2: per-chunk detail
 	const auto t0 = std::chrono::steady_clock::now();
-	{ // room in the newest arena, or a new one: 256 MB first, doubling up to SSV_RETAIN_ARENA_MB (4 GB), never smaller than the batch
-		if (!c->arenas.empty() && c->arenas.back().cap - c->arenas.back().used >= off[7]) arena = &c->arenas.back();
-		else {
-			static const size_t arena_max = []() { const char *e = getenv("SSV_RETAIN_ARENA_MB"); return (size_t)(e ? atoll(e) : 4096) << 20; }();
-			size_t cap = c->arenas.empty() ? std::min(arena_max, (size_t)256 << 20) : std::min(arena_max, c->arenas.back().cap * 2);
-			if (cap < off[7]) cap = off[7];
-			ssv_ctx::RetainArena a;
-			// a spare one that is large enough (the smallest such), else a new one
-			size_t pick = c->spare_arenas.size();
-			for (size_t k = 0; k < c->spare_arenas.size(); ++k)
-				if (c->spare_arenas[k].cap >= off[7] && (pick == c->spare_arenas.size() || c->spare_arenas[k].cap < c->spare_arenas[pick].cap)) pick = k;
-			if (pick < c->spare_arenas.size()) { a.base = c->spare_arenas[pick].base; cap = c->spare_arenas[pick].cap; c->spare_arenas.erase(c->spare_arenas.begin() + (long)pick); }
-			else {
-				size_t acap = 0;
-				if (uint8_t *b = arena_ahead_take(c, &acap)) { // the one asked for ahead - if this batch fits (else it waits among the spares)
-					if (acap >= off[7]) { a.base = b; cap = acap; }
-					else c->spare_arenas.push_back({b, acap});
-				}
-				if (!a.base) HIPCHECK(c, dev_malloc(c, reinterpret_cast<void **>(&a.base), cap));
-			}
-			a.cap = cap;
-			c->arenas.push_back(a);
-			arena = &c->arenas.back();
-			// the next one, while this one fills (not when spares are waiting: a context that has been through a release has its memory)
-			if (c->spare_arenas.empty()) arena_ahead_start(c, std::min(arena_max, cap * 2));
-		}
-		slab = arena->base + arena->used;
-		arena->slabs.push_back(arena->used);
-		arena->used += off[7]; ++arena->live; // (off[] are multiples of 256: every batch starts 256-byte aligned)
-	}
+	CHECK(retain_slab(c, off[7], &arena, &slab));
 	const auto t1 = std::chrono::steady_clock::now();
 	const void *src[7] = {d.tid, d.pos, d.n_cigar, d.ends, d.rec, d.cigar, d.seqqual};
 	const size_t bytes[7] = {n * 4, n * 4, n * 2, n, n * sizeof(ssv_record), (size_t)b->n_cigar_total * 4, (size_t)b->seqqual_bytes};
@@ -1089,6 +1102,7 @@ const char *ssv_prof_names(void) { return kProfNameList; }
 #include "readthrough_api.inc"
 #include "samdec_api.inc"
 #include "alnpack_api.inc"
+#include "dup_api.inc"
 #include "group_api.inc"
 
 

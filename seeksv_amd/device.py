@@ -286,6 +286,32 @@ class Context:
     def batch_release(self, batch):
         self._check(self._lib.ssv_batch_release(self._h, C.byref(batch)), "ssv_batch_release")
 
+    # ---- duplicate read pairs marked while the sample is retained (ssv_dup_*: `seeksv run -M`) ----
+    def dup_begin(self):
+        """ssv_dup_begin: a new stream of batches in file order"""
+        self._check(self._lib.ssv_dup_begin(self._h), "ssv_dup_begin")
+
+    def dup_retain(self, batch, names, last=False):
+        """ssv_dup_retain in the place of batch_retain: the decoder's device batch (with every record's qualities) and its names (bamdec_names() /
+        samdec_names(), or a list) -> (Batch, carried): a retained batch with final flags - the `carried` records held back by the call before, then
+        this batch's records up to its own trailing run (all of them with last) - to be given back with batch_release"""
+        n, keep_names = self._as_names(names)
+        out, carried = _abi.Batch(), C.c_int64()
+        self._check(self._lib.ssv_dup_retain(self._h, C.byref(batch), C.byref(n), int(bool(last)), C.byref(out), C.byref(carried)), "ssv_dup_retain")
+        return out, carried.value
+
+    def dup_finish(self):
+        """ssv_dup_finish -> dict of the stream's counts (ssv_dup_stats)"""
+        st = _abi.DupStats()
+        self._check(self._lib.ssv_dup_finish(self._h, C.byref(st)), "ssv_dup_finish")
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def batch_lines(self, dev_batch):
+        """the record lines of a device batch (a retained one too) -> numpy array of _abi.RECORD_DTYPE (a hook of the tests, no part of the C ABI)"""
+        lines = np.zeros(int(dev_batch.n), dtype=_abi.RECORD_DTYPE)
+        self._check(self._lib.ssv_batch_lines_to_host(self._h, C.byref(dev_batch), lines.ctypes.data if len(lines) else None), "ssv_batch_lines_to_host")
+        return lines
+
     def batch_to_host(self, dev_batch):
         """Device batch -> dict of owned numpy arrays (tests)."""
         h = _abi.Batch()

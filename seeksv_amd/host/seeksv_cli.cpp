@@ -94,6 +94,7 @@ struct PhaseTimer {
 static std::shared_mutex g_outputs_mu;
 static vector<string> g_outputs_unfinished;
 static bool g_dying = false;
+static vector<string> g_outputs_refused; // `run -M`: what the run created before its input turned out not to be coordinate sorted is taken away again
 
 [[noreturn]] static void die(const string &msg)
 {
@@ -101,6 +102,7 @@ static bool g_dying = false;
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		g_dying = true;
 		for (const string &p : g_outputs_unfinished) if (truncate(p.c_str(), 0) != 0) {} // (nothing more can be done about it here)
+		for (const string &p : g_outputs_refused) if (unlink(p.c_str()) != 0) {}
 	}
 	cerr << msg << endl;
 	cout.flush(); cerr.flush(); fflush(nullptr);
@@ -182,6 +184,8 @@ static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv]
 	     << "                               them and looked up on the GPU; the output is that of `getclip` on the normal followed by `somatic`.  Writes no other file.\n"
 	     << "                               Not with -N above 1; the normal must be a BAM\n"
 	     << "         -c <string>           with -K: options of the clip pass, as `getclip` takes them (-t, -q, -s; not -N, -G, -o)\n"
+	     << "         -M                    with -K: mark duplicate read pairs of the normal (flag 0x400) on the GPU where its records are retained, before any pass reads a\n"
+	     << "                               flag: the output of `somatic -K` on the same BAM with those flags set.  The rule and its limits: `seeksv run`'s -M\n"
 	     << "         -t <double>           Threshold of match rate while comparing two soft-clipped reads [0.9]\n"
 	     << "         -q <int>              Minimum mapping quality of discordant read pair [20]\n"
 	     << "         -l <int>              Maximum search length to find microhomology [30]\n"
@@ -1041,6 +1045,7 @@ struct GetclipOptions {
 	double threshold = 0.9;
 	int min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
 	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false, prefix_given = false;
+	bool mark_dups = false; // `run -M`, `somatic -K -M` (no option of getclip's own): duplicate read pairs are marked where the records are retained
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1108,6 +1113,10 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	if (text_input) {
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_unfinished.push_back(g->path);
+	}
+	if (o.mark_dups && !probe_only) { // -M: an input that is not coordinate sorted is refused where the stage meets it, and the run leaves no file behind
+		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
+		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_refused.push_back(g->path);
 	}
 
 	src.open(o.bamfile, [&] { return acquire_ctx(o.device, run); }, o.device_inflate, "[main_samview] fail to open file for reading.", run);
@@ -1206,23 +1215,18 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		});
 		if (last) { emitter.join(); pt.lap("wait for the last pass's output"); }
 	};
-	src.pump(0, [&](const ssv_batch_t &b) {
-		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
-		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
-		changes_of.emplace_back();
-		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
-		pt.lap("host_side_channel");
-	}, [&](const ssv_batch_t &decoded) {
-		ssv_batch_t b = decoded;
-		if (run && run->collect) { // `seeksv run`: the batch stays in HBM for the getsv passes
-			const int rc = ssv_batch_retain(ctx, &decoded, &b);
-			if (rc == SSV_E_NOMEM && probe_only)
-				die("seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead");
-			check(ctx, rc);
-			run->batches.push_back(b);
-		}
+	// -M: retention goes through ssv_dup_retain, which holds back a batch's trailing run: what it hands out is the records held back before, then the decoded
+	// batch's up to its own trailing run.  The decoder's contig changes are relative to the decoded batch: they move by the records held back, and those that
+	// fall into the new hold-back wait for the batch that brings their record (dup_pending: relative to the hold-back's first record).
+	const bool mark_dups = o.mark_dups && run && run->collect;
+	int64_t dup_held = 0;
+	vector<pair<int64_t, int32_t>> dup_pending;
+	if (mark_dups && pt.on) ssv_prof_enable(ctx, 1); // (SSV_TIMING: the stage's own kernel time, below)
+	if (mark_dups) check(ctx, ssv_dup_begin(ctx));
+	// the records of a retained (or decoded) batch through the clip scan, the pass ending in front of every contig that comes back
+	auto scan_batch = [&](const ssv_batch_t &b, const vector<pair<int64_t, int32_t>> &changes) {
 		int64_t lo = 0;
-		for (const auto &ch : changes_of.front()) {
+		for (const auto &ch : changes) {
 			pass_flushes.push_back(scan_last_tid); // the visit that ends here is flushed
 			if (ch.second <= pass_max_tid || pass_records + (ch.first - lo) >= pass_records_max) { // a contig that comes back (or a pass that is long enough): the pass ends in front of this record
 				check(ctx, ssv_clip_scan_range(ctx, &b, lo, ch.first));
@@ -1233,17 +1237,81 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			}
 			pass_max_tid = scan_last_tid = ch.second;
 		}
-		changes_of.pop_front();
 		check(ctx, ssv_clip_scan_range(ctx, &b, lo, b.n));
 		pass_records += b.n - lo;
+	};
+	// -M: one call of ssv_dup_retain (decoded == nullptr: the end of the file, which flushes the hold-back) and the scan of what it handed out
+	auto dup_step = [&](const ssv_batch_t *decoded, const vector<pair<int64_t, int32_t>> &changes) {
+		ssv_batch_t none, b;
+		memset(&none, 0, sizeof(none));
+		none.mem = SSV_MEM_DEVICE;
+		ssv_names_t names;
+		memset(&names, 0, sizeof(names));
+		names.mem = SSV_MEM_DEVICE;
+		if (decoded) check(ctx, ssv_bamdec_names(ctx, &names));
+		int64_t carried = 0;
+		const int rc = ssv_dup_retain(ctx, decoded ? decoded : &none, &names, decoded ? 0 : 1, &b, &carried);
+		if (rc == SSV_E_NOMEM && probe_only)
+			die("seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead");
+		check(ctx, rc);
+		vector<pair<int64_t, int32_t>> now;
+		vector<pair<int64_t, int32_t>> later;
+		for (const auto &ch : dup_pending) (ch.first < b.n ? now : later).emplace_back(ch.first < b.n ? ch.first : ch.first - b.n, ch.second);
+		for (const auto &ch : changes) { const int64_t at = dup_held + ch.first; (at < b.n ? now : later).emplace_back(at < b.n ? at : at - b.n, ch.second); }
+		dup_pending.swap(later);
+		dup_held += (decoded ? decoded->n : 0) - b.n;
+		if (b.n == 0) { check(ctx, ssv_batch_release(ctx, &b)); return; } // (a batch that is one run entirely: its records come with a later one)
+		run->batches.push_back(b);
+		scan_batch(b, now);
+	};
+	src.pump(mark_dups ? 1 : 0, [&](const ssv_batch_t &b) {
+		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
+		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
+		changes_of.emplace_back();
+		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
+		pt.lap("host_side_channel");
+	}, [&](const ssv_batch_t &decoded) {
+		if (mark_dups) {
+			dup_step(&decoded, changes_of.front());
+			changes_of.pop_front();
+			pt.lap("gpu_markdup+scan(wait h2d+kernels)");
+			return;
+		}
+		ssv_batch_t b = decoded;
+		if (run && run->collect) { // `seeksv run`: the batch stays in HBM for the getsv passes
+			const int rc = ssv_batch_retain(ctx, &decoded, &b);
+			if (rc == SSV_E_NOMEM && probe_only)
+				die("seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead");
+			check(ctx, rc);
+			run->batches.push_back(b);
+		}
+		scan_batch(b, changes_of.front());
+		changes_of.pop_front();
 		pt.lap("gpu_scan(wait h2d+kernels)");
 	});
+	if (mark_dups) { // the end of the file flushes the hold-back
+		dup_step(nullptr, vector<pair<int64_t, int32_t>>());
+		ssv_dup_stats ds;
+		check(ctx, ssv_dup_finish(ctx, &ds));
+		cerr << "[seeksv] -M: marked " << ds.heads_marked << " + " << ds.tails_marked << " duplicate records (" << ds.groups << " groups) of " << ds.records << endl;
+		pt.lap("gpu_markdup(flush)");
+		if (pt.on) {
+			cerr << "[timing] (-M kernel time:";
+			for (const char *g : {"dup_select", "dup_mark", "dup_retain"}) {
+				double ms = 0; int64_t launches = 0;
+				ssv_prof_get(ctx, g, &ms, &launches, nullptr);
+				cerr << ' ' << g << ' ' << ms << " ms in " << launches << " launches" << (g[4] == 'r' ? "" : ",");
+			}
+			cerr << "; hold-back at most " << ds.held_max << " records, " << ds.set_entries << " digests in the set)" << endl;
+			ssv_prof_enable(ctx, 0);
+		}
+	}
 	pass_flushes.push_back(scan_last_tid);
 	emit_pass(true);
 	if (!probe_only) cerr << "[GetSClipReads] finished!" << endl;
 	unmapped.finish();
 	if (!probe_only) out.close();
-	{ std::unique_lock<std::shared_mutex> lk(g_outputs_mu); g_outputs_unfinished.clear(); }
+	{ std::unique_lock<std::shared_mutex> lk(g_outputs_mu); g_outputs_unfinished.clear(); g_outputs_refused.clear(); }
 	pt.lap("gzip");
 	if (pt.on) cerr << "[timing] (unmapped side channel, beside the reading: " << unmapped.records() << " records, " << unmapped.pairs() << " pairs written, its thread busy " << unmapped.busy_seconds() << " s)" << endl;
 	if (pt.on) cerr << "[timing] (format, all passes, beside the reading: " << emit_format_s << " s; gzip: " << emit_gzip_s << " s)" << endl;
@@ -2031,6 +2099,7 @@ struct SomaticOptions {
 	bool device_inflate = device_inflate_default(), verify_crc = false;
 	vector<int> devices;
 	string normal_bam_file, clipped_file, tumor_file, somatic_file;
+	bool mark_dups = false; // -M (with -K): duplicate read pairs of the normal are marked where its records are retained
 	bool from_bam = false; // -K: no clip.gz - the normal's clusters come from its BAM, and the look-ups run on the GPU where the clusters lie
 	GetclipOptions clip;   // -K: the clip pass's options (-c: getclip's -t / -q / -s; the defaults are getclip's)
 };
@@ -2042,7 +2111,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	optind = 0;
 	string clip_opts;
 	bool clip_opts_given = false;
-	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:")) >= 0) {
+	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:M")) >= 0) {
 		switch (c) {
 		case 't': o.min_map_rate = atof(optarg); break;
 		case 'q': o.min_mapQ = atoi(optarg); break;
@@ -2055,10 +2124,12 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 		case 'N': o.n_ranks = atoi(optarg); break;
 		case 'J': o.dump_lookups = optarg; break; // test hook: the look-ups only (no insert-size or tally pass; without -K no BAM pass and no GPU), one line per output row
 		case 'K': o.from_bam = true; break;
+		case 'M': o.mark_dups = true; break;
 		case 'c': clip_opts = optarg; clip_opts_given = true; break;
 		}
 	}
 	if (o.n_ranks < 1) usage_somatic();
+	if (o.mark_dups && !o.from_bam) die("seeksv somatic: -M marks duplicates where the clip pass of -K retains the normal's records; without -K there is no such pass");
 	if (clip_opts_given && !o.from_bam) die("seeksv somatic: -c hands getclip's options to the clip pass of -K; without -K there is no such pass");
 	if (argc != optind + (o.from_bam ? 3 : 4)) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
 	else if (o.offset >= 90 || o.offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
@@ -2073,6 +2144,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	if (!is_bam_name(o.normal_bam_file)) die("seeksv somatic -K: the normal must be a BAM (a name ending in .bam); SAM text is not supported");
 	o.clip.bamfile = o.normal_bam_file; o.clip.device = o.device; o.clip.devices = vector<int>(1, o.device); o.clip.n_ranks = 1;
 	o.clip.device_inflate = true; // (as `seeksv run`: decoded on the GPU, where the records stay)
+	o.clip.mark_dups = o.mark_dups;
 	if (o.verify_crc) o.clip.verify_crc = true;
 	return o;
 }
@@ -2937,6 +3009,12 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               `seeksv realign -P` on the two files + `seeksv getsv -F`, from one decode.  The records are built on the GPU and stay\n"
 	     << "                               there: no prefix.F.bam is written (`seeksv realign -P` writes one); every other file is unchanged.  Not with -F in -v\n"
 	     << "                               or -N in -c.\n"
+	     << "         -M                    mark duplicate read pairs (flag 0x400) on the GPU while the decoded records are retained, before any pass reads a flag; every pass\n"
+	     << "                               ignores marked records, as with a BAM marked beforehand.  The input must be a coordinate-sorted BAM; no file is written for it.\n"
+	     << "                               This program's own rule, after `samtools rmdup`: pairs with both ends mapped; equal (contig, pos, mate contig, mate pos, strands)\n"
+	     << "                               of the leftmost read; the highest sum of base qualities >= 15 stays, the earliest of equals; the mate follows its read.  Aligned\n"
+	     << "                               positions, not unclipped 5' ends (Picard's): copies clipped differently are not found; single reads and pairs with an unmapped\n"
+	     << "                               end are never marked; read groups / libraries are not told apart.  Not with -N above 1, not on SAM text\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
 	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
 	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
@@ -2949,10 +3027,11 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
-	bool split = false, ranks_given = false;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:")) >= 0) {
+	bool split = false, ranks_given = false, mark_dups = false;
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:M")) >= 0) {
 		switch (c) {
 		case 'P': split = true; break;
+		case 'M': mark_dups = true; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
@@ -2978,6 +3057,9 @@ static int cmd_run(int argc, char **argv)
 	if (split && ranked) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N is not supported with it");
 	if (split && !sv.connect_bam.empty()) die("seeksv run: -P is the -F pass of this run; -F inside -v names another source for it");
 	if (split && clip.ranks_given) die("seeksv run: -P takes the unmapped pairs of a single getclip pass; -N inside -c is not supported with it");
+	// -M: one stream of records in file order, decoded with every record's qualities by the BAM decoder
+	if (mark_dups && ranked) die("seeksv run: -M marks duplicates in one stream of records in file order; -N above 1 is not supported with it");
+	if (mark_dups && !is_bam_name(bam)) die("seeksv run: -M reads a BAM; SAM text is not supported with it");
 	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
 	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
 		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
@@ -2985,7 +3067,7 @@ static int cmd_run(int argc, char **argv)
 	if (clip.ranks_given || clip.devices_given) die("seeksv run: -N or -G inside -c is not supported; the ranks of a run and their GPUs are run's own -N and -G");
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
-	clip.prefix = prefix; clip.bamfile = bam;
+	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups;
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
 
