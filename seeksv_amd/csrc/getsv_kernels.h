@@ -368,7 +368,7 @@ struct GetsvStage {
 // K5/K7 getsv_scan, the streaming pass: reads tid and pos of every record (8 B/record, eight 16-byte loads in flight per lane), looks
 // the record's start tile up in the genome tile map (L2 resident, wave-coherent because the BAM is coordinate sorted) and writes the
 // indices of the ~1 % of records that start near a depth window or a junction window.  Same persistent, atomic-free structure as
-// k_clip_scan; the lookups are branch-free (clamped indices) so that they pipeline.
+// k_clip_scan_ends; the lookups are branch-free (clamped indices) so that they pipeline.
 // Does the whole tile lie inside ONE run of the tid column (then its contig is known without reading the column)?  Workgroup-uniform: a binary
 // search over the <= 48 run starts in the kernel arguments (scalar loads).  -1: no (no runs given, or a run boundary falls into the tile).
 __device__ __forceinline__ int tile_run_tid(const RunTab &R, int64_t tile, int64_t n)
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(BLOCK) void k_getsv_scan(GetsvArgs a, GetsvStage g)
 	for (int64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x, parity ^= 1) {
 		const int64_t t0 = tile * CS_TILE + (int64_t)threadIdx.x * CS_ITEMS;
 		const int64_t next = tile + gridDim.x;
-		if (next < g.ntiles) { nrun = tile_run_tid(a.runs, next, b.n); getsv_scan_load(b, next, nt4, np4, nrun); } // software pipeline, as in k_clip_scan
+		if (next < g.ntiles) { nrun = tile_run_tid(a.runs, next, b.n); getsv_scan_load(b, next, nt4, np4, nrun); } // software pipeline, as in k_clip_scan_ends
 		uint32_t mask = 0;
 		// Fast path (coordinate-sorted input at WGS depth): every record of this wavefront's share of the tile is on one contig and
 		// their start tiles span < 64 genome tiles.  Then 64 tile-map bytes are fetched once per wavefront (one byte per lane), turned
