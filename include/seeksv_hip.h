@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_batch_sort, ssv_sorted, ssv_samdec_any_order (`seeksv run -u`: an original in any order, coordinate sorted while it is retained).
+                             v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
                              v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
                              v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
                              v9 (additive, same version): ssv_clip_table_wire_bytes, ssv_table_wire (what a cluster table's copy really moved).
@@ -615,6 +616,10 @@ int ssv_samdec_sorted(ssv_ctx *ctx, int keep_all_seq);
  * fields - which ssvh_raw_record_fastq reads like the BAM decoder's.  inflated_bytes: the bytes of text the call was given; tail_offset, repaired_blocks: 0.
  * Lifetimes as for ssv_bamdec_last (unmapped_raw: two page-locked buffers in turn, valid until the decode after the next one).  SSV_E_STATE without the mode. */
 int ssv_samdec_lists(ssv_ctx *ctx, ssv_bamdec_info *out);
+/* Optional, after ssv_samdec_begin (v9, additive; `seeksv run -u`): text in any record order, with the meaning of ssv_bamdec_any_order.  A chunk with more than
+ * 65536 contig changes among its mapped-pair records is then decoded like any other; only its contig-change list (ssv_samdec_lists: n_tid_runs = 0) is not
+ * handed out.  Everything else is unchanged; off after every ssv_samdec_begin. */
+int ssv_samdec_any_order(ssv_ctx *ctx, int on);
 
 /* ---- the clipped-sequence re-alignments of `getsv` out of a decoded batch (getsv.h:437-446 opens every name without ".bam" as SAM text) ----
  * What the host join (InputSoftInfoStoreBreakpoint + GetAlignInfo, getsv.h:423-541, getsv.cpp:25-71) reads of every record of clip.bam / clip.sam: tid, pos, flag,
@@ -840,6 +845,37 @@ int ssv_dup_begin(ssv_ctx *ctx);
 int ssv_dup_retain(ssv_ctx *ctx, const ssv_batch_t *device_batch, const ssv_names_t *names, int last, ssv_batch_t *out, int64_t *carried);
 /* Ends the stream (also one that was not ended with `last`: what is still held back is dropped) and hands the counts out. */
 int ssv_dup_finish(ssv_ctx *ctx, ssv_dup_stats *out);
+
+/* ---- an original in any record order, coordinate sorted while it is retained (v9, additive; `seeksv run -u`) -----------------------------------
+ * THE RULE.  The records of in[0 .. n_in) are one sequence: batch order first, then record order.  A record's key is (t, p): t = tid < 0 ? n_targets : tid
+ * (unplaced records come last), p = (uint32_t)(pos + 1) (position -1 in front of position 0).  The output is that sequence stably sorted by (t, p): records
+ * with equal keys keep their input order.  This is the comparison of libbam 0.1.x's sorter (contig, then position, nothing else); newer samtools also breaks
+ * ties by strand.  No external sorter was run or matched, and equality with the output of any one of them is not claimed.  (seeksv's results depend on the
+ * order of ties only through BAM order inside a clip bin.)
+ *
+ * in: batches of ssv_batch_retain / ssv_dup_retain / an earlier ssv_batch_sort (anything else: SSV_E_ARG).  A contig id >= n_targets: SSV_E_ARG; 2^32 records
+ * or more in total: SSV_E_RANGE (the sort carries a record's index as 32 bits); no memory: SSV_E_NOMEM.  On failure the inputs are untouched and still the
+ * caller's.  On success they are released by the call (in[] is zeroed) and out->batches are the caller's, each given back with ssv_batch_release like any
+ * retained batch: the records in sorted order, cut into batches of at most max_out_records records (0: 16 M, or SSV_SORT_BATCH_RECORDS from the environment -
+ * tests), earlier where a batch would reach 2^31 records or 2^32 CIGAR operations.  Every field of every record is unchanged - hot columns, cigar_ends, the
+ * whole line with xc and cigar_head, all operations, the bases + qualities of the records that had them (packed back to back as the decoders pack them;
+ * SSV_NO_SEQ stays SSV_NO_SEQ) - except cigar_off / seq_off, which are those of the new batch.  max_ref_span: the maximum over the inputs (0 when one of them
+ * did not know); tid_runs: filled up to the decoders' 64 runs, NULL above.
+ * Already sorted - (t, p) never goes down, inside and across the batches: the inputs are handed back as out->batches (the same device memory, nothing copied,
+ * no sort or gather kernel launched), already_sorted = 1.
+ * change_*: the contig changes among the records without UNMAP|MUNMAP (flag & 12 == 0), the list ssv_bamdec_info.tid_run_index / tid_run_tid carries, continued
+ * across the output batches from contig 0: batch b's changes are [change_first[b], change_first[b + 1]), change_index counts inside ITS batch.
+ * Memory: inputs and outputs are resident together (twice the retained sample) plus 24 bytes a record of keys and indices.  Synchronises the stream.
+ * Timed as sort_keys (check, keys, change lists), sort_radix, sort_gather (sizes, scans, gather). */
+typedef struct {
+	int64_t n_records, n_batches;
+	int32_t already_sorted, pad;
+	ssv_batch_t *batches;          /* [n_batches] host array owned by the context until the next ssv_batch_sort */
+	const int64_t *change_first;   /* [n_batches + 1] into change_index / change_tid */
+	const uint32_t *change_index;  /* record index inside its batch ... */
+	const int32_t *change_tid;     /* ... and its contig */
+} ssv_sorted;
+int ssv_batch_sort(ssv_ctx *ctx, ssv_batch_t *in, int64_t n_in, int32_t n_targets, int64_t max_out_records, ssv_sorted *out);
 
 #ifdef __cplusplus
 }

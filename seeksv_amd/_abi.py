@@ -346,6 +346,11 @@ class DupStats(C.Structure):  # ssv_dup_stats
     _fields_ = [(k, C.c_int64) for k in ("records", "taking_part", "groups", "heads_marked", "tails_marked", "set_entries", "held_max")]
 
 
+class Sorted(C.Structure):  # ssv_sorted
+    _fields_ = [("n_records", C.c_int64), ("n_batches", C.c_int64), ("already_sorted", C.c_int32), ("pad", C.c_int32), ("batches", C.POINTER(Batch)),
+                ("change_first", C.POINTER(C.c_int64)), ("change_index", C.POINTER(C.c_uint32)), ("change_tid", C.POINTER(C.c_int32))]
+
+
 def hip_lib():
     """libseeksv_hip.so - raises when it is not built; creating a context raises when there is no GPU."""
     lib = _load("libseeksv_hip.so")
@@ -428,5 +433,7 @@ def hip_lib():
         lib.ssv_dup_retain.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.c_int, C.POINTER(Batch), C.POINTER(C.c_int64)]
         lib.ssv_dup_finish.argtypes = [V, C.POINTER(DupStats)]
         lib.ssv_batch_lines_to_host.argtypes = [V, C.POINTER(Batch), V]
+        lib.ssv_batch_sort.argtypes = [V, C.POINTER(Batch), C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sorted)]
+        lib.ssv_samdec_any_order.argtypes = [V, C.c_int]
         lib._typed = True
     return lib

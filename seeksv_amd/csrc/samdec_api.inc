@@ -23,6 +23,7 @@ struct ssv_samdec_state {
 	ssv_samdec_info info{};
 	// ssv_samdec_sorted: a coordinate-sorted original
 	bool sorted = false, keep_all_seq = false, decoded = false, have_lists = false;
+	bool any_order = false; // ssv_samdec_any_order: chunks with more contig changes than the list holds go through without the list
 	int32_t prev_tid = 0; // contig of the last mapped-pair record so far (clip_reads.h:407: starts at 0)
 	DBuf ship, ship_idx, seq_list, raw_bytes, raw_off, raw;
 	HBuf h_raw[2]; // two in turn, as the BAM decoder's: a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded
@@ -58,7 +59,7 @@ int ssv_samdec_begin(ssv_ctx *c, const ssv_samdec_params *p)
 		if (any) HIPCHECK(c, hipStreamSynchronize(c->st_h2d));
 	}
 	d.n_targets = p->n_targets; d.first_line = p->first_line; d.lines_done = 0; d.carry = 0; d.have_batch = false;
-	d.sorted = d.keep_all_seq = d.decoded = d.have_lists = false; d.prev_tid = 0;
+	d.sorted = d.keep_all_seq = d.decoded = d.have_lists = d.any_order = false; d.prev_tid = 0;
 	memset(&d.lists, 0, sizeof(d.lists));
 	memset(&d.info, 0, sizeof(d.info));
 	// the contig names as a hash table: FNV-1a, linear probing, at most half full; the first of two equal names wins
@@ -122,6 +123,16 @@ int ssv_samdec_sorted(ssv_ctx *c, int keep_all_seq)
 	if (!c) return SSV_E_ARG;
 	if (!c->sd || c->sd->phase != ssv_samdec_state::ACTIVE || c->sd->decoded) { c->err = "ssv_samdec_sorted belongs between ssv_samdec_begin and the first ssv_samdec_decode"; return SSV_E_ARG; }
 	c->sd->sorted = true; c->sd->keep_all_seq = keep_all_seq != 0;
+	return SSV_OK;
+}
+
+// Optional, after ssv_samdec_begin: text in any record order (`run -u`).  A chunk with more than 65536 contig changes among
+// its mapped-pair records is then decoded like any other; only its contig-change list (ssv_samdec_lists: n_tid_runs) is not handed out.
+int ssv_samdec_any_order(ssv_ctx *c, int on)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->sd || c->sd->phase != ssv_samdec_state::ACTIVE) { c->err = "ssv_samdec_any_order before ssv_samdec_begin"; return SSV_E_ARG; }
+	c->sd->any_order = on != 0;
 	return SSV_OK;
 }
 
@@ -273,8 +284,10 @@ int ssv_samdec_decode(ssv_ctx *c, const void *text, size_t bytes, int mem, int l
 	HIPCHECK(c, hipStreamSynchronize(st));
 	memcpy(&werr, d.h_small.p, 8);
 	if (werr != ssv::SAM_NO_ERROR) return samdec_refuse(c, werr);
-	const uint32_t n_runs = d.sorted ? hs[12] : 0u, n_raw_runs = d.sorted ? hs[14] : 0u;
+	uint32_t n_runs = d.sorted ? hs[12] : 0u;
+	const uint32_t n_raw_runs = d.sorted ? hs[14] : 0u;
 	const int32_t last_tid = (int32_t)hs[13];
+	if (n_runs > TidLists::RUN_CAP && d.any_order) n_runs = 0; // (the list is incomplete - not handed out; the kernel wrote no more than RUN_CAP entries)
 	if (n_runs > TidLists::RUN_CAP) {
 		c->err = "more than 65536 contig changes in one chunk: the SAM text is not coordinate sorted";
 		d.phase = ssv_samdec_state::FAILED;

@@ -306,6 +306,29 @@ class Context:
         self._check(self._lib.ssv_dup_finish(self._h, C.byref(st)), "ssv_dup_finish")
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    # ---- an original in any order, coordinate sorted while it is retained (ssv_batch_sort: `seeksv run -u`) ----
+    def batch_sort(self, batches, n_targets, max_out_records=0):
+        """ssv_batch_sort: retained batches (batch_retain's) in input order -> dict(n_records, already_sorted, batches: the retained batches that hold the
+        records stably sorted by the rule of include/seeksv_hip.h, each to be given back with batch_release, changes: per output batch the (record, contig)
+        pairs where the contig changes among the records without UNMAP|MUNMAP).  On success the inputs are the call's (released, or - already sorted -
+        handed back as the outputs); on failure they are still the caller's."""
+        arr = (_abi.Batch * max(1, len(batches)))(*batches)
+        out = _abi.Sorted()
+        self._check(self._lib.ssv_batch_sort(self._h, arr, len(batches), int(n_targets), int(max_out_records), C.byref(out)), "ssv_batch_sort")
+        res, changes = [], []
+        for k in range(out.n_batches):
+            b = _abi.Batch()
+            C.memmove(C.byref(b), C.byref(out.batches[k]), C.sizeof(_abi.Batch))
+            res.append(b)
+            lo, hi = out.change_first[k], out.change_first[k + 1]
+            changes.append([(int(out.change_index[j]), int(out.change_tid[j])) for j in range(lo, hi)])
+        return dict(n_records=int(out.n_records), already_sorted=bool(out.already_sorted), batches=res, changes=changes)
+
+    def samdec_any_order(self, on=True):
+        """ssv_samdec_any_order, after samdec_begin: text in any record order - a chunk with more contig changes than the list holds is decoded all the same,
+        without its contig-change list"""
+        self._check(self._lib.ssv_samdec_any_order(self._h, int(bool(on))), "ssv_samdec_any_order")
+
     def batch_lines(self, dev_batch):
         """the record lines of a device batch (a retained one too) -> numpy array of _abi.RECORD_DTYPE (a hook of the tests, no part of the C ABI)"""
         lines = np.zeros(int(dev_batch.n), dtype=_abi.RECORD_DTYPE)

@@ -575,7 +575,7 @@ struct BatchSource {
 	ssv_ctx *ctx = nullptr;
 	bool on_device = false;
 	const RunSession *resident = nullptr; // the records are in HBM already: the run's retained batches
-	bool any_order = false;    // -Z: a file in any record order (getsv -F: split alignments in read order) - ssv_bamdec_any_order
+	bool any_order = false;    // a file in any record order (getsv -F: split alignments in read order; run -u) - ssv_bamdec_any_order, ssv_samdec_any_order
 	size_t resident_next = 0;
 	// ---- device mode: a reader thread runs up to three chunks ahead of the decoder ----
 	// A chunk = whole BGZF blocks, the file's bytes as they are.  Two ways to get them to the GPU:
@@ -646,6 +646,7 @@ struct BatchSource {
 			if (!text) open_text_header(path, open_error);
 			ctx = get_ctx();
 			text->begin(ctx, true);
+			if (any_order) check(ctx, ssv_samdec_any_order(ctx, 1));
 			return;
 		}
 		if (ssvh_bam_open(path.c_str(), &bam) != 0) die(open_error);
@@ -1046,6 +1047,7 @@ struct GetclipOptions {
 	int min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
 	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false, prefix_given = false;
 	bool mark_dups = false; // `run -M`, `somatic -K -M` (no option of getclip's own): duplicate read pairs are marked where the records are retained
+	bool sort_input = false; // `run -u` (no option of getclip's own): the input is in any order; its retained records are coordinate sorted on the GPU before any pass
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1114,11 +1116,13 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_unfinished.push_back(g->path);
 	}
-	if (o.mark_dups && !probe_only) { // -M: an input that is not coordinate sorted is refused where the stage meets it, and the run leaves no file behind
+	const bool sort_input = o.sort_input && run && run->collect && !probe_only;
+	if ((o.mark_dups && !probe_only) || sort_input) { // -M: an input that is not coordinate sorted is refused where the stage meets it, and the run leaves no file behind; -u: so does a sample that does not fit twice
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_refused.push_back(g->path);
 	}
 
+	src.any_order = sort_input;
 	src.open(o.bamfile, [&] { return acquire_ctx(o.device, run); }, o.device_inflate, "[main_samview] fail to open file for reading.", run);
 	ssv_ctx *ctx = src.ctx;
 	ssv_clip_params p = clip_params(o);
@@ -1219,6 +1223,9 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	// batch's up to its own trailing run.  The decoder's contig changes are relative to the decoded batch: they move by the records held back, and those that
 	// fall into the new hold-back wait for the batch that brings their record (dup_pending: relative to the hold-back's first record).
 	const bool mark_dups = o.mark_dups && run && run->collect;
+	vector<ssv_batch_t> unsorted; // -u: the retained batches in input order
+	static const char *const kSortNoMemory = "seeksv run: -u keeps the decoded sample in GPU memory twice while it is sorted (2 x 80 bytes a record, plus 24 bytes a record of keys): out of memory; "
+	                                         "sort the input with `samtools sort` and run without -u";
 	int64_t dup_held = 0;
 	vector<pair<int64_t, int32_t>> dup_pending;
 	if (mark_dups && pt.on) ssv_prof_enable(ctx, 1); // (SSV_TIMING: the stage's own kernel time, below)
@@ -1267,10 +1274,20 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	src.pump(mark_dups ? 1 : 0, [&](const ssv_batch_t &b) {
 		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
 		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
+		if (sort_input) { pt.lap("host_side_channel"); return; } // (-u: the contig changes are those of the sorted records, below)
 		changes_of.emplace_back();
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
 		pt.lap("host_side_channel");
 	}, [&](const ssv_batch_t &decoded) {
+		if (sort_input) { // -u: the batch is only kept; every pass waits for the sort
+			ssv_batch_t b;
+			const int rc = ssv_batch_retain(ctx, &decoded, &b);
+			if (rc == SSV_E_NOMEM) die(kSortNoMemory);
+			check(ctx, rc);
+			unsorted.push_back(b);
+			pt.lap("gpu_retain(wait h2d+kernels)");
+			return;
+		}
 		if (mark_dups) {
 			dup_step(&decoded, changes_of.front());
 			changes_of.pop_front();
@@ -1304,6 +1321,44 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			}
 			cerr << "; hold-back at most " << ds.held_max << " records, " << ds.set_entries << " digests in the set)" << endl;
 			ssv_prof_enable(ctx, 0);
+		}
+	}
+	if (sort_input) { // -u: one sort of everything that was kept; then the passes see the batches as they would have come from a sorted file
+		if (pt.on) { ssv_prof_enable(ctx, 1); ssv_prof_reset(ctx); }
+		const size_t n_unsorted = unsorted.size();
+		auto resident = [](const ssv_batch_t *b, int64_t n) { // hot columns, cigar_ends, lines, operations, bases + qualities
+			int64_t bytes = 0;
+			for (int64_t k = 0; k < n; ++k) bytes += b[k].n * (4 + 4 + 2 + 1 + 64) + b[k].n_cigar_total * 4 + b[k].seqqual_bytes;
+			return bytes;
+		};
+		const int64_t bytes_in = resident(unsorted.data(), (int64_t)n_unsorted);
+		ssv_sorted sorted;
+		const int rc = ssv_batch_sort(ctx, unsorted.data(), (int64_t)n_unsorted, ssvh_bam_n_targets(bam), 0, &sorted);
+		if (rc == SSV_E_NOMEM) die(kSortNoMemory);
+		check(ctx, rc);
+		unsorted.clear(); // (the call's: released, or handed back as the result's batches)
+		if (sorted.already_sorted) cerr << "[seeksv] -u: " << sorted.n_records << " records in " << sorted.n_batches << " batches already in coordinate order" << endl;
+		else cerr << "[seeksv] -u: sorted " << sorted.n_records << " records from " << n_unsorted << " into " << sorted.n_batches << " batches" << endl;
+		pt.lap("gpu_coordinate_sort");
+		if (pt.on) {
+			cerr << "[timing] (-u kernel time:";
+			for (const char *g : {"sort_keys", "sort_radix", "sort_gather"}) {
+				double ms = 0; int64_t launches = 0;
+				ssv_prof_get(ctx, g, &ms, &launches, nullptr);
+				cerr << ' ' << g << ' ' << ms << " ms in " << launches << " launches" << (g[5] == 'g' ? ";" : ",");
+			}
+			const int64_t bytes_out = sorted.already_sorted ? 0 : resident(sorted.batches, sorted.n_batches), bytes_keys = sorted.already_sorted ? 0 : 24 * sorted.n_records;
+			cerr << " resident at the peak: " << bytes_in << " + " << bytes_out << " bytes of records, " << bytes_keys << " bytes of keys and indices)" << endl;
+			ssv_prof_enable(ctx, 0);
+		}
+		for (int64_t k = 0; k < sorted.n_batches; ++k) {
+			const ssv_batch_t &b = sorted.batches[k];
+			if (b.n == 0) { ssv_batch_t gone = b; check(ctx, ssv_batch_release(ctx, &gone)); continue; }
+			vector<pair<int64_t, int32_t>> changes;
+			for (int64_t j = sorted.change_first[k]; j < sorted.change_first[k + 1]; ++j) changes.emplace_back((int64_t)sorted.change_index[j], sorted.change_tid[j]);
+			run->batches.push_back(b);
+			scan_batch(b, changes);
+			pt.lap("gpu_scan(wait kernels)");
 		}
 	}
 	pass_flushes.push_back(scan_last_tid);
@@ -3015,6 +3070,12 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               of the leftmost read; the highest sum of base qualities >= 15 stays, the earliest of equals; the mate follows its read.  Aligned\n"
 	     << "                               positions, not unclipped 5' ends (Picard's): copies clipped differently are not found; single reads and pairs with an unmapped\n"
 	     << "                               end are never marked; read groups / libraries are not told apart.  Not with -N above 1, not on SAM text\n"
+	     << "         -u                    the input is in ANY order (an aligner's output through a pipe, read-name order): its records are coordinate sorted on the GPU, where\n"
+	     << "                               the run keeps them, before any pass reads them - no `samtools sort`, no file.  A stable sort by (contig, position), unplaced\n"
+	     << "                               records last, records at one place in input order (libbam 0.1.x's comparison; newer samtools also orders by strand: no external\n"
+	     << "                               sorter was matched).  Every file and stdout are what `seeksv run` writes for the same records in that order, except\n"
+	     << "                               prefix.unmapped_[12].fq.gz, which hold the same pairs in input order.  The sample is resident twice while it is sorted\n"
+	     << "                               (2 x 80 bytes a record).  Not with -N above 1, -P or -M, and not inside -c or -v\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
 	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
 	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
@@ -3027,11 +3088,12 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
-	bool split = false, ranks_given = false, mark_dups = false;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:M")) >= 0) {
+	bool split = false, ranks_given = false, mark_dups = false, unsorted = false;
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:Mu")) >= 0) {
 		switch (c) {
 		case 'P': split = true; break;
 		case 'M': mark_dups = true; break;
+		case 'u': unsorted = true; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
@@ -3047,6 +3109,11 @@ static int cmd_run(int argc, char **argv)
 	const string bam = argv[optind], fasta = argv[optind + 1], prefix = argv[optind + 2];
 	// The three steps' options, each through the step's own parser: a usage error or a value out of range ends the run here with the step's usage text, before
 	// the GPU context is asked for and before any file exists.  The GPU of realign is run's own -G.
+	// -u is run's own: refused inside -c / -v with its reason, not with the steps' usage texts
+	for (const string *words : {&clip_opts, &sv_opts}) {
+		std::istringstream in(*words);
+		for (string w; in >> w;) if (w == "-u") die("seeksv run: -u sorts the records that this run keeps, once, for all its steps; -u inside -c or -v is not supported");
+	}
 	const RealignOptions aln = parse_words("realign", aln_opts, parse_realign);
 	if (aln.gpu_given) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
 	GetclipOptions clip = parse_words("getclip", clip_opts, parse_getclip);
@@ -3060,6 +3127,10 @@ static int cmd_run(int argc, char **argv)
 	// -M: one stream of records in file order, decoded with every record's qualities by the BAM decoder
 	if (mark_dups && ranked) die("seeksv run: -M marks duplicates in one stream of records in file order; -N above 1 is not supported with it");
 	if (mark_dups && !is_bam_name(bam)) die("seeksv run: -M reads a BAM; SAM text is not supported with it");
+	// -u: one stream of records kept on one GPU and sorted there
+	if (unsorted && ranked) die("seeksv run: -u sorts the records that one GPU keeps; -N above 1 is not supported with it");
+	if (unsorted && split) die("seeksv run: -u hands the unmapped pairs over in input order, which is not the order -P's pass takes them in from a sorted file; -P is not supported with it");
+	if (unsorted && mark_dups) die("seeksv run: -u does not carry the read names through the sort, which -M's digests need; -M is not supported with it");
 	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
 	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
 		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
@@ -3067,7 +3138,7 @@ static int cmd_run(int argc, char **argv)
 	if (clip.ranks_given || clip.devices_given) die("seeksv run: -N or -G inside -c is not supported; the ranks of a run and their GPUs are run's own -N and -G");
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
-	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups;
+	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted;
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
 
