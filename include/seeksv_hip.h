@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_batch_sort, ssv_sorted, ssv_samdec_any_order (`seeksv run -u`: an original in any order, coordinate sorted while it is retained).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_pairdup_retain / ssv_pairdup_rows / ssv_pairdup_mark, ssv_pairdup_stats (`seeksv run -D`: duplicate pairs by unclipped 5' ends, any record order).
+                             v9 (additive, same version): ssv_batch_sort, ssv_sorted, ssv_samdec_any_order (`seeksv run -u`: an original in any order, coordinate sorted while it is retained).
                              v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
                              v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
                              v9 (additive, same version): ssv_realign_split_batch (`seeksv run -P`: the split alignments as a device batch for ssv_rt_scan).
@@ -876,6 +877,55 @@ typedef struct {
 	const int32_t *change_tid;     /* ... and its contig */
 } ssv_sorted;
 int ssv_batch_sort(ssv_ctx *ctx, ssv_batch_t *in, int64_t n_in, int32_t n_targets, int64_t max_out_records, ssv_sorted *out);
+
+/* ---- duplicate read pairs by the unclipped 5' ends of both reads, in any record order (v9, additive; `seeksv run -D`, `seeksv somatic -K -D`) ----
+ * A second rule beside ssv_dup_retain's, for what that one cannot see: copies of one fragment that the aligner clipped differently, and input that is not
+ * coordinate sorted.  Mates are joined by read name, so nothing here depends on record order.  This is Picard's comparison in outline; the rule is this
+ * library's own, no external duplicate marker was run or matched.
+ * THE RULE.  The records of all batches are one sequence in input order: batch order first, then record order.  A record's index in it is g (< 2^32, else
+ * SSV_E_RANGE).
+ *   takes part  flag & 0x1 set, none of 0x4 | 0x8 | 0x100 | 0x800 | 0x400 set, tid >= 0, mtid >= 0 and n_cigar > 0 (a record that arrives with 0x400 keeps it
+ *               and takes no part); every other record is never touched
+ *   end u       64-bit signed, may be negative.  Forward (!(flag & 0x10)): pos minus the lengths of the leading run of S / H operations.  Reverse: pos +
+ *               reference span (M D N = X) - 1 + the lengths of the trailing run of S / H operations
+ *   name hash   64-bit FNV-1a (offset 1469598103934665603, prime 1099511628211) over the read name's bytes without the NUL; SSV_DUP_DIGEST_BITS=k in the
+ *               environment keeps the low k bits (tests: names that collide follow the same rule)
+ *   mates       the records that take part and have equal name hash form a name group.  A name group is a PAIR iff it has exactly two records, exactly one of
+ *               them has 0x40, each record's (mtid, mpos) equals the other's (tid, pos), and each record's 0x20 agrees with the other's 0x10.  The records
+ *               of every other name group are left untouched and counted as `unpaired`
+ *   key         a = the record with the smaller (tid, u, reverse), on a tie the one with 0x40; b = the other.  key = (tid_a, u_a, rev_a, tid_b, u_b, rev_b),
+ *               compared exactly (the pairs are ordered by the key itself, not by a hash of it)
+ *   score       the sum over both records of the quality bytes >= 15 (32 bits); a record with l_qseq == 0 or first quality byte 0xff adds 0
+ *   keeper      the group's (pairs of equal key) highest score; among equal scores the pair whose smaller g is smallest.  Both records of every other pair
+ *               of the group get flag |= 0x400
+ * When no two pairs of a group have equal scores, the set of marked records does not depend on the input order.
+ * Limits: libraries (RG / LB) are not told apart; which mate is first of pair is not part of the key; single reads and pairs with an unmapped end are never
+ * marked; a name that occurs on more than two primary records is left alone.
+ *
+ * ssv_pairdup_retain takes the place of ssv_batch_retain for a batch decoded with keep_all_seq, and its names (ssv_bamdec_names or ssv_samdec_names; as
+ * ssv_rt_scan takes them).  *out has the form of ssv_dup_retain's output: bases + qualities only for records whose first or last operation is S (the others
+ * get SSV_NO_SEQ), cigar_off / seq_off those of *out's own arrays, tid_runs as the decoder gave them; given back with ssv_batch_release.  Behind the other
+ * parts of the batch's memory sits one 24-byte row per record - { uint64 name_hash; int64 u; uint32 score; uint32 kind } - kind 1: the record takes part,
+ * 0: it does not and the row is all zero.  ssv_pairdup_rows hands out where they lie (device memory; tests).  Errors leave everything as it was: NULL
+ * arguments, a host batch, a record that takes part without its qualities: SSV_E_ARG; no memory: SSV_E_NOMEM.
+ *
+ * ssv_pairdup_mark works over all retained batches at once, in place: the flags of the rule are written into the record lines of batches[0 .. n).  Batches
+ * that are not ssv_pairdup_retain's, one given twice, or batches a call has marked already: SSV_E_ARG; no memory: SSV_E_NOMEM; on any failure nothing is
+ * changed.  Afterwards the rows are dead and the batches are ordinary retained batches (ssv_batch_sort takes them and carries their flags like every
+ * other field).  Memory: 8 bytes a record, 32 bytes a record that takes part and 32 bytes a pair of temporaries, given back on return together with what the retain calls kept between them (20 bytes a record of the largest batch).  No pass is
+ * quadratic in the size of a group.  Synchronises the stream.  Timed as pairdup_ends (retain), pairdup_join (compaction, name sort, join, pairs),
+ * pairdup_mark (key sorts, pick and scatter). */
+typedef struct {
+	int64_t records;      /* records in all batches */
+	int64_t taking_part;  /* of them: records that take part */
+	int64_t unpaired;     /* of those: records whose name group is no pair */
+	int64_t pairs;
+	int64_t groups_many;  /* groups of two or more pairs */
+	int64_t pairs_marked; /* pairs whose two records got 0x400 */
+} ssv_pairdup_stats;
+int ssv_pairdup_retain(ssv_ctx *ctx, const ssv_batch_t *device_batch, const ssv_names_t *names, ssv_batch_t *out);
+int ssv_pairdup_rows(ssv_ctx *ctx, const ssv_batch_t *batch, const void **dev_rows);
+int ssv_pairdup_mark(ssv_ctx *ctx, ssv_batch_t *batches, int64_t n, ssv_pairdup_stats *stats);
 
 #ifdef __cplusplus
 }

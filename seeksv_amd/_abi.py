@@ -346,6 +346,13 @@ class DupStats(C.Structure):  # ssv_dup_stats
     _fields_ = [(k, C.c_int64) for k in ("records", "taking_part", "groups", "heads_marked", "tails_marked", "set_entries", "held_max")]
 
 
+class PairdupStats(C.Structure):  # ssv_pairdup_stats
+    _fields_ = [(k, C.c_int64) for k in ("records", "taking_part", "unpaired", "pairs", "groups_many", "pairs_marked")]
+
+
+PAIRDUP_ROW_DTYPE = np.dtype([("name_hash", "<u8"), ("u", "<i8"), ("score", "<u4"), ("kind", "<u4")])  # a row of ssv_pairdup_retain
+
+
 class Sorted(C.Structure):  # ssv_sorted
     _fields_ = [("n_records", C.c_int64), ("n_batches", C.c_int64), ("already_sorted", C.c_int32), ("pad", C.c_int32), ("batches", C.POINTER(Batch)),
                 ("change_first", C.POINTER(C.c_int64)), ("change_index", C.POINTER(C.c_uint32)), ("change_tid", C.POINTER(C.c_int32))]
@@ -435,5 +442,9 @@ def hip_lib():
         lib.ssv_batch_lines_to_host.argtypes = [V, C.POINTER(Batch), V]
         lib.ssv_batch_sort.argtypes = [V, C.POINTER(Batch), C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sorted)]
         lib.ssv_samdec_any_order.argtypes = [V, C.c_int]
+        lib.ssv_pairdup_retain.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(Batch)]
+        lib.ssv_pairdup_rows.argtypes = [V, C.POINTER(Batch), C.POINTER(V)]
+        lib.ssv_pairdup_rows_to_host.argtypes = [V, C.POINTER(Batch), V]
+        lib.ssv_pairdup_mark.argtypes = [V, C.POINTER(Batch), C.c_int64, C.POINTER(PairdupStats)]
         lib._typed = True
     return lib

@@ -324,6 +324,32 @@ class Context:
             changes.append([(int(out.change_index[j]), int(out.change_tid[j])) for j in range(lo, hi)])
         return dict(n_records=int(out.n_records), already_sorted=bool(out.already_sorted), batches=res, changes=changes)
 
+    # ---- duplicate read pairs by the unclipped 5' ends of both reads, in any record order (ssv_pairdup_*: `seeksv run -D`) ----
+    def pairdup_retain(self, batch, names):
+        """ssv_pairdup_retain in the place of batch_retain: the decoder's device batch (with every record's qualities) and its names (bamdec_names() /
+        samdec_names(), or a list) -> Batch: a retained batch in dup_retain's form that carries one row per record for pairdup_mark, to be given back
+        with batch_release"""
+        n, keep_names = self._as_names(names)
+        out = _abi.Batch()
+        self._check(self._lib.ssv_pairdup_retain(self._h, C.byref(batch), C.byref(n), C.byref(out)), "ssv_pairdup_retain")
+        return out
+
+    def pairdup_rows(self, batch):
+        """the rows of a batch of pairdup_retain that no pairdup_mark has used yet -> numpy array of _abi.PAIRDUP_ROW_DTYPE (tests)"""
+        dev = C.c_void_p()
+        self._check(self._lib.ssv_pairdup_rows(self._h, C.byref(batch), C.byref(dev)), "ssv_pairdup_rows")
+        rows = np.zeros(int(batch.n), dtype=_abi.PAIRDUP_ROW_DTYPE)
+        self._check(self._lib.ssv_pairdup_rows_to_host(self._h, C.byref(batch), rows.ctypes.data if len(rows) else None), "ssv_pairdup_rows_to_host")
+        return rows
+
+    def pairdup_mark(self, batches):
+        """ssv_pairdup_mark: the rule's 0x400 into the record lines of all the batches of pairdup_retain (one sequence in this order), in place -> dict of
+        the counts (ssv_pairdup_stats).  The batches stay the caller's: ordinary retained batches afterwards."""
+        arr = (_abi.Batch * max(1, len(batches)))(*batches)
+        st = _abi.PairdupStats()
+        self._check(self._lib.ssv_pairdup_mark(self._h, arr, len(batches), C.byref(st)), "ssv_pairdup_mark")
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def samdec_any_order(self, on=True):
         """ssv_samdec_any_order, after samdec_begin: text in any record order - a chunk with more contig changes than the list holds is decoded all the same,
         without its contig-change list"""

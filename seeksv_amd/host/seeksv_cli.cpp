@@ -186,6 +186,9 @@ static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv]
 	     << "         -c <string>           with -K: options of the clip pass, as `getclip` takes them (-t, -q, -s; not -N, -G, -o)\n"
 	     << "         -M                    with -K: mark duplicate read pairs of the normal (flag 0x400) on the GPU where its records are retained, before any pass reads a\n"
 	     << "                               flag: the output of `somatic -K` on the same BAM with those flags set.  The rule and its limits: `seeksv run`'s -M\n"
+	     << "         -D                    with -K: mark duplicate pairs of the normal by the unclipped 5' ends of both reads, mates joined by read name, once all its records\n"
+	     << "                               are retained: the output of `somatic -K` on the same BAM with those flags set.  The rule and its limits: `seeksv run`'s -D.\n"
+	     << "                               Not with -M\n"
 	     << "         -t <double>           Threshold of match rate while comparing two soft-clipped reads [0.9]\n"
 	     << "         -q <int>              Minimum mapping quality of discordant read pair [20]\n"
 	     << "         -l <int>              Maximum search length to find microhomology [30]\n"
@@ -500,6 +503,7 @@ struct SamTextDecoder {
 	seeksv::SamTextReader rd;
 	ssv_ctx *ctx = nullptr;
 	bool ended = false, over = false, sorted = false;
+	bool keep_all_seq = false; // (run -D: every record's bases + qualities, set before begin())
 	ssv_names_t names{};
 	void open(const string &path, const char *open_error)
 	{
@@ -520,7 +524,7 @@ struct SamTextDecoder {
 		memset(&sp, 0, sizeof(sp));
 		sp.n_targets = (int32_t)cnames.size(); sp.target_names = cnames.data(); sp.first_line = rd.first_record_line();
 		check(ctx, ssv_samdec_begin(ctx, &sp));
-		if (sorted) check(ctx, ssv_samdec_sorted(ctx, 0));
+		if (sorted) check(ctx, ssv_samdec_sorted(ctx, keep_all_seq ? 1 : 0));
 		const char *e = getenv("SSV_SAM_CHUNK_KB");
 		const size_t chunk = e && atoll(e) > 0 ? (size_t)atoll(e) << 10 : (size_t)256 << 20;
 		rd.start(chunk, sam_stage_alloc, sam_stage_free);
@@ -1047,6 +1051,7 @@ struct GetclipOptions {
 	int min_mapQ = 1, device = 0, n_ranks = 1, halo_bp = 65536;
 	bool save_low_quality = false, device_inflate = device_inflate_default(), verify_crc = false, ranks_given = false, devices_given = false, prefix_given = false;
 	bool mark_dups = false; // `run -M`, `somatic -K -M` (no option of getclip's own): duplicate read pairs are marked where the records are retained
+	bool pair_dups = false; // `run -D`, `somatic -K -D` (no option of getclip's own): duplicate pairs by the unclipped 5' ends of both reads, marked once all records are retained
 	bool sort_input = false; // `run -u` (no option of getclip's own): the input is in any order; its retained records are coordinate sorted on the GPU before any pass
 	vector<int> devices;
 	string prefix = "output", bamfile;
@@ -1117,12 +1122,14 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_unfinished.push_back(g->path);
 	}
 	const bool sort_input = o.sort_input && run && run->collect && !probe_only;
-	if ((o.mark_dups && !probe_only) || sort_input) { // -M: an input that is not coordinate sorted is refused where the stage meets it, and the run leaves no file behind; -u: so does a sample that does not fit twice
+	if ((o.mark_dups && !probe_only) || sort_input || (o.pair_dups && run && run->collect && !probe_only)) { // -D: so does a sample whose rows and keys do not fit; -M: an input that is not coordinate sorted is refused where the stage meets it, and the run leaves no file behind; -u: so does a sample that does not fit twice
 		std::unique_lock<std::shared_mutex> lk(g_outputs_mu);
 		for (GzOut *g : {&out.soft, &out.fq, &out.unmapped1, &out.unmapped2}) g_outputs_refused.push_back(g->path);
 	}
 
+	const bool pair_dups = o.pair_dups && run && run->collect;
 	src.any_order = sort_input;
+	if (text_input && pair_dups) src.text->keep_all_seq = true;
 	src.open(o.bamfile, [&] { return acquire_ctx(o.device, run); }, o.device_inflate, "[main_samview] fail to open file for reading.", run);
 	ssv_ctx *ctx = src.ctx;
 	ssv_clip_params p = clip_params(o);
@@ -1228,7 +1235,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	                                         "sort the input with `samtools sort` and run without -u";
 	int64_t dup_held = 0;
 	vector<pair<int64_t, int32_t>> dup_pending;
-	if (mark_dups && pt.on) ssv_prof_enable(ctx, 1); // (SSV_TIMING: the stage's own kernel time, below)
+	if ((mark_dups || (o.pair_dups && run && run->collect)) && pt.on) ssv_prof_enable(ctx, 1); // (SSV_TIMING: the stage's own kernel time, below)
 	if (mark_dups) check(ctx, ssv_dup_begin(ctx));
 	// the records of a retained (or decoded) batch through the clip scan, the pass ending in front of every contig that comes back
 	auto scan_batch = [&](const ssv_batch_t &b, const vector<pair<int64_t, int32_t>> &changes) {
@@ -1271,14 +1278,41 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		run->batches.push_back(b);
 		scan_batch(b, now);
 	};
-	src.pump(mark_dups ? 1 : 0, [&](const ssv_batch_t &b) {
+	// -D: the pump only retains (ssv_pairdup_retain: every batch with one row per record); one ssv_pairdup_mark behind the last chunk works on all of them, then
+	// -u's sort where it was asked for, and then every batch goes through the clip scan - with the contig changes the decoder gave for it (pd_changes)
+	vector<ssv_batch_t> pd_batches;
+	vector<vector<pair<int64_t, int32_t>>> pd_changes;
+	static const char *const kPairNoMemory = "seeksv run: -D keeps the decoded sample in GPU memory with 24 bytes a record of rows, and sorts 32 bytes a record that takes part: out of memory; "
+	                                         "mark the duplicates beforehand and run without -D";
+	static const char *const kProbeNoMemory = "seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead";
+	src.pump(mark_dups || pair_dups ? 1 : 0, [&](const ssv_batch_t &b) {
 		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
 		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
 		if (sort_input) { pt.lap("host_side_channel"); return; } // (-u: the contig changes are those of the sorted records, below)
+		if (pair_dups) { // (kept until the scans, behind the mark)
+			pd_changes.emplace_back();
+			src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { pd_changes.back().emplace_back(i, tid); });
+			pt.lap("host_side_channel");
+			return;
+		}
 		changes_of.emplace_back();
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
 		pt.lap("host_side_channel");
 	}, [&](const ssv_batch_t &decoded) {
+		if (pair_dups) { // -D: the batch is only kept, with its rows; every pass waits for the mark
+			ssv_names_t names;
+			memset(&names, 0, sizeof(names));
+			names.mem = SSV_MEM_DEVICE;
+			if (text_input) names = src.text->names;
+			else check(ctx, ssv_bamdec_names(ctx, &names));
+			ssv_batch_t b;
+			const int rc = ssv_pairdup_retain(ctx, &decoded, &names, &b);
+			if (rc == SSV_E_NOMEM) die(probe_only ? kProbeNoMemory : kPairNoMemory); // (with -u too: what did not fit is -D's retention with rows)
+			check(ctx, rc);
+			(sort_input ? unsorted : pd_batches).push_back(b);
+			pt.lap("gpu_retain+rows(wait h2d+kernels)");
+			return;
+		}
 		if (sort_input) { // -u: the batch is only kept; every pass waits for the sort
 			ssv_batch_t b;
 			const int rc = ssv_batch_retain(ctx, &decoded, &b);
@@ -1323,6 +1357,37 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			ssv_prof_enable(ctx, 0);
 		}
 	}
+	if (pair_dups) { // -D: one mark over everything that was kept, in input order
+		vector<ssv_batch_t> &kept = sort_input ? unsorted : pd_batches;
+		ssv_pairdup_stats ps;
+		const int rc = ssv_pairdup_mark(ctx, kept.data(), (int64_t)kept.size(), &ps);
+		if (rc == SSV_E_NOMEM) die(probe_only ? kProbeNoMemory : kPairNoMemory);
+		check(ctx, rc);
+		cerr << "[seeksv] -D: marked " << ps.pairs_marked << " duplicate pairs (" << ps.groups_many << " groups of two or more) of " << ps.pairs << " pairs; " << ps.unpaired << " of " << ps.taking_part
+		     << " records that take part have no mate by name, " << ps.records << " records" << endl;
+		pt.lap("gpu_pair_duplicates");
+		if (pt.on) {
+			cerr << "[timing] (-D kernel time:";
+			const char *const groups[3] = {"pairdup_ends", "pairdup_join", "pairdup_mark"};
+			for (int k = 0; k < 3; ++k) {
+				double ms = 0; int64_t launches = 0;
+				ssv_prof_get(ctx, groups[k], &ms, &launches, nullptr);
+				cerr << ' ' << groups[k] << ' ' << ms << " ms in " << launches << " launches" << (k == 2 ? ";" : ",");
+			}
+			cerr << " resident at the peak beside the records: " << 24 * ps.records << " bytes of rows, " << 8 * ps.records + 32 * ps.taking_part + 32 * ps.pairs << " bytes of keys and indices)" << endl;
+			ssv_prof_enable(ctx, 0);
+		}
+		if (!sort_input) {
+			for (size_t k = 0; k < pd_batches.size(); ++k) {
+				ssv_batch_t b = pd_batches[k];
+				if (b.n == 0) { check(ctx, ssv_batch_release(ctx, &b)); continue; }
+				run->batches.push_back(b);
+				scan_batch(b, pd_changes[k]);
+				pt.lap("gpu_scan(wait kernels)");
+			}
+			pd_batches.clear();
+		}
+	}
 	if (sort_input) { // -u: one sort of everything that was kept; then the passes see the batches as they would have come from a sorted file
 		if (pt.on) { ssv_prof_enable(ctx, 1); ssv_prof_reset(ctx); }
 		const size_t n_unsorted = unsorted.size();
@@ -1331,7 +1396,8 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			for (int64_t k = 0; k < n; ++k) bytes += b[k].n * (4 + 4 + 2 + 1 + 64) + b[k].n_cigar_total * 4 + b[k].seqqual_bytes;
 			return bytes;
 		};
-		const int64_t bytes_in = resident(unsorted.data(), (int64_t)n_unsorted);
+		int64_t bytes_in = resident(unsorted.data(), (int64_t)n_unsorted);
+		if (pair_dups) for (const ssv_batch_t &b : unsorted) bytes_in += 24 * b.n; // (-D: the inputs still carry their rows, dead since the mark)
 		ssv_sorted sorted;
 		const int rc = ssv_batch_sort(ctx, unsorted.data(), (int64_t)n_unsorted, ssvh_bam_n_targets(bam), 0, &sorted);
 		if (rc == SSV_E_NOMEM) die(kSortNoMemory);
@@ -2155,6 +2221,7 @@ struct SomaticOptions {
 	vector<int> devices;
 	string normal_bam_file, clipped_file, tumor_file, somatic_file;
 	bool mark_dups = false; // -M (with -K): duplicate read pairs of the normal are marked where its records are retained
+	bool pair_dups = false; // -D (with -K): ... by the unclipped 5' ends of both reads, once all its records are retained
 	bool from_bam = false; // -K: no clip.gz - the normal's clusters come from its BAM, and the look-ups run on the GPU where the clusters lie
 	GetclipOptions clip;   // -K: the clip pass's options (-c: getclip's -t / -q / -s; the defaults are getclip's)
 };
@@ -2166,7 +2233,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	optind = 0;
 	string clip_opts;
 	bool clip_opts_given = false;
-	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:M")) >= 0) {
+	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:MD")) >= 0) {
 		switch (c) {
 		case 't': o.min_map_rate = atof(optarg); break;
 		case 'q': o.min_mapQ = atoi(optarg); break;
@@ -2180,11 +2247,14 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 		case 'J': o.dump_lookups = optarg; break; // test hook: the look-ups only (no insert-size or tally pass; without -K no BAM pass and no GPU), one line per output row
 		case 'K': o.from_bam = true; break;
 		case 'M': o.mark_dups = true; break;
+		case 'D': o.pair_dups = true; break;
 		case 'c': clip_opts = optarg; clip_opts_given = true; break;
 		}
 	}
 	if (o.n_ranks < 1) usage_somatic();
 	if (o.mark_dups && !o.from_bam) die("seeksv somatic: -M marks duplicates where the clip pass of -K retains the normal's records; without -K there is no such pass");
+	if (o.pair_dups && !o.from_bam) die("seeksv somatic: -D marks duplicate pairs once the clip pass of -K has retained the normal's records; without -K there is no such pass");
+	if (o.pair_dups && o.mark_dups) die("seeksv somatic: -D and -M are two rules for the one duplicate flag; -M is not supported with -D");
 	if (clip_opts_given && !o.from_bam) die("seeksv somatic: -c hands getclip's options to the clip pass of -K; without -K there is no such pass");
 	if (argc != optind + (o.from_bam ? 3 : 4)) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
 	else if (o.offset >= 90 || o.offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
@@ -2199,7 +2269,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	if (!is_bam_name(o.normal_bam_file)) die("seeksv somatic -K: the normal must be a BAM (a name ending in .bam); SAM text is not supported");
 	o.clip.bamfile = o.normal_bam_file; o.clip.device = o.device; o.clip.devices = vector<int>(1, o.device); o.clip.n_ranks = 1;
 	o.clip.device_inflate = true; // (as `seeksv run`: decoded on the GPU, where the records stay)
-	o.clip.mark_dups = o.mark_dups;
+	o.clip.mark_dups = o.mark_dups; o.clip.pair_dups = o.pair_dups;
 	if (o.verify_crc) o.clip.verify_crc = true;
 	return o;
 }
@@ -3070,6 +3140,13 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               of the leftmost read; the highest sum of base qualities >= 15 stays, the earliest of equals; the mate follows its read.  Aligned\n"
 	     << "                               positions, not unclipped 5' ends (Picard's): copies clipped differently are not found; single reads and pairs with an unmapped\n"
 	     << "                               end are never marked; read groups / libraries are not told apart.  Not with -N above 1, not on SAM text\n"
+	     << "         -D                    mark duplicate pairs (flag 0x400) by the unclipped 5' ends of both reads, in any record order: mates are joined by read name, a\n"
+	     << "                               pair's key is (contig, unclipped 5' end, strand) of both reads, the highest sum of base qualities >= 15 over BOTH reads stays, of\n"
+	     << "                               equals the pair that comes first in the input.  Finds copies that the aligner clipped differently, which -M does not.  Takes a BAM\n"
+	     << "                               or SAM text, with or without -u.  This program's own rule, Picard's comparison in outline; no external marker was matched.\n"
+	     << "                               Libraries are not told apart; which mate is first of pair is not part of the key; single reads and pairs with an unmapped end\n"
+	     << "                               are never marked; a name on more than two primary records is left alone.  The clip scan waits for the whole decode (as with -u).\n"
+	     << "                               Not with -M, -P or -N above 1\n"
 	     << "         -u                    the input is in ANY order (an aligner's output through a pipe, read-name order): its records are coordinate sorted on the GPU, where\n"
 	     << "                               the run keeps them, before any pass reads them - no `samtools sort`, no file.  A stable sort by (contig, position), unplaced\n"
 	     << "                               records last, records at one place in input order (libbam 0.1.x's comparison; newer samtools also orders by strand: no external\n"
@@ -3088,12 +3165,13 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
-	bool split = false, ranks_given = false, mark_dups = false, unsorted = false;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:Mu")) >= 0) {
+	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false;
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuD")) >= 0) {
 		switch (c) {
 		case 'P': split = true; break;
 		case 'M': mark_dups = true; break;
 		case 'u': unsorted = true; break;
+		case 'D': pair_dups = true; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
@@ -3131,6 +3209,10 @@ static int cmd_run(int argc, char **argv)
 	if (unsorted && ranked) die("seeksv run: -u sorts the records that one GPU keeps; -N above 1 is not supported with it");
 	if (unsorted && split) die("seeksv run: -u hands the unmapped pairs over in input order, which is not the order -P's pass takes them in from a sorted file; -P is not supported with it");
 	if (unsorted && mark_dups) die("seeksv run: -u does not carry the read names through the sort, which -M's digests need; -M is not supported with it");
+	// -D: one mark over the records that one GPU keeps, behind the whole decode
+	if (pair_dups && mark_dups) die("seeksv run: -D and -M are two rules for the one duplicate flag; -M is not supported with -D");
+	if (pair_dups && ranked) die("seeksv run: -D joins mates by name among the records that one GPU keeps; -N above 1 is not supported with it");
+	if (pair_dups && split) die("seeksv run: -D defers every pass behind the whole decode, -P's pass among them; -P is not supported with it");
 	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
 	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
 		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
@@ -3138,7 +3220,7 @@ static int cmd_run(int argc, char **argv)
 	if (clip.ranks_given || clip.devices_given) die("seeksv run: -N or -G inside -c is not supported; the ranks of a run and their GPUs are run's own -N and -G");
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
-	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted;
+	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted; clip.pair_dups = pair_dups;
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
 
