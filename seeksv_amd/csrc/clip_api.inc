@@ -153,12 +153,7 @@ int ssv_clip_scan_range(ssv_ctx *c, const ssv_batch_t *b, int64_t rec_begin, int
 	if (!d.cigar) { c->err = "batch without cigar"; return SSV_E_ARG; }
 	d.n = rec_end; // what lies behind the range is not looked at (nor does it move the contig-switch state)
 	if (rec_end == 0) return SSV_OK;
-	if (!d.ends) { // the batcher did not fill the cigar_ends column: built from the lines
-		CHECK(ensure(c, c->ends_buf, (size_t)d.n + 16));
-		k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
-		HIPCHECK(c, hipGetLastError());
-		d.ends = P<uint8_t>(c->ends_buf);
-	}
+	CHECK(staged_ends(c, d)); // (the batcher did not fill the cigar_ends column: built from the lines)
 	const bool persistent = b->mem == (SSV_MEM_DEVICE | SSV_MEM_PERSISTENT);
 	const int64_t ntiles = (d.n + CC_TILE - 1) / CC_TILE;
 	const unsigned grid = scan_blocks(ntiles, "SSV_CLIP_SCAN_BLOCKS", 256 * 6);

@@ -17,8 +17,8 @@ struct ssv_dup_state {
 	} hold[2];
 	int cur = 0;
 	// a call's temporaries
-	DBuf sel, at, cand, wave_break, rs, rat, rfirst, keys, rstart, isdup, keeper, fresh, mark, cig_n, cig_at, seq_b, seq_at, name_b, name_at, wave_cnt, wave_part, tmp, small, hnames, hoff;
-	HBuf h_small;
+	DBuf sel, at, cand, wave_break, rs, rat, rfirst, keys, rstart, isdup, keeper, fresh, mark, cig_n, cig_at, seq_b, seq_at, name_b, name_at, wave_cnt, wave_part, tmp, hnames, hoff;
+	SmallWords small;
 };
 
 namespace {
@@ -69,10 +69,8 @@ int ssv_dup_begin(ssv_ctx *c)
 	if (!c->dup) c->dup.reset(new ssv_dup_state());
 	ssv_dup_state &D = *c->dup;
 	D.phase = ssv_dup_state::IDLE;
-	const char *e = getenv("SSV_DUP_DIGEST_BITS"); // (tests) the digest cut to its low bits, so that digests collide
-	const int bits = e ? std::max(1, std::min(64, atoi(e))) : 64;
-	D.mask = bits == 64 ? ~0ull : ((1ull << bits) - 1);
-	e = getenv("SSV_DUP_SET_SLOTS"); // (tests) a small start, so that the set grows
+	D.mask = env_low_bits_mask("SSV_DUP_DIGEST_BITS"); // (tests) so that digests collide
+	const char *e = getenv("SSV_DUP_SET_SLOTS"); // (tests) a small start, so that the set grows
 	uint64_t slots = 16;
 	const uint64_t want = e ? (uint64_t)std::max<long long>(16, atoll(e)) : (uint64_t)1 << 16;
 	while (slots < want) slots *= 2;
@@ -80,7 +78,7 @@ int ssv_dup_begin(ssv_ctx *c)
 	D.slots = slots;
 	D.emitted = 0; D.entries = 0; D.st = ssv_dup_stats{};
 	for (auto &h : D.hold) { h.n = 0; h.cig = 0; h.seq_bytes = 0; h.name_bytes = 0; h.span = 0; }
-	CHECK(ensure(c, D.small, DUP_SMALL_BYTES)); CHECK(ensure_host(c, D.h_small, DUP_SMALL_BYTES));
+	CHECK(D.small.reserve(c, DUP_SMALL_BYTES));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
 	D.phase = ssv_dup_state::ACTIVE;
 	return SSV_OK;
@@ -97,12 +95,7 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 	HIPCHECK(c, hipSetDevice(c->device));
 	DevBatch d;
 	CHECK(stage_batch(c, b, d));
-	if (d.n && !d.ends) {
-		CHECK(ensure(c, c->ends_buf, (size_t)d.n + 16));
-		k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
-		HIPCHECK(c, hipGetLastError());
-		d.ends = P<uint8_t>(c->ends_buf);
-	}
+	CHECK(staged_ends(c, d));
 	DevNames names{nullptr, nullptr, 0};
 	if (d.n) CHECK(stage_names(c, nm, d.n, D.hnames, D.hoff, names));
 	ssv_dup_state::Hold &H = D.hold[D.cur], &H2 = D.hold[D.cur ^ 1];
@@ -113,15 +106,10 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 	if (N >= (1ll << 31)) { c->err = "ssv_dup_retain: the hold-back and the batch together exceed 2^31 records"; return SSV_E_RANGE; }
 	const size_t n4 = (size_t)N * 4 + 16;
 	const int64_t nw = (int64_t)grid_for(N, BLOCK) * WAVES_PER_BLOCK;
-	uint64_t *sm = P<uint64_t>(D.small);
-	const uint64_t *hs = P<uint64_t>(D.h_small);
+	uint64_t *sm = P<uint64_t>(D.small.dev);
+	const uint64_t *hs = P<uint64_t>(D.small.host);
 	auto w32 = [&](int k) { return reinterpret_cast<uint32_t *>(sm + k); };
-	auto fetch = [&]() -> int {
-		HIPCHECK(c, hipMemcpyAsync(D.h_small.p, D.small.p, DUP_SMALL_BYTES, hipMemcpyDeviceToHost, c->st));
-		HIPCHECK(c, hipStreamSynchronize(c->st));
-		return SSV_OK;
-	};
-	HIPCHECK(c, hipMemsetAsync(D.small.p, 0, DUP_SMALL_BYTES, c->st));
+	CHECK(D.small.clear(c));
 	CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(N + 1) * 4)); CHECK(ensure(c, c->scan_scratch64, scan_scratch_elems(N + 1) * 8));
 	uint32_t *sc32 = P<uint32_t>(c->scan_scratch);
 	uint64_t *sc64 = P<uint64_t>(c->scan_scratch64);
@@ -136,7 +124,7 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 		k_rt_place<<<grid_for(N, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(D.sel), P<uint32_t>(D.at), N, P<uint32_t>(D.cand));
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(fetch());
+	CHECK(D.small.fetch(c));
 	if (hs[DW_UNSORTED]) { c->err = "ssv_dup_retain: the records are not coordinate sorted"; return SSV_E_ARG; }
 	const int64_t m = (int64_t)hs[DW_M], cut = last ? N : (int64_t)hs[DW_CUT], n_hold = N - cut;
 
@@ -165,7 +153,7 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 		k_rt_place<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(D.rs), P<uint32_t>(D.rat), m, P<uint32_t>(D.rfirst));
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(fetch());
+	CHECK(D.small.fetch(c));
 	if (hs[DW_BAD]) { c->err = "ssv_dup_retain: a record that takes part comes without its qualities (decode with keep_all_seq)"; return SSV_E_ARG; }
 	const int64_t n_runs = (int64_t)hs[DW_RUNS], out_cig = (int64_t)hs[DW_OUT_CIG], hold_cig = (int64_t)hs[DW_HOLD_CIG], part = (int64_t)hs[DW_PART];
 	const uint64_t out_seq = hs[DW_OUT_SEQ], hold_seq = hs[DW_HOLD_SEQ], hold_names = hs[DW_HOLD_NAMES];
@@ -182,7 +170,7 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 		exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(D.isdup), P<uint32_t>(D.tmp), m, 0u, sc32, w32(DW_DUPS));
 		exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(D.keeper), P<uint32_t>(D.tmp), m, 0u, sc32, w32(DW_GROUPS));
 		HIPCHECK(c, hipGetLastError());
-		CHECK(fetch());
+		CHECK(D.small.fetch(c));
 		n_dup = (int64_t)hs[DW_DUPS]; n_groups = (int64_t)hs[DW_GROUPS];
 	}
 
@@ -191,15 +179,8 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 	CHECK(ensure(c, H2.tid, (size_t)n_hold * 4 + 16)); CHECK(ensure(c, H2.pos, (size_t)n_hold * 4 + 16)); CHECK(ensure(c, H2.ncig, (size_t)n_hold * 2 + 16)); CHECK(ensure(c, H2.ends, (size_t)n_hold + 16));
 	CHECK(ensure(c, H2.rec, (size_t)n_hold * sizeof(ssv_record) + 64)); CHECK(ensure(c, H2.cigar, (size_t)hold_cig * 4 + 64)); CHECK(ensure(c, H2.seq, (size_t)hold_seq + 64));
 	CHECK(ensure(c, H2.names, (size_t)hold_names + 16)); CHECK(ensure(c, H2.noff, (size_t)n_hold * 8 + 16));
-	auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t n_out = (size_t)cut;
-	const size_t sz[7] = {up(n_out * 4 + 16), up(n_out * 4 + 16), up(n_out * 2 + 16), up(n_out + 16), up(n_out * sizeof(ssv_record) + 64), up((size_t)out_cig * 4 + 64), up((size_t)out_seq + 64)};
-	size_t off[8]; off[0] = 0;
-	for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + sz[k];
-	ssv_ctx::RetainArena *arena = nullptr;
-	uint8_t *slab = nullptr;
-	CHECK(retain_slab(c, off[7], &arena, &slab));
-	struct Guard { ssv_ctx::RetainArena *arena; size_t need; bool keep = false; ~Guard() { if (!keep) retain_slab_undo(arena, need); } } guard{arena, off[7]};
+	RetainedSlab R((size_t)cut, (size_t)out_cig, (size_t)out_seq);
+	CHECK(R.take(c));
 
 	// ---- the marked heads' digests into the set; then every settled tail asks it ----
 	int64_t n_tail_waves = 0;
@@ -222,20 +203,18 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 	{
 		ProfScope ps(c, P_DUP_RETAIN, N);
 		if (cut) {
-			const DupDst dst{reinterpret_cast<int32_t *>(slab + off[0]), reinterpret_cast<int32_t *>(slab + off[1]), reinterpret_cast<uint16_t *>(slab + off[2]), slab + off[3],
-			                 reinterpret_cast<ssv_record *>(slab + off[4]), reinterpret_cast<uint32_t *>(slab + off[5]), slab + off[6], nullptr, nullptr};
+			const DupDst dst{R.dst(), nullptr, nullptr};
 			k_dup_gather<<<grid_for(cut * DUP_SUB, BLOCK), BLOCK, 0, c->st>>>(v, 0, cut, P<uint8_t>(D.mark), P<uint32_t>(D.cig_at), P<uint64_t>(D.seq_at), P<uint32_t>(D.seq_b), nullptr, nullptr, 1, dst);
 		}
 		if (n_hold) {
-			const DupDst dst{P<int32_t>(H2.tid), P<int32_t>(H2.pos), P<uint16_t>(H2.ncig), P<uint8_t>(H2.ends), P<ssv_record>(H2.rec), P<uint32_t>(H2.cigar), P<uint8_t>(H2.seq), P<char>(H2.names),
+			const DupDst dst{{P<int32_t>(H2.tid), P<int32_t>(H2.pos), P<uint16_t>(H2.ncig), P<uint8_t>(H2.ends), P<ssv_record>(H2.rec), P<uint32_t>(H2.cigar), P<uint8_t>(H2.seq)}, P<char>(H2.names),
 			                 P<uint64_t>(H2.noff)};
 			k_dup_gather<<<grid_for(n_hold * DUP_SUB, BLOCK), BLOCK, 0, c->st>>>(v, cut, n_hold, nullptr, P<uint32_t>(D.cig_at), P<uint64_t>(D.seq_at), P<uint32_t>(D.seq_b), P<uint64_t>(D.name_at),
 			                                                                    P<uint32_t>(D.name_b), 0, dst);
 		}
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(fetch()); // (the source - the decoder's buffers - may be overwritten by the next decode)
-	guard.keep = true;
+	CHECK(D.small.fetch(c)); // (the source - the decoder's buffers - may be overwritten by the next decode)
 	const int32_t span = (H.n && d.n) ? ((H.span && d.max_ref_span) ? std::max(H.span, d.max_ref_span) : 0) : (H.n ? H.span : d.max_ref_span);
 	H2.n = n_hold; H2.cig = hold_cig; H2.seq_bytes = hold_seq; H2.name_bytes = hold_names; H2.span = n_hold ? span : 0;
 	*carried = cut ? H.n : 0;
@@ -246,11 +225,7 @@ int ssv_dup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, int 
 	D.st.records += cut; D.st.taking_part += part; D.st.groups += n_groups; D.st.heads_marked += n_dup; D.st.tails_marked += n_tail_waves ? (int64_t)hs[DW_TAILS] : 0;
 	D.st.set_entries = D.entries; D.st.held_max = std::max(D.st.held_max, n_hold);
 	if (last) D.phase = ssv_dup_state::ENDED;
-	memset(out, 0, sizeof(*out));
-	out->n = cut; out->mem = SSV_MEM_DEVICE | SSV_MEM_PERSISTENT; out->max_ref_span = span;
-	out->tid = reinterpret_cast<const int32_t *>(slab + off[0]); out->pos = reinterpret_cast<const int32_t *>(slab + off[1]); out->n_cigar = reinterpret_cast<const uint16_t *>(slab + off[2]);
-	out->cigar_ends = slab + off[3]; out->rec = reinterpret_cast<const ssv_record *>(slab + off[4]); out->cigar = reinterpret_cast<const uint32_t *>(slab + off[5]);
-	out->seqqual = slab + off[6]; out->n_cigar_total = out_cig; out->seqqual_bytes = (int64_t)out_seq;
+	R.hand_out(out, span);
 	return SSV_OK;
 }
 

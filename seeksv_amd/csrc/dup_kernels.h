@@ -8,12 +8,13 @@
 
 #include "common.h"
 #include "clip_kernels.h"
+#include "retained.h"
 
 namespace ssv {
 
 enum : int { F_READ1 = 64, F_SUPPLEMENTARY = 2048 };
 constexpr uint64_t FNV_OFFSET = 1469598103934665603ull, FNV_PRIME = 1099511628211ull; // (as k_rt_measure)
-constexpr int DUP_SUB = 16;                       // lanes per record in the per-record kernels
+constexpr int DUP_SUB = RET_SUB;                  // lanes per record in the per-record kernels
 constexpr int DUP_PER_BLOCK = BLOCK / DUP_SUB;
 
 // the records a call works on: the run held back by the call before (a), then the new batch (b); n = a.n + b.n
@@ -316,10 +317,9 @@ __global__ __launch_bounds__(BLOCK) void k_dup_sizes(DupView v, int64_t cut, uin
 		const bool has = r.seq_off() != SSV_NO_SEQ;
 		part = dup_takes_part(r.flag(), r.tid(), r.mtid());
 		if (part && !has && lq > 0) *bad = 1u;
-		const uint8_t e = f.ends[f.j];
-		const bool clipped = e != 0xff && ((e & 15) == C_S || (e >> 4) == C_S);
+		const bool clipped = ends_clipped(f.ends[f.j]);
 		cig_n[i] = (uint32_t)r.n_cigar();
-		seq_b[i] = has && (i >= cut || clipped) ? (uint32_t)((lq + 1) / 2 + lq) : 0u;
+		seq_b[i] = has && (i >= cut || clipped) ? seq_bytes(lq) : 0u;
 		uint32_t nb = 0;
 		if (i >= cut) {
 			const char *p = f.nbase + f.noff[f.j] + f.nbias;
@@ -333,8 +333,7 @@ __global__ __launch_bounds__(BLOCK) void k_dup_sizes(DupView v, int64_t cut, uin
 	if (lane_id() == 0) wave_part[((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6] = (uint32_t)__popcll(bal);
 }
 
-struct DupDst {
-	int32_t *tid, *pos; uint16_t *n_cigar; uint8_t *ends; ssv_record *rec; uint32_t *cigar; uint8_t *seqqual;
+struct DupDst : RetDst {
 	char *names; uint64_t *name_off; // the hold-back only (NULL: no names)
 };
 
@@ -353,26 +352,13 @@ __global__ __launch_bounds__(BLOCK) void k_dup_gather(DupView v, int64_t first, 
 	const RecLine r = rec_load(f.rec, f.j);
 	const uint32_t coff = cig_at[i], sb = seq_b[i];
 	const uint64_t soff = seq_at[i];
-	const int nc = r.n_cigar();
 	const uint8_t e = f.ends[f.j];
 	if (sub == 0) {
-		const bool clipped = e != 0xff && ((e & 15) == C_S || (e >> 4) == C_S);
-		const bool keep = r.seq_off() != SSV_NO_SEQ && (!seq_only_clipped || clipped);
-		const uint64_t so = keep ? soff : SSV_NO_SEQ;
-		const uint32_t fmx = r.w_fmx | (mark && mark[i] ? (uint32_t)F_DUP : 0u);
-		dst.tid[d] = r.tid(); dst.pos[d] = r.pos(); dst.n_cigar[d] = (uint16_t)nc; dst.ends[d] = e;
-		uint4 *p = reinterpret_cast<uint4 *>(dst.rec + d);
-		p[0] = make_uint4(r.w_tid, r.w_pos, fmx, r.w_nc);
-		p[1] = make_uint4(r.w_lq, r.w_mtid, r.w_mpos, r.w_isize);
-		p[2] = make_uint4(coff, r.h0, r.h1, r.h2);
-		p[3] = make_uint4(r.h3, r.h4, (uint32_t)so, (uint32_t)(so >> 32));
+		const bool keep = r.seq_off() != SSV_NO_SEQ && (!seq_only_clipped || ends_clipped(e));
+		ret_write_record(dst, d, r, &e, r.w_fmx | (mark && mark[i] ? (uint32_t)F_DUP : 0u), coff, keep ? soff : SSV_NO_SEQ);
 		if (dst.name_off) dst.name_off[d] = name_at[i];
 	}
-	for (int j = sub; j < nc; j += DUP_SUB) dst.cigar[coff + (uint32_t)j] = r.op(f.cigar, j);
-	if (sb) {
-		const uint8_t *s = f.seqqual + r.seq_off();
-		for (uint32_t j = (uint32_t)sub; j < sb; j += DUP_SUB) dst.seqqual[soff + j] = s[j];
-	}
+	ret_copy_parts(dst, r, f.cigar, f.seqqual, sub, coff, soff, sb);
 	if (dst.names) {
 		const char *pn = f.nbase + f.noff[f.j] + f.nbias;
 		const uint32_t nb = name_b[i];

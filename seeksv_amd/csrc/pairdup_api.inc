@@ -3,8 +3,8 @@
 
 struct ssv_pairdup_state {
 	// ssv_pairdup_retain's temporaries
-	DBuf hnames, hoff, cig_n, cig_at, seq_b, seq_at, small;
-	HBuf h_small;
+	DBuf hnames, hoff, cig_n, cig_at, seq_b, seq_at;
+	SmallWords small;
 	// ssv_pairdup_mark's
 	DBuf src, part, at, keys[2], vals[2], first, pat, w1, w2, w3, g1, g2;
 	// when the mark returns everything goes back, the retain calls' temporaries too (the mark ends the retention: the sort and the passes that follow get the memory)
@@ -16,29 +16,6 @@ namespace {
 enum PdWord { PW_BAD, PW_CIG, PW_SEQ, PW_PART, PW_PAIRS, PW_MARKED, PW_MANY, PW_COUNT }; // u64 words of the small block
 constexpr size_t PD_SMALL_BYTES = 64;
 static_assert(PW_COUNT * 8 <= PD_SMALL_BYTES, "the small block holds every word");
-
-int pd_fetch(ssv_ctx *c, ssv_pairdup_state &S)
-{
-	HIPCHECK(c, hipMemcpyAsync(S.h_small.p, S.small.p, PD_SMALL_BYTES, hipMemcpyDeviceToHost, c->st));
-	HIPCHECK(c, hipStreamSynchronize(c->st));
-	return SSV_OK;
-}
-
-int pd_digest_bits()
-{
-	const char *e = getenv("SSV_DUP_DIGEST_BITS"); // (tests) the name hash cut to its low bits, so that names collide
-	return e ? std::max(1, std::min(64, atoi(e))) : 64;
-}
-
-inline size_t pd_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the parts of a retained batch with rows: the seven of every retained batch, then the rows
-void pd_layout(size_t n, size_t cig, size_t seq, size_t off[9])
-{
-	const size_t sz[8] = {pd_up(n * 4 + 16), pd_up(n * 4 + 16), pd_up(n * 2 + 16), pd_up(n + 16), pd_up(n * sizeof(ssv_record) + 64), pd_up(cig * 4 + 64), pd_up(seq + 64), pd_up(n * sizeof(PdRow) + 16)};
-	off[0] = 0;
-	for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + sz[k];
-}
 
 ssv_ctx::PairdupLive *pd_live(ssv_ctx *c, const ssv_batch_t *b)
 {
@@ -60,21 +37,15 @@ int ssv_pairdup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, 
 	ssv_pairdup_state &S = *c->pairdup;
 	DevBatch d;
 	CHECK(stage_batch(c, b, d));
-	if (d.n && !d.ends) {
-		CHECK(ensure(c, c->ends_buf, (size_t)d.n + 16));
-		k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
-		HIPCHECK(c, hipGetLastError());
-		d.ends = P<uint8_t>(c->ends_buf);
-	}
+	CHECK(staged_ends(c, d));
 	DevNames names{nullptr, nullptr, 0};
 	if (d.n) CHECK(stage_names(c, nm, d.n, S.hnames, S.hoff, names));
 	const int64_t N = d.n;
-	const int bits = pd_digest_bits();
-	const uint64_t mask = bits == 64 ? ~0ull : ((1ull << bits) - 1);
-	CHECK(ensure(c, S.small, PD_SMALL_BYTES)); CHECK(ensure_host(c, S.h_small, PD_SMALL_BYTES));
-	uint64_t *sm = P<uint64_t>(S.small);
-	const uint64_t *hs = P<uint64_t>(S.h_small);
-	HIPCHECK(c, hipMemsetAsync(S.small.p, 0, PD_SMALL_BYTES, c->st));
+	const uint64_t mask = env_low_bits_mask("SSV_DUP_DIGEST_BITS"); // (tests) so that names collide
+	CHECK(S.small.reserve(c, PD_SMALL_BYTES));
+	uint64_t *sm = P<uint64_t>(S.small.dev);
+	const uint64_t *hs = P<uint64_t>(S.small.host);
+	CHECK(S.small.clear(c));
 
 	// ---- what every record takes in the batch that stays ----
 	if (N) {
@@ -86,23 +57,14 @@ int ssv_pairdup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, 
 		exclusive_scan<uint32_t, uint64_t>(c->st, P<uint32_t>(S.seq_b), P<uint64_t>(S.seq_at), N, 0ull, P<uint64_t>(c->scan_scratch64), sm + PW_SEQ);
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(pd_fetch(c, S));
+	CHECK(S.small.fetch(c));
 	const size_t out_cig = (size_t)hs[PW_CIG], out_seq = (size_t)hs[PW_SEQ];
 
-	// ---- memory (the last point where the call can fail for lack of it) ----
-	size_t off[9];
-	pd_layout((size_t)N, out_cig, out_seq, off);
-	ssv_tid_run *runs = nullptr;
-	if (b->tid_runs && b->n_tid_runs > 0) { // (host memory: a copy that lives as long as the batch)
-		runs = static_cast<ssv_tid_run *>(malloc((size_t)b->n_tid_runs * sizeof(ssv_tid_run)));
-		if (!runs) { c->err = "out of host memory (tid_runs)"; return SSV_E_NOMEM; }
-		memcpy(runs, b->tid_runs, (size_t)b->n_tid_runs * sizeof(ssv_tid_run));
-	}
-	ssv_ctx::RetainArena *arena = nullptr;
-	uint8_t *slab = nullptr;
-	struct Guard { ssv_ctx::RetainArena *&arena; size_t need; ssv_tid_run *&runs; bool keep = false; ~Guard() { if (!keep) { if (arena) retain_slab_undo(arena, need); free(runs); } } } guard{arena, off[8], runs};
-	CHECK(retain_slab(c, off[8], &arena, &slab));
-	PdRow *rows = reinterpret_cast<PdRow *>(slab + off[7]);
+	// ---- memory (the last point where the call can fail for lack of it): the seven parts of every retained batch, then the rows ----
+	RetainedSlab R((size_t)N, out_cig, out_seq, (size_t)N * sizeof(PdRow) + 16);
+	CHECK(R.copy_runs(c, b));
+	CHECK(R.take(c));
+	PdRow *rows = R.part<PdRow>(7);
 
 	// ---- the rows, and the records into the slab ----
 	if (N) {
@@ -111,22 +73,15 @@ int ssv_pairdup_retain(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm, 
 		DupView v;
 		memset(&v, 0, sizeof(v));
 		v.b = d; v.nb = names; v.n = N;
-		const DupDst dst{reinterpret_cast<int32_t *>(slab + off[0]), reinterpret_cast<int32_t *>(slab + off[1]), reinterpret_cast<uint16_t *>(slab + off[2]), slab + off[3],
-		                 reinterpret_cast<ssv_record *>(slab + off[4]), reinterpret_cast<uint32_t *>(slab + off[5]), slab + off[6], nullptr, nullptr};
+		const DupDst dst{R.dst(), nullptr, nullptr};
 		k_dup_gather<<<grid_for(N * DUP_SUB, BLOCK), BLOCK, 0, c->st>>>(v, 0, N, nullptr, P<uint32_t>(S.cig_at), P<uint64_t>(S.seq_at), P<uint32_t>(S.seq_b), nullptr, nullptr, 1, dst);
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(pd_fetch(c, S)); // (the source - the decoder's buffers - may be overwritten by the next decode)
+	CHECK(S.small.fetch(c)); // (the source - the decoder's buffers - may be overwritten by the next decode)
 	if (hs[PW_BAD]) { c->err = "ssv_pairdup_retain: a record that takes part comes without its qualities (decode with keep_all_seq)"; return SSV_E_ARG; }
-	guard.keep = true;
-	for (size_t k = c->pairdup_live.size(); k-- > 0;) if (c->pairdup_live[k].slab == (const void *)slab) c->pairdup_live.erase(c->pairdup_live.begin() + (long)k);
-	c->pairdup_live.push_back(ssv_ctx::PairdupLive{slab, N, rows});
-	memset(out, 0, sizeof(*out));
-	out->n = N; out->mem = SSV_MEM_DEVICE | SSV_MEM_PERSISTENT; out->max_ref_span = b->max_ref_span;
-	out->tid = reinterpret_cast<const int32_t *>(slab + off[0]); out->pos = reinterpret_cast<const int32_t *>(slab + off[1]); out->n_cigar = reinterpret_cast<const uint16_t *>(slab + off[2]);
-	out->cigar_ends = slab + off[3]; out->rec = reinterpret_cast<const ssv_record *>(slab + off[4]); out->cigar = reinterpret_cast<const uint32_t *>(slab + off[5]);
-	out->seqqual = slab + off[6]; out->n_cigar_total = (int64_t)out_cig; out->seqqual_bytes = (int64_t)out_seq;
-	if (runs) { out->tid_runs = runs; out->n_tid_runs = b->n_tid_runs; }
+	for (size_t k = c->pairdup_live.size(); k-- > 0;) if (c->pairdup_live[k].slab == (const void *)R.slab) c->pairdup_live.erase(c->pairdup_live.begin() + (long)k);
+	c->pairdup_live.push_back(ssv_ctx::PairdupLive{R.slab, N, rows});
+	R.hand_out(out, b->max_ref_span);
 	return SSV_OK;
 }
 
@@ -174,17 +129,18 @@ int ssv_pairdup_mark(ssv_ctx *c, ssv_batch_t *batches, int64_t n_batches, ssv_pa
 	ssv_pairdup_state &S = *c->pairdup;
 	struct Drop { ssv_pairdup_state &S; ~Drop() { S.drop(); } } drop{S};
 	const int n_src = (int)tab.size();
-	const int bits = pd_digest_bits();
-	CHECK(ensure(c, S.small, PD_SMALL_BYTES)); CHECK(ensure_host(c, S.h_small, PD_SMALL_BYTES));
-	uint64_t *sm = P<uint64_t>(S.small);
-	const uint64_t *hs = P<uint64_t>(S.h_small);
+	int bits;
+	(void)env_low_bits_mask("SSV_DUP_DIGEST_BITS", &bits); // (the name sort looks at the bits that ssv_pairdup_retain kept)
+	CHECK(S.small.reserve(c, PD_SMALL_BYTES));
+	uint64_t *sm = P<uint64_t>(S.small.dev);
+	const uint64_t *hs = P<uint64_t>(S.small.host);
 	int64_t m = 0, n_pairs = 0, marked = 0, many = 0;
 
 	if (N) {
 		// ---- the rows that take part, with g, ordered by name hash ----
 		CHECK(ensure(c, S.src, tab.size() * sizeof(PdSrc)));
 		HIPCHECK(c, hipMemcpyAsync(S.src.p, tab.data(), tab.size() * sizeof(PdSrc), hipMemcpyHostToDevice, c->st));
-		HIPCHECK(c, hipMemsetAsync(S.small.p, 0, PD_SMALL_BYTES, c->st));
+		CHECK(S.small.clear(c));
 		const PdSrc *src = P<PdSrc>(S.src);
 		CHECK(ensure(c, S.part, (size_t)N * 4 + 16)); CHECK(ensure(c, S.at, (size_t)N * 4 + 16));
 		CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(N + 1) * 4 + 64));
@@ -194,7 +150,7 @@ int ssv_pairdup_mark(ssv_ctx *c, ssv_batch_t *batches, int64_t n_batches, ssv_pa
 			exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(S.part), P<uint32_t>(S.at), N, 0u, P<uint32_t>(c->scan_scratch), reinterpret_cast<uint32_t *>(sm + PW_PART));
 			HIPCHECK(c, hipGetLastError());
 		}
-		CHECK(pd_fetch(c, S)); // (the table's host copy is read by now)
+		CHECK(S.small.fetch(c)); // (the table's host copy is read by now)
 		m = (int64_t)hs[PW_PART];
 	}
 	if (m) {
@@ -212,7 +168,7 @@ int ssv_pairdup_mark(ssv_ctx *c, ssv_batch_t *batches, int64_t n_batches, ssv_pa
 			k_pd_join<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(src, n_src, keys[cur], vals[cur], m, P<uint32_t>(S.first));
 			exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(S.first), P<uint32_t>(S.pat), m, 0u, P<uint32_t>(c->scan_scratch), reinterpret_cast<uint32_t *>(sm + PW_PAIRS));
 			HIPCHECK(c, hipGetLastError());
-			CHECK(pd_fetch(c, S));
+			CHECK(S.small.fetch(c));
 			n_pairs = (int64_t)hs[PW_PAIRS];
 			if (n_pairs) {
 				// (the pairs' sorts use the name sort's buffers: the rows in name order move to the side that the first pair sort writes last)
@@ -240,7 +196,7 @@ int ssv_pairdup_mark(ssv_ctx *c, ssv_batch_t *batches, int64_t n_batches, ssv_pa
 			k_pd_pick<<<grid_for(n_pairs, BLOCK), BLOCK, 0, c->st>>>(src, n_src, vals[cur], n_pairs, P<uint64_t>(S.w1), P<uint64_t>(S.w2), P<uint64_t>(S.w3), P<uint32_t>(S.g1), P<uint32_t>(S.g2),
 			                                                        reinterpret_cast<unsigned long long *>(sm + PW_MARKED));
 			HIPCHECK(c, hipGetLastError());
-			CHECK(pd_fetch(c, S));
+			CHECK(S.small.fetch(c));
 			marked = (int64_t)hs[PW_MARKED]; many = (int64_t)hs[PW_MANY];
 		}
 	}

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "clip_kernels.h"
 #include "dup_kernels.h"
+#include "retained.h"
 
 namespace ssv {
 
@@ -30,10 +31,9 @@ __global__ __launch_bounds__(BLOCK) void k_pd_sizes(DevBatch b, uint32_t *__rest
 	const uint4 q1 = p[1], q3 = p[3];
 	const int lq = (int)q1.x > 0 ? (int)q1.x : 0;
 	const bool has = ((uint64_t)q3.z | ((uint64_t)q3.w << 32)) != SSV_NO_SEQ;
-	const uint8_t e = b.ends[i];
-	const bool clipped = e != 0xff && ((e & 15) == C_S || (e >> 4) == C_S);
+	const bool clipped = ends_clipped(b.ends[i]);
 	cig_n[i] = (uint32_t)b.n_cigar[i];
-	seq_b[i] = has && clipped ? (uint32_t)((lq + 1) / 2 + lq) : 0u;
+	seq_b[i] = has && clipped ? seq_bytes(lq) : 0u;
 }
 
 // 16 lanes per record: the row.  *bad = 1: a record that takes part came without its qualities.
@@ -90,22 +90,11 @@ __global__ __launch_bounds__(BLOCK) void k_pd_rows(DevBatch b, DevNames nm, uint
 // one batch of the call: where its records start in the sequence of all of them, its lines (the flags are written there) and its rows
 struct PdSrc { int64_t start; ssv_record *rec; const PdRow *rows; };
 
-// the batch that holds record g: the last one that starts at or below g (as sort_kernels.h's sort_find)
-__device__ __forceinline__ int pd_find(const PdSrc *__restrict__ src, int n_src, int64_t g)
-{
-	int lo = 0, hi = n_src;
-	while (hi - lo > 1) {
-		const int mid = (lo + hi) >> 1;
-		if (src[mid].start <= g) lo = mid; else hi = mid;
-	}
-	return lo;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_pd_part(const PdSrc *__restrict__ src, int n_src, int64_t n, uint32_t *__restrict__ part)
 {
 	const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (g >= n) return;
-	const int k = pd_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	part[g] = src[k].rows[g - src[k].start].kind != 0u;
 }
 
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void k_pd_compact(const PdSrc *__restrict__ 
 {
 	const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (g >= n || !part[g]) return;
-	const int k = pd_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	keys[at[g]] = src[k].rows[g - src[k].start].name_hash;
 	vals[at[g]] = (uint32_t)g;
 }
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(BLOCK) void k_pd_compact(const PdSrc *__restrict__ 
 struct PdFields { int tid, pos, flag, mtid, mpos; };
 __device__ __forceinline__ PdFields pd_fields(const PdSrc *__restrict__ src, int n_src, int64_t g, const PdRow **row)
 {
-	const int k = pd_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	const int64_t j = g - src[k].start;
 	const uint4 *p = reinterpret_cast<const uint4 *>(src[k].rec + j);
 	const uint4 a = p[0], b = p[1];
@@ -212,7 +201,7 @@ __global__ __launch_bounds__(BLOCK) void k_pd_pick(const PdSrc *__restrict__ src
 			const uint32_t gs[2] = {g1[p], g2[p]};
 #pragma unroll
 			for (int s = 0; s < 2; ++s) {
-				const int bk = pd_find(src, n_src, gs[s]);
+				const int bk = src_find(src, n_src, gs[s]);
 				ssv_record *r = src[bk].rec + ((int64_t)gs[s] - src[bk].start);
 				r->flag = (uint16_t)(r->flag | (uint16_t)F_DUP);
 			}

@@ -26,9 +26,7 @@ int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p)
 	R.phase = ssv_rt_state::IDLE;
 	R.min_mapq = p->min_mapq; R.n_targets = p->n_targets;
 	// SSV_RT_HASH_BITS (tests): the name hash cut to its low bits, so that names collide and the exact path runs
-	const char *e = getenv("SSV_RT_HASH_BITS");
-	R.hash_bits = e ? std::max(1, std::min(64, atoi(e))) : 64;
-	R.hash_mask = R.hash_bits == 64 ? ~0ull : ((1ull << R.hash_bits) - 1);
+	R.hash_mask = env_low_bits_mask("SSV_RT_HASH_BITS", &R.hash_bits);
 	R.rec_base = 0; R.n_cand = 0; R.name_used = R.seq_used = R.cig_used = 0;
 	CHECK(ensure(c, R.rank, (size_t)p->n_targets * 4 + 16));
 	if (p->n_targets) HIPCHECK(c, hipMemcpyAsync(R.rank.p, p->name_rank, (size_t)p->n_targets * 4, hipMemcpyHostToDevice, c->st));
@@ -51,12 +49,7 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 	const int64_t n = d.n;
 	if (n == 0) return SSV_OK;
 	ProfScope ps(c, P_RT_SCAN, n);
-	if (!d.ends) {
-		CHECK(ensure(c, c->ends_buf, (size_t)n + 16));
-		k_build_ends<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
-		HIPCHECK(c, hipGetLastError());
-		d.ends = P<uint8_t>(c->ends_buf);
-	}
+	CHECK(staged_ends(c, d));
 	DevNames names;
 	CHECK(stage_names(c, nm, n, R.hnames, R.hoff, names));
 	// ---- select: the ends column (and behind a passing pair the flag / mapq of the line) -> ordered compaction ----

@@ -830,9 +830,9 @@ int stage_batch(ssv_ctx *c, const ssv_batch_t *b, DevBatch &d, bool keep_announc
 	return SSV_OK;
 }
 
-// `need` bytes (a multiple of 256: every batch starts 256-byte aligned) for a batch that stays (ssv_batch_retain, ssv_dup_retain): room in the newest arena,
-// or a new one - 256 MB first, doubling up to SSV_RETAIN_ARENA_MB (4 GB), never smaller than the batch.  The arena counts the slab as live; a caller that
-// fails afterwards takes it back (retain_slab_undo).
+// `need` bytes (a multiple of 256: every batch starts 256-byte aligned) for a batch that stays (RetainedSlab below, for ssv_batch_retain, ssv_dup_retain,
+// ssv_pairdup_retain and ssv_batch_sort): room in the newest arena, or a new one - 256 MB first, doubling up to SSV_RETAIN_ARENA_MB (4 GB), never smaller than
+// the batch.  The arena counts the slab as live; a caller that fails afterwards takes it back (retain_slab_undo).
 int retain_slab(ssv_ctx *c, size_t need, ssv_ctx::RetainArena **arena_out, uint8_t **slab)
 {
 	ssv_ctx::RetainArena *arena = nullptr;
@@ -868,6 +868,93 @@ int retain_slab(ssv_ctx *c, size_t need, ssv_ctx::RetainArena **arena_out, uint8
 	return SSV_OK;
 }
 inline void retain_slab_undo(ssv_ctx::RetainArena *arena, size_t need) { --arena->live; arena->used -= need; arena->slabs.pop_back(); }
+
+// The retained form, stated once: seven parts in one slab, each 256-byte aligned - tid, pos, n_cigar, cigar_ends, the lines, the operations, the
+// bases + qualities - and behind them `extra` bytes of the producer's own (ssv_pairdup_retain's rows).  The object holds the slab, and a host copy of tid_runs
+// when it was given one, and gives both back when it goes - unless the batch was handed out.
+struct RetainedSlab {
+	size_t n, cigar_total, seq_bytes;
+	size_t off[9]; // off[7]: where the extra bytes begin, off[8]: the slab's size
+	ssv_ctx::RetainArena *arena = nullptr;
+	uint8_t *slab = nullptr;
+	ssv_tid_run *runs = nullptr;
+	int64_t n_runs = 0;
+	bool handed_out = false;
+	RetainedSlab(size_t n_, size_t cigar_total_, size_t seq_bytes_, size_t extra = 0) : n(n_), cigar_total(cigar_total_), seq_bytes(seq_bytes_)
+	{
+		const size_t sz[8] = {n * 4 + 16, n * 4 + 16, n * 2 + 16, n + 16, n * sizeof(ssv_record) + 64, cigar_total * 4 + 64, seq_bytes + 64, extra};
+		off[0] = 0;
+		for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + ((sz[k] + 255) & ~(size_t)255);
+	}
+	RetainedSlab(const RetainedSlab &) = delete;
+	RetainedSlab &operator=(const RetainedSlab &) = delete;
+	~RetainedSlab() { if (!handed_out) { if (arena) retain_slab_undo(arena, off[8]); free(runs); } }
+	int take(ssv_ctx *c) { return retain_slab(c, off[8], &arena, &slab); }
+	// room for a host copy of the tid column as `count` runs, which lives as long as the batch (NULL: none to be had, the error is set)
+	ssv_tid_run *new_runs(ssv_ctx *c, int64_t count)
+	{
+		runs = static_cast<ssv_tid_run *>(malloc((size_t)count * sizeof(ssv_tid_run)));
+		if (!runs) c->err = "out of host memory (tid_runs)";
+		else n_runs = count;
+		return runs;
+	}
+	int copy_runs(ssv_ctx *c, const ssv_batch_t *b) // the runs of a batch that has them
+	{
+		if (!b->tid_runs || b->n_tid_runs <= 0) return SSV_OK;
+		if (!new_runs(c, b->n_tid_runs)) return SSV_E_NOMEM;
+		memcpy(runs, b->tid_runs, (size_t)b->n_tid_runs * sizeof(ssv_tid_run));
+		return SSV_OK;
+	}
+	template <typename T> T *part(int k) const { return reinterpret_cast<T *>(slab + off[k]); }
+	RetDst dst() const { return RetDst{part<int32_t>(0), part<int32_t>(1), part<uint16_t>(2), part<uint8_t>(3), part<ssv_record>(4), part<uint32_t>(5), part<uint8_t>(6)}; }
+	// the batch as its owner sees it; from here on the slab and the runs are the batch's (ssv_batch_release)
+	void hand_out(ssv_batch_t *out, int32_t max_ref_span)
+	{
+		const RetDst d = dst();
+		handed_out = true;
+		memset(out, 0, sizeof(*out));
+		out->n = (int64_t)n; out->mem = SSV_MEM_DEVICE | SSV_MEM_PERSISTENT; out->max_ref_span = max_ref_span;
+		out->tid = d.tid; out->pos = d.pos; out->n_cigar = d.n_cigar; out->cigar_ends = d.ends; out->rec = d.rec; out->cigar = d.cigar; out->seqqual = d.seqqual;
+		out->n_cigar_total = (int64_t)cigar_total; out->seqqual_bytes = (int64_t)seq_bytes;
+		if (runs) { out->tid_runs = runs; out->n_tid_runs = n_runs; }
+	}
+};
+
+// a staged batch that came without its cigar_ends column: built from the lines into the context's buffer
+int staged_ends(ssv_ctx *c, DevBatch &d)
+{
+	if (d.ends || d.n == 0) return SSV_OK;
+	CHECK(ensure(c, c->ends_buf, (size_t)d.n + 16));
+	k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, P<uint8_t>(c->ends_buf));
+	HIPCHECK(c, hipGetLastError());
+	d.ends = P<uint8_t>(c->ends_buf);
+	return SSV_OK;
+}
+
+// A small block of device words that a call's kernels and scans leave their counts in, and its pinned host copy.  What the words mean, and how many
+// bytes they take, is the stage's.
+struct SmallWords {
+	DBuf dev;
+	HBuf host;
+	size_t bytes = 0;
+	int reserve(ssv_ctx *c, size_t bytes_) { bytes = bytes_; CHECK(ensure(c, dev, bytes)); return ensure_host(c, host, bytes); }
+	int clear(ssv_ctx *c) { HIPCHECK(c, hipMemsetAsync(dev.p, 0, bytes, c->st)); return SSV_OK; }
+	int fetch(ssv_ctx *c) // the host copy is current, and everything on the stream before it is done
+	{
+		HIPCHECK(c, hipMemcpyAsync(host.p, dev.p, bytes, hipMemcpyDeviceToHost, c->st));
+		HIPCHECK(c, hipStreamSynchronize(c->st));
+		return SSV_OK;
+	}
+};
+
+// (tests) an environment variable that cuts a 64-bit hash to its low bits, so that hashes collide: the mask, and how many bits it keeps
+uint64_t env_low_bits_mask(const char *name, int *bits_out = nullptr)
+{
+	const char *e = getenv(name);
+	const int bits = e ? std::max(1, std::min(64, atoi(e))) : 64;
+	if (bits_out) *bits_out = bits;
+	return bits == 64 ? ~0ull : ((1ull << bits) - 1);
+}
 
 __global__ void k_max_span(DevBatch b, int *out)
 {
@@ -1005,40 +1092,23 @@ int ssv_batch_retain(ssv_ctx *c, const ssv_batch_t *b, ssv_batch_t *out)
 	DevBatch d;
 	CHECK(stage_batch(c, b, d)); // (builds the record lines when the batch has none)
 	const size_t n = (size_t)b->n;
-	auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t sz[7] = {up(n * 4 + 16), up(n * 4 + 16), up(n * 2 + 16), up(n + 16), up(n * sizeof(ssv_record) + 64), up((size_t)b->n_cigar_total * 4 + 64), up((size_t)b->seqqual_bytes + 64)};
-	size_t off[8]; off[0] = 0;
-	for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + sz[k];
-	uint8_t *slab = nullptr;
-	ssv_tid_run *runs = nullptr;
-	if (b->tid_runs && b->n_tid_runs > 0) { // (host memory: a copy that lives as long as the batch)
-		runs = static_cast<ssv_tid_run *>(malloc((size_t)b->n_tid_runs * sizeof(ssv_tid_run)));
-		if (!runs) { c->err = "out of host memory (tid_runs)"; return SSV_E_NOMEM; }
-		memcpy(runs, b->tid_runs, (size_t)b->n_tid_runs * sizeof(ssv_tid_run));
-	}
-	ssv_ctx::RetainArena *arena = nullptr;
-	struct Guard { ssv_ctx::RetainArena *&arena; size_t need; ssv_tid_run *&runs; bool keep = false; ~Guard() { if (!keep) { if (arena) retain_slab_undo(arena, need); free(runs); } } } guard{arena, off[7], runs};
+	RetainedSlab R(n, (size_t)b->n_cigar_total, (size_t)b->seqqual_bytes);
+	CHECK(R.copy_runs(c, b));
 	static const bool timing = [] { const char *e = getenv("SSV_TIMING"); return e ? atoi(e) : 0; }() >= 2; // SSV_TIMING=2: per-chunk detail
 	const auto t0 = std::chrono::steady_clock::now();
-	CHECK(retain_slab(c, off[7], &arena, &slab));
+	CHECK(R.take(c));
 	const auto t1 = std::chrono::steady_clock::now();
 	const void *src[7] = {d.tid, d.pos, d.n_cigar, d.ends, d.rec, d.cigar, d.seqqual};
-	const size_t bytes[7] = {n * 4, n * 4, n * 2, n, n * sizeof(ssv_record), (size_t)b->n_cigar_total * 4, (size_t)b->seqqual_bytes};
+	const size_t bytes[7] = {n * 4, n * 4, n * 2, n, n * sizeof(ssv_record), R.cigar_total * 4, R.seq_bytes};
 	if (!d.ends && n) { // no cigar_ends column: built from the lines, straight into the slab
-		k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, slab + off[3]);
+		k_build_ends<<<grid_for(d.n, BLOCK), BLOCK, 0, c->st>>>(d, R.part<uint8_t>(3));
 		HIPCHECK(c, hipGetLastError());
 	}
-	for (int k = 0; k < 7; ++k) if (src[k] && bytes[k]) HIPCHECK(c, hipMemcpyAsync(slab + off[k], src[k], bytes[k], hipMemcpyDeviceToDevice, c->st));
+	for (int k = 0; k < 7; ++k) if (src[k] && bytes[k]) HIPCHECK(c, hipMemcpyAsync(R.part<uint8_t>(k), src[k], bytes[k], hipMemcpyDeviceToDevice, c->st));
 	HIPCHECK(c, hipStreamSynchronize(c->st)); // the source (the decoder's buffers) may be overwritten by the next decode
-	if (timing) fprintf(stderr, "[timing] (retain: %lld records, %zu bytes: hipMalloc %.4f s, copies + wait %.4f s)\n", (long long)b->n, off[7], std::chrono::duration<double>(t1 - t0).count(),
+	if (timing) fprintf(stderr, "[timing] (retain: %lld records, %zu bytes: hipMalloc %.4f s, copies + wait %.4f s)\n", (long long)b->n, R.off[8], std::chrono::duration<double>(t1 - t0).count(),
 	                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
-	guard.keep = true;
-	memset(out, 0, sizeof(*out));
-	out->n = b->n; out->mem = SSV_MEM_DEVICE | SSV_MEM_PERSISTENT; out->max_ref_span = b->max_ref_span;
-	out->tid = reinterpret_cast<const int32_t *>(slab + off[0]); out->pos = reinterpret_cast<const int32_t *>(slab + off[1]); out->n_cigar = reinterpret_cast<const uint16_t *>(slab + off[2]);
-	out->cigar_ends = slab + off[3]; out->rec = reinterpret_cast<const ssv_record *>(slab + off[4]); out->cigar = reinterpret_cast<const uint32_t *>(slab + off[5]);
-	out->seqqual = slab + off[6]; out->n_cigar_total = b->n_cigar_total; out->seqqual_bytes = b->seqqual_bytes;
-	if (runs) { out->tid_runs = runs; out->n_tid_runs = b->n_tid_runs; }
+	R.hand_out(out, b->max_ref_span);
 	return SSV_OK;
 }
 

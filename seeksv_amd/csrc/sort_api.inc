@@ -7,8 +7,9 @@ struct ssv_sort_state {
 	std::vector<uint32_t> change_index;
 	std::vector<int32_t> change_tid;
 	// a call's temporaries (given back when it returns: the passes that follow get the memory)
-	DBuf src, keys[2], vals[2], cig_n, seq_b, cig_at, seq_at, flag, mark, at, tile_last, tile_prev, ch_index, ch_tid, raw_runs, small;
-	HBuf h_small, h_changes, h_raw_runs;
+	DBuf src, keys[2], vals[2], cig_n, seq_b, cig_at, seq_at, flag, mark, at, tile_last, tile_prev, ch_index, ch_tid, raw_runs;
+	HBuf h_changes, h_raw_runs;
+	SmallWords small;
 	void drop()
 	{
 		for (DBuf *x : {&src, &keys[0], &keys[1], &vals[0], &vals[1], &cig_n, &seq_b, &cig_at, &seq_at, &flag, &mark, &at, &tile_last, &tile_prev, &ch_index, &ch_tid, &raw_runs}) x->reset();
@@ -26,13 +27,6 @@ constexpr int64_t SORT_DEFAULT_BATCH = (int64_t)16 << 20;
 
 inline int bits_of(uint64_t x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
 
-int sort_fetch(ssv_ctx *c, ssv_sort_state &S)
-{
-	HIPCHECK(c, hipMemcpyAsync(S.h_small.p, S.small.p, SORT_SMALL_BYTES, hipMemcpyDeviceToHost, c->st));
-	HIPCHECK(c, hipStreamSynchronize(c->st));
-	return SSV_OK;
-}
-
 // The contig changes among the records of one batch that are not UNMAP|MUNMAP (tid: its hot column, rec: its lines), appended to the lists; prev_tid: the
 // contig of the last such record before the batch, and behind it on return.
 int sort_changes(ssv_ctx *c, ssv_sort_state &S, const int32_t *tid, const ssv_record *rec, int64_t n, int32_t &prev_tid)
@@ -42,15 +36,15 @@ int sort_changes(ssv_ctx *c, ssv_sort_state &S, const int32_t *tid, const ssv_re
 	CHECK(ensure(c, S.flag, (size_t)n * 2 + 16)); CHECK(ensure(c, S.mark, (size_t)n * 4 + 16)); CHECK(ensure(c, S.at, (size_t)n * 4 + 16));
 	CHECK(ensure(c, S.tile_last, (size_t)n_tiles * 4 + 16)); CHECK(ensure(c, S.tile_prev, (size_t)n_tiles * 4 + 16));
 	CHECK(ensure(c, c->scan_scratch, (size_t)scan_scratch_elems(n) * 4 + 64));
-	uint32_t *w = P<uint32_t>(S.small);
+	uint32_t *w = P<uint32_t>(S.small.dev);
 	k_sort_flags<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(rec, n, P<uint16_t>(S.flag));
 	k_tid_tile_last<<<(unsigned)n_tiles, BLOCK, 0, c->st>>>(tid, P<uint16_t>(S.flag), n, P<int32_t>(S.tile_last));
 	k_tid_tile_carry<<<1, WAVE, 0, c->st>>>(P<int32_t>(S.tile_last), n_tiles, prev_tid, P<int32_t>(S.tile_prev), reinterpret_cast<int32_t *>(w + SW_LAST_TID));
 	k_sort_change_mark<<<(unsigned)n_tiles, BLOCK, 0, c->st>>>(tid, P<uint16_t>(S.flag), n, P<int32_t>(S.tile_prev), P<uint32_t>(S.mark));
 	exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(S.mark), P<uint32_t>(S.at), n, 0u, P<uint32_t>(c->scan_scratch), w + SW_CHANGES);
 	HIPCHECK(c, hipGetLastError());
-	CHECK(sort_fetch(c, S));
-	const uint32_t *hs = P<uint32_t>(S.h_small);
+	CHECK(S.small.fetch(c));
+	const uint32_t *hs = P<uint32_t>(S.small.host);
 	const size_t m = hs[SW_CHANGES];
 	prev_tid = (int32_t)hs[SW_LAST_TID];
 	if (!m) return SSV_OK;
@@ -104,11 +98,11 @@ int ssv_batch_sort(ssv_ctx *c, ssv_batch_t *in, int64_t n_in, int32_t n_targets,
 	const bool in_is_ours = !S.batches.empty() && in == S.batches.data(); // (the outputs of the call before, sorted again)
 	const std::vector<ssv_batch_t> inputs(in, in + n_in);
 	struct Drop { ssv_sort_state &S; ~Drop() { S.drop(); } } drop{S};
-	CHECK(ensure(c, S.small, SORT_SMALL_BYTES)); CHECK(ensure_host(c, S.h_small, SORT_SMALL_BYTES));
-	uint32_t *w = P<uint32_t>(S.small);
-	uint64_t *w64 = P<uint64_t>(S.small) + SORT_SMALL_U64_AT;
-	const uint32_t *hs = P<uint32_t>(S.h_small);
-	const uint64_t *hs64 = P<uint64_t>(S.h_small) + SORT_SMALL_U64_AT;
+	CHECK(S.small.reserve(c, SORT_SMALL_BYTES));
+	uint32_t *w = P<uint32_t>(S.small.dev);
+	uint64_t *w64 = P<uint64_t>(S.small.dev) + SORT_SMALL_U64_AT;
+	const uint32_t *hs = P<uint32_t>(S.small.host);
+	const uint64_t *hs64 = P<uint64_t>(S.small.host) + SORT_SMALL_U64_AT;
 
 	// ---- the inputs as one sequence; is it in order already ----
 	const int n_src = (int)std::max<int64_t>(1, n_in);
@@ -123,14 +117,14 @@ int ssv_batch_sort(ssv_ctx *c, ssv_batch_t *in, int64_t n_in, int32_t n_targets,
 	}
 	CHECK(ensure(c, S.src, tab.size() * sizeof(SortSrc)));
 	HIPCHECK(c, hipMemcpyAsync(S.src.p, tab.data(), tab.size() * sizeof(SortSrc), hipMemcpyHostToDevice, c->st));
-	HIPCHECK(c, hipMemsetAsync(S.small.p, 0, SORT_SMALL_BYTES, c->st));
+	CHECK(S.small.clear(c));
 	const SortSrc *src = P<SortSrc>(S.src);
 	if (N) {
 		ProfScope ps(c, P_SORT_KEYS, N);
 		k_sort_check<<<grid_for(N, BLOCK), BLOCK, 0, c->st>>>(src, n_src, N, n_targets, w);
 		HIPCHECK(c, hipGetLastError());
 	}
-	CHECK(sort_fetch(c, S)); // (the table's host copy is read by now)
+	CHECK(S.small.fetch(c)); // (the table's host copy is read by now)
 	if (hs[SW_BAD]) { c->err = "ssv_batch_sort: a record's contig id is not below n_targets"; return SSV_E_ARG; }
 	const bool down = hs[SW_DOWN] != 0;
 	const int p_bits = bits_of(hs[SW_MAXP]), t_bits = bits_of((uint64_t)n_targets);
@@ -193,22 +187,14 @@ int ssv_batch_sort(ssv_ctx *c, ssv_batch_t *in, int64_t n_in, int32_t n_targets,
 				exclusive_scan<uint32_t, uint64_t>(c->st, P<uint32_t>(S.cig_n), P<uint64_t>(S.cig_at), count, 0ull, P<uint64_t>(c->scan_scratch64), w64 + 0);
 				exclusive_scan<uint32_t, uint64_t>(c->st, P<uint32_t>(S.seq_b), P<uint64_t>(S.seq_at), count, 0ull, P<uint64_t>(c->scan_scratch64), w64 + 1);
 				HIPCHECK(c, hipGetLastError());
-				CHECK(sort_fetch(c, S));
+				CHECK(S.small.fetch(c));
 				out_cig = hs64[0]; out_seq = hs64[1];
 				if (out_cig < (1ull << 32) || count == 1) break;
 				count = (count + 1) / 2;
 			}
-			auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-			const size_t n_out = (size_t)count;
-			const size_t sz[7] = {up(n_out * 4 + 16), up(n_out * 4 + 16), up(n_out * 2 + 16), up(n_out + 16), up(n_out * sizeof(ssv_record) + 64), up((size_t)out_cig * 4 + 64), up((size_t)out_seq + 64)};
-			size_t off[8]; off[0] = 0;
-			for (int k = 0; k < 7; ++k) off[k + 1] = off[k] + sz[k];
-			ssv_ctx::RetainArena *arena = nullptr;
-			uint8_t *slab = nullptr;
-			CHECK(retain_slab(c, off[7], &arena, &slab));
-			struct Guard { ssv_ctx::RetainArena *arena; size_t need; bool keep = false; ~Guard() { if (!keep) retain_slab_undo(arena, need); } } guard{arena, off[7]};
-			const SortDst dst{reinterpret_cast<int32_t *>(slab + off[0]), reinterpret_cast<int32_t *>(slab + off[1]), reinterpret_cast<uint16_t *>(slab + off[2]), slab + off[3],
-			                  reinterpret_cast<ssv_record *>(slab + off[4]), reinterpret_cast<uint32_t *>(slab + off[5]), slab + off[6]};
+			RetainedSlab R((size_t)count, (size_t)out_cig, (size_t)out_seq);
+			CHECK(R.take(c));
+			const RetDst dst = R.dst();
 			{
 				ProfScope ps(c, P_SORT_GATHER, count);
 				k_sort_gather<<<grid_for(count * SORT_SUB, BLOCK), BLOCK, 0, c->st>>>(src, n_src, perm, first, count, P<uint64_t>(S.cig_at), P<uint64_t>(S.seq_at), P<uint32_t>(S.seq_b), dst);
@@ -225,21 +211,15 @@ int ssv_batch_sort(ssv_ctx *c, ssv_batch_t *in, int64_t n_in, int32_t n_targets,
 				CHECK(sort_changes(c, S, dst.tid, dst.rec, count, prev_tid)); // (synchronises: the runs and their count are on the host)
 			}
 			const uint32_t nr = hs[SW_RAW_RUNS];
-			ssv_tid_run *runs = nullptr;
 			if (nr >= 1 && nr <= SORT_RAW_RUN_CAP) {
-				runs = static_cast<ssv_tid_run *>(malloc((size_t)nr * sizeof(ssv_tid_run)));
-				if (!runs) { c->err = "out of host memory (tid_runs)"; return SSV_E_NOMEM; }
+				ssv_tid_run *runs = R.new_runs(c, nr);
+				if (!runs) return SSV_E_NOMEM;
 				const TidRun *r = P<TidRun>(S.h_raw_runs);
 				for (uint32_t k = 0; k < nr; ++k) runs[k] = ssv_tid_run{(int64_t)r[k].index, r[k].tid, 0};
 				std::sort(runs, runs + nr, [](const ssv_tid_run &a, const ssv_tid_run &b) { return a.first < b.first; });
 			}
-			guard.keep = true;
 			ssv_batch_t b;
-			memset(&b, 0, sizeof(b));
-			b.n = count; b.mem = SSV_MEM_DEVICE | SSV_MEM_PERSISTENT; b.max_ref_span = span;
-			b.tid = dst.tid; b.pos = dst.pos; b.n_cigar = dst.n_cigar; b.cigar_ends = dst.ends; b.rec = dst.rec; b.cigar = dst.cigar; b.seqqual = dst.seqqual;
-			b.n_cigar_total = (int64_t)out_cig; b.seqqual_bytes = (int64_t)out_seq;
-			if (runs) { b.tid_runs = runs; b.n_tid_runs = nr; }
+			R.hand_out(&b, span);
 			made.push_back(b);
 			S.change_first.push_back((int64_t)S.change_index.size());
 			first += count;

@@ -9,10 +9,11 @@
 #include "common.h"
 #include "clip_kernels.h"
 #include "bamdec_kernels.h"
+#include "retained.h"
 
 namespace ssv {
 
-constexpr int SORT_SUB = 16;   // lanes per record in the gather
+constexpr int SORT_SUB = RET_SUB;   // lanes per record in the gather
 
 // one input batch: where its records start in the sequence of all inputs, and its arrays
 struct SortSrc {
@@ -25,20 +26,9 @@ struct SortSrc {
 	const uint8_t *seqqual;
 };
 
-// the batch that holds global record g: the last one that starts at or below g (empty batches share their start with the one behind them; src[0].start == 0)
-__device__ __forceinline__ int sort_find(const SortSrc *__restrict__ src, int n_src, int64_t g)
-{
-	int lo = 0, hi = n_src;
-	while (hi - lo > 1) {
-		const int mid = (lo + hi) >> 1;
-		if (src[mid].start <= g) lo = mid; else hi = mid;
-	}
-	return lo;
-}
-
 __device__ __forceinline__ int2 sort_pos(const SortSrc *__restrict__ src, int n_src, int64_t g)
 {
-	const int k = sort_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	const int64_t j = g - src[k].start;
 	return make_int2(src[k].tid[j], src[k].pos[j]);
 }
@@ -77,38 +67,35 @@ __global__ __launch_bounds__(BLOCK) void k_sort_keys(const SortSrc *__restrict__
 }
 
 // ---- sizes ----
-// what output record first + d takes in its batch: its operations, the bytes of its bases + qualities when it has them (packed as the decoders pack them:
-// ceil(l_qseq / 2) + l_qseq bytes, no padding between records)
+// what output record first + d takes in its batch: its operations, the bytes of its bases + qualities when it has them
 __global__ __launch_bounds__(BLOCK) void k_sort_sizes(const SortSrc *__restrict__ src, int n_src, const uint32_t *__restrict__ perm, int64_t first, int64_t count,
                                                       uint32_t *__restrict__ cig_n, uint32_t *__restrict__ seq_b)
 {
 	const int64_t d = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	if (d >= count) return;
 	const int64_t g = perm[first + d];
-	const int k = sort_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	const int64_t j = g - src[k].start;
 	const uint4 *p = reinterpret_cast<const uint4 *>(src[k].rec + j);
 	const uint4 b = p[1], e = p[3];
 	const int lq = (int)b.x > 0 ? (int)b.x : 0;
 	const bool has = ((uint64_t)e.z | ((uint64_t)e.w << 32)) != SSV_NO_SEQ;
 	cig_n[d] = (uint32_t)src[k].n_cigar[j];
-	seq_b[d] = has ? (uint32_t)((lq + 1) / 2 + lq) : 0u;
+	seq_b[d] = has ? seq_bytes(lq) : 0u;
 }
-
-struct SortDst { int32_t *tid, *pos; uint16_t *n_cigar; uint8_t *ends; ssv_record *rec; uint32_t *cigar; uint8_t *seqqual; };
 
 // ---- gather ----
 // 16 lanes per output record: the first lane the hot columns and the line (cigar_off / seq_off for the new batch, nothing else changed), all of them the
 // operations and the bytes of bases + qualities
 __global__ __launch_bounds__(BLOCK) void k_sort_gather(const SortSrc *__restrict__ src, int n_src, const uint32_t *__restrict__ perm, int64_t first, int64_t count,
-                                                       const uint64_t *__restrict__ cig_at, const uint64_t *__restrict__ seq_at, const uint32_t *__restrict__ seq_b, SortDst dst)
+                                                       const uint64_t *__restrict__ cig_at, const uint64_t *__restrict__ seq_at, const uint32_t *__restrict__ seq_b, RetDst dst)
 {
 	const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
 	const int64_t d = t / SORT_SUB;
 	const int sub = (int)(t & (SORT_SUB - 1));
 	if (d >= count) return;
 	const int64_t g = perm[first + d];
-	const int k = sort_find(src, n_src, g);
+	const int k = src_find(src, n_src, g);
 	const int64_t j = g - src[k].start;
 	const ssv_record *rec = src[k].rec;
 	const uint32_t *cigar = src[k].cigar;
@@ -116,21 +103,8 @@ __global__ __launch_bounds__(BLOCK) void k_sort_gather(const SortSrc *__restrict
 	const RecLine r = rec_load(rec, j);
 	const uint32_t coff = (uint32_t)cig_at[d], sb = seq_b[d];
 	const uint64_t soff = seq_at[d];
-	const int nc = r.n_cigar();
-	if (sub == 0) {
-		const uint64_t so = r.seq_off() != SSV_NO_SEQ ? soff : SSV_NO_SEQ;
-		dst.tid[d] = r.tid(); dst.pos[d] = r.pos(); dst.n_cigar[d] = (uint16_t)nc; dst.ends[d] = src[k].ends[j];
-		uint4 *p = reinterpret_cast<uint4 *>(dst.rec + d);
-		p[0] = make_uint4(r.w_tid, r.w_pos, r.w_fmx, r.w_nc);
-		p[1] = make_uint4(r.w_lq, r.w_mtid, r.w_mpos, r.w_isize);
-		p[2] = make_uint4(coff, r.h0, r.h1, r.h2);
-		p[3] = make_uint4(r.h3, r.h4, (uint32_t)so, (uint32_t)(so >> 32));
-	}
-	for (int q = sub; q < nc; q += SORT_SUB) dst.cigar[coff + (uint32_t)q] = r.op(cigar, q);
-	if (sb) {
-		const uint8_t *s = seqqual + r.seq_off();
-		for (uint32_t q = (uint32_t)sub; q < sb; q += SORT_SUB) dst.seqqual[soff + q] = s[q];
-	}
+	if (sub == 0) ret_write_record(dst, d, r, src[k].ends + j, r.w_fmx, coff, r.seq_off() != SSV_NO_SEQ ? soff : SSV_NO_SEQ);
+	ret_copy_parts(dst, r, cigar, seqqual, sub, coff, soff, sb);
 }
 
 // ---- contig changes among the records that are not UNMAP|MUNMAP ----
