@@ -11,7 +11,7 @@ HOST_SRC = seeksv_amd/host/bam_reader.cpp seeksv_amd/host/bam_partition.cpp seek
 HIP_SRC  = seeksv_amd/csrc/seeksv_hip.hip
 # the `seeksv` command line: its sources, and the headers only they include
 CLI_SRC  = seeksv_amd/host/seeksv_cli.cpp seeksv_amd/host/junction_stage.cpp seeksv_amd/host/readthrough_stage.cpp seeksv_amd/host/sam_text.cpp seeksv_amd/host/somatic_stage.cpp
-CLI_DEPS = seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.h
+CLI_DEPS = seeksv_amd/host/fastq_reads.h seeksv_amd/host/unmapped_pairs.h seeksv_amd/host/junction_stage.h seeksv_amd/host/readthrough_stage.h seeksv_amd/host/sam_text.h seeksv_amd/host/somatic_stage.h seeksv_amd/host/regions.h
 HIP_DEPS = $(wildcard seeksv_amd/csrc/*.h) $(wildcard seeksv_amd/csrc/*.inc) $(wildcard seeksv_amd/csrc/*.hip) include/seeksv_hip.h
 
 all: host hip synth cli primcheck
@@ -70,6 +70,7 @@ asan: $(LIBDIR)/libseeksv_hip.so
 		-L$(ASAN_DIR) -lseeksv_host -lseeksv_hip -lz -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,$(ROCM)/lib
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Iseeksv_amd/csrc tests/native/inflate_check.cpp -lz -o $(ASAN_DIR)/inflate_check && $(ASAN_DIR)/inflate_check
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/fastq_reads_check.cpp -o $(ASAN_DIR)/fastq_reads_check && $(ASAN_DIR)/fastq_reads_check
+	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/regions_check.cpp -lz -o $(ASAN_DIR)/regions_check && $(ASAN_DIR)/regions_check
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so):$$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0 SSV_CLEAN_EXIT=1 \
 		SSV_TEST_CXXFLAGS="$(ASAN_FLAGS)" SSV_LIBDIR=$(abspath $(ASAN_DIR)) SSV_ORACLE_SO=$(abspath $(ASAN_DIR))/liboracle.so SSV_CLI=$(abspath $(ASAN_DIR))/seeksv \
 		python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider

@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_pairdup_retain / ssv_pairdup_rows / ssv_pairdup_mark, ssv_pairdup_stats (`seeksv run -D`: duplicate pairs by unclipped 5' ends, any record order).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_regions_set / ssv_regions_clear / ssv_region_retain / ssv_batch_select / ssv_region_lds_capacity, ssv_region, ssv_region_info (`seeksv run -L`, `-X`: the retained records restricted to BED regions).
+                             v9 (additive, same version): ssv_pairdup_retain / ssv_pairdup_rows / ssv_pairdup_mark, ssv_pairdup_stats (`seeksv run -D`: duplicate pairs by unclipped 5' ends, any record order).
                              v9 (additive, same version): ssv_batch_sort, ssv_sorted, ssv_samdec_any_order (`seeksv run -u`: an original in any order, coordinate sorted while it is retained).
                              v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
                              v9 (additive, same version): ssv_samdec_sorted / ssv_samdec_lists (getclip, run: the original alignments as SAM text).
@@ -926,6 +927,54 @@ typedef struct {
 int ssv_pairdup_retain(ssv_ctx *ctx, const ssv_batch_t *device_batch, const ssv_names_t *names, ssv_batch_t *out);
 int ssv_pairdup_rows(ssv_ctx *ctx, const ssv_batch_t *batch, const void **dev_rows);
 int ssv_pairdup_mark(ssv_ctx *ctx, ssv_batch_t *batches, int64_t n, ssv_pairdup_stats *stats);
+
+/* ---- the records that stay resident restricted to a list of regions (v9, additive; `seeksv run -L`, `-X`, `seeksv somatic -K -L`, `-X`) ----------------
+ * THE RULE.  It follows `samtools view -L` in outline; the rule is this library's own, no external tool was run or matched.
+ *   regions     a region is (tid, s, t), 0-based half-open as in BED, 0 <= s < t.  The list that goes to the device is NORMALISED per contig by the host:
+ *               sorted by s, regions that overlap or abut merged, t clipped to the contig's length, a region left empty by the clipping dropped
+ *   interval    a record's interval is [pos, e), all of it in 64 bits: span = the sum of the lengths of its M, D, N, = and X operations, e = pos + max(span, 1).
+ *               A record without CIGAR, or whose operations consume no reference, covers one base; so does an unmapped read placed at its mate's
+ *               position.  pos == -1 gives [-1, 0), whatever the CIGAR says: it overlaps nothing
+ *   overlap     a record overlaps the list iff tid >= 0 and some region of contig tid has s < e and pos < t.  A record with tid < 0 (or tid >= n_targets)
+ *               overlaps nothing.  No flag bit takes part in the decision
+ *   include     (exclude == 0, -L) a record is kept iff it overlaps
+ *   exclude     (exclude != 0, -X) a record is kept iff it does not overlap; unplaced records stay
+ *   output      kept records keep their order and every field - hot columns, cigar_ends, the whole line with xc and cigar_head, all operations, the bases +
+ *               qualities of the records that had them (SSV_NO_SEQ stays SSV_NO_SEQ) - except cigar_off / seq_off, which are those of the output's own
+ *               arrays, packed back to back as the decoders pack them
+ * After merging, the last region of the contig with s < e decides: the record overlaps iff that region exists and its t > pos.
+ *
+ * ssv_regions_set takes the host list, already normalised (n == 0 is a valid list: -L then keeps nothing, -X everything).  A list that is not - unsorted,
+ * overlapping or abutting entries, s >= t, s < 0, tid outside [0, n_targets) - gives SSV_E_ARG and leaves the list of before.  ssv_regions_clear removes the
+ * list and gives the stage's memory back.  On the device the list is an offsets array of n_targets + 1 entries and two arrays s[], t[]; a contig's regions
+ * are staged in LDS while a tile of records stays on that contig, up to ssv_region_lds_capacity() of them, and searched in global memory otherwise.
+ *
+ * ssv_region_retain takes the place of ssv_batch_retain for a decoder's batch: *out is a retained batch (ssv_batch_release) that holds only the kept records;
+ * the input is untouched.  When every record is kept *out equals ssv_batch_retain's output part for part.
+ * ssv_batch_select takes a retained batch - of ssv_batch_retain, ssv_dup_retain, an earlier ssv_batch_sort or ssv_batch_select, or ssv_pairdup_retain AFTER
+ * ssv_pairdup_mark (before the mark its rows would be orphaned: SSV_E_ARG; anything else: SSV_E_ARG).  On success `in` is released by the call and zeroed.
+ * When every record is kept `in` is handed back as *out: the same device memory, no gather launched, info->uncopied = 1.
+ * Both: info carries the counts, the contig changes of *out among its records without UNMAP|MUNMAP (flag & 12 == 0; index inside *out, contig - the list
+ * ssv_bamdec_info.tid_run_index / tid_run_tid carries; host memory of the context's, valid until the next of these calls) and the contig of the last such
+ * record, which the caller passes back as last_tid with the next batch (0 at the start, as in the decoders).  out->n may be 0: the batch is empty and is
+ * still given back with ssv_batch_release.  max_ref_span is the input's; tid_runs are filled as ssv_batch_sort fills them.  No list set: SSV_E_STATE; a host
+ * batch or NULL arguments: SSV_E_ARG; no memory: SSV_E_NOMEM; every error leaves the input valid and the caller's.  Memory between calls: up to 15 bytes
+ * a record of the largest input and 34 bytes a kept record of temporaries, until ssv_regions_clear.  Synchronises the stream.  Timed as region_select (flags, scan,
+ * sizes, change lists) and region_gather. */
+typedef struct { int32_t tid, s, t; } ssv_region;
+typedef struct {
+	int64_t n_in, n_kept;
+	int32_t uncopied;              /* 1: ssv_batch_select handed its input back */
+	int32_t last_tid;              /* contig of the last record without UNMAP|MUNMAP so far */
+	uint32_t n_changes, pad;
+	const uint32_t *change_index;  /* record index inside *out ... */
+	const int32_t *change_tid;     /* ... and its contig */
+} ssv_region_info;
+int ssv_regions_set(ssv_ctx *ctx, const ssv_region *regions, int64_t n, int32_t n_targets, int exclude);
+int ssv_regions_clear(ssv_ctx *ctx);
+int ssv_region_lds_capacity(void);
+int ssv_region_retain(ssv_ctx *ctx, const ssv_batch_t *device_batch, int32_t last_tid, ssv_batch_t *out, ssv_region_info *info);
+int ssv_batch_select(ssv_ctx *ctx, ssv_batch_t *in, int32_t last_tid, ssv_batch_t *out, ssv_region_info *info);
 
 #ifdef __cplusplus
 }

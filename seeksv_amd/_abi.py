@@ -358,6 +358,15 @@ class Sorted(C.Structure):  # ssv_sorted
                 ("change_first", C.POINTER(C.c_int64)), ("change_index", C.POINTER(C.c_uint32)), ("change_tid", C.POINTER(C.c_int32))]
 
 
+class Region(C.Structure):  # ssv_region
+    _fields_ = [("tid", C.c_int32), ("s", C.c_int32), ("t", C.c_int32)]
+
+
+class RegionInfo(C.Structure):  # ssv_region_info
+    _fields_ = [("n_in", C.c_int64), ("n_kept", C.c_int64), ("uncopied", C.c_int32), ("last_tid", C.c_int32), ("n_changes", C.c_uint32), ("pad", C.c_uint32),
+                ("change_index", C.POINTER(C.c_uint32)), ("change_tid", C.POINTER(C.c_int32))]
+
+
 def hip_lib():
     """libseeksv_hip.so - raises when it is not built; creating a context raises when there is no GPU."""
     lib = _load("libseeksv_hip.so")
@@ -446,5 +455,9 @@ def hip_lib():
         lib.ssv_pairdup_rows.argtypes = [V, C.POINTER(Batch), C.POINTER(V)]
         lib.ssv_pairdup_rows_to_host.argtypes = [V, C.POINTER(Batch), V]
         lib.ssv_pairdup_mark.argtypes = [V, C.POINTER(Batch), C.c_int64, C.POINTER(PairdupStats)]
+        lib.ssv_regions_set.argtypes = [V, C.POINTER(Region), C.c_int64, C.c_int32, C.c_int]
+        lib.ssv_regions_clear.argtypes = [V]
+        lib.ssv_region_retain.argtypes = [V, C.POINTER(Batch), C.c_int32, C.POINTER(Batch), C.POINTER(RegionInfo)]
+        lib.ssv_batch_select.argtypes = [V, C.POINTER(Batch), C.c_int32, C.POINTER(Batch), C.POINTER(RegionInfo)]
         lib._typed = True
     return lib

@@ -350,6 +350,40 @@ class Context:
         self._check(self._lib.ssv_pairdup_mark(self._h, arr, len(batches), C.byref(st)), "ssv_pairdup_mark")
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    # ---- the retained records restricted to a list of regions (ssv_regions_set, ssv_region_retain, ssv_batch_select: `seeksv run -L`, `-X`) ----
+    def regions_set(self, regions, n_targets, exclude=False):
+        """ssv_regions_set: the list of (tid, s, t) triples, normalised as include/seeksv_hip.h says (sorted, merged, clipped), for the calls below;
+        exclude: a record is kept iff it overlaps none of them"""
+        arr = (_abi.Region * max(1, len(regions)))(*[_abi.Region(int(t), int(s), int(e)) for t, s, e in regions])
+        self._check(self._lib.ssv_regions_set(self._h, arr, len(regions), int(n_targets), int(bool(exclude))), "ssv_regions_set")
+
+    def regions_clear(self):
+        self._check(self._lib.ssv_regions_clear(self._h), "ssv_regions_clear")
+
+    def region_lds_capacity(self):
+        """how many regions of one contig the selection stages in LDS; a longer list is searched in global memory"""
+        return int(self._lib.ssv_region_lds_capacity())
+
+    @staticmethod
+    def _region_info(info):
+        return dict(n_in=int(info.n_in), n_kept=int(info.n_kept), uncopied=bool(info.uncopied), last_tid=int(info.last_tid),
+                    changes=[(int(info.change_index[j]), int(info.change_tid[j])) for j in range(info.n_changes)])
+
+    def region_retain(self, dev_batch, last_tid=0):
+        """ssv_region_retain in the place of batch_retain: the decoder's device batch -> (Batch, info): a retained batch of the records the list keeps, to be
+        given back with batch_release, and dict(n_in, n_kept, uncopied, last_tid: what to pass with the next batch, changes: the (record, contig) pairs
+        where the contig changes among the output's records without UNMAP|MUNMAP)"""
+        out, info = _abi.Batch(), _abi.RegionInfo()
+        self._check(self._lib.ssv_region_retain(self._h, C.byref(dev_batch), int(last_tid), C.byref(out), C.byref(info)), "ssv_region_retain")
+        return out, self._region_info(info)
+
+    def batch_select(self, batch, last_tid=0):
+        """ssv_batch_select: a retained batch -> (Batch, info) as region_retain.  On success the input is the call's (released, or - every record kept -
+        handed back as the output: info["uncopied"]) and zeroed; on failure it is still the caller's."""
+        out, info = _abi.Batch(), _abi.RegionInfo()
+        self._check(self._lib.ssv_batch_select(self._h, C.byref(batch), int(last_tid), C.byref(out), C.byref(info)), "ssv_batch_select")
+        return out, self._region_info(info)
+
     def samdec_any_order(self, on=True):
         """ssv_samdec_any_order, after samdec_begin: text in any record order - a chunk with more contig changes than the list holds is decoded all the same,
         without its contig-change list"""

@@ -50,6 +50,7 @@
 #include "somatic_stage.h"
 #include "unmapped_pairs.h"
 #include "fastq_reads.h"
+#include "regions.h"
 #include "../csrc/thp.h"
 #include "seeksv_hip.h"
 #include "seeksv_host.h"
@@ -189,6 +190,9 @@ static void check(ssv_ctx *ctx, int rc) { if (rc != SSV_OK) die(string("[seeksv]
 	     << "         -D                    with -K: mark duplicate pairs of the normal by the unclipped 5' ends of both reads, mates joined by read name, once all its records\n"
 	     << "                               are retained: the output of `somatic -K` on the same BAM with those flags set.  The rule and its limits: `seeksv run`'s -D.\n"
 	     << "                               Not with -M\n"
+	     << "         -L <file>             with -K: keep only the normal's records that overlap a region of this BED file, behind -M / -D and in front of every pass: the\n"
+	     << "                               output of `somatic -K` on a normal that holds the kept records.  The rule and the file's form: `seeksv run`'s -L.  Not with -X\n"
+	     << "         -X <file>             with -K: keep only the normal's records that overlap NO region of this BED file.  The rule: `seeksv run`'s -X.  Not with -L\n"
 	     << "         -t <double>           Threshold of match rate while comparing two soft-clipped reads [0.9]\n"
 	     << "         -q <int>              Minimum mapping quality of discordant read pair [20]\n"
 	     << "         -l <int>              Maximum search length to find microhomology [30]\n"
@@ -1053,6 +1057,8 @@ struct GetclipOptions {
 	bool mark_dups = false; // `run -M`, `somatic -K -M` (no option of getclip's own): duplicate read pairs are marked where the records are retained
 	bool pair_dups = false; // `run -D`, `somatic -K -D` (no option of getclip's own): duplicate pairs by the unclipped 5' ends of both reads, marked once all records are retained
 	bool sort_input = false; // `run -u` (no option of getclip's own): the input is in any order; its retained records are coordinate sorted on the GPU before any pass
+	string regions_file;     // `run -L FILE` / `-X FILE`, `somatic -K -L` / `-X` (no option of getclip's own): the records that stay resident are restricted to a BED file's regions
+	bool regions_exclude = false; // -X: a record stays iff it overlaps none of them
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1109,10 +1115,24 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	BatchSource src;
 	const bool text_input = !is_bam_name(o.bamfile);
 	// like the reference: complain about the input before anything is created (a text input's header is read here, and libbam's [samopen] line printed)
-	if (text_input) src.open_text_header(o.bamfile, "[main_samview] fail to open file for reading.");
+	// -L / -X: the BED file is read against the input's header here, so that a file that is refused leaves nothing behind
+	const bool restrict = !o.regions_file.empty() && run && run->collect;
+	const char *const restrict_opt = o.regions_exclude ? "-X" : "-L";
+	seeksv::RegionList region_list;
+	auto read_regions = [&](const ssvh_bam *header) {
+		if (!restrict) return;
+		vector<string> names;
+		vector<int32_t> lens;
+		for (int32_t t = 0, nt = ssvh_bam_n_targets(header); t < nt; ++t) { const char *nm = ssvh_bam_target_name(header, t); names.emplace_back(nm ? nm : ""); lens.push_back(ssvh_bam_target_len(header, t)); }
+		string err;
+		if (!seeksv::read_bed(o.regions_file, names, lens, region_list, &err)) die(err);
+		if (region_list.unknown) cerr << "[seeksv] " << restrict_opt << ": " << region_list.unknown << " of " << region_list.lines << " lines of " << o.regions_file << " name a contig that the input's header does not have: ignored" << endl;
+	};
+	if (text_input) { src.open_text_header(o.bamfile, "[main_samview] fail to open file for reading."); read_regions(src.bam); }
 	else {
 		ssvh_bam *probe = nullptr;
 		if (ssvh_bam_open(o.bamfile.c_str(), &probe) != 0) die("[main_samview] fail to open file for reading.");
+		read_regions(probe);
 		ssvh_bam_close(probe);
 	}
 	const bool probe_only = run && run->probe_only; // `somatic -K`, see RunSession
@@ -1237,6 +1257,39 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	vector<pair<int64_t, int32_t>> dup_pending;
 	if ((mark_dups || (o.pair_dups && run && run->collect)) && pt.on) ssv_prof_enable(ctx, 1); // (SSV_TIMING: the stage's own kernel time, below)
 	if (mark_dups) check(ctx, ssv_dup_begin(ctx));
+	// -L / -X: the list goes to the GPU once; every batch that stays passes through it directly behind retention and marking - in front of -u's sort and of every
+	// scan -, and the contig changes that the scans get are those of the kept records (the call's own list), not the decoder's
+	static const char *const kRegionNoMemory = "seeksv run: -L / -X write the kept records of a batch into memory of their own while the batch is still there: out of memory; "
+	                                           "restrict the input with `samtools view -L` and run without the option";
+	int32_t region_last_tid = 0;
+	int64_t region_in = 0, region_kept = 0;
+	if (restrict) {
+		static_assert(sizeof(seeksv::Region) == sizeof(ssv_region), "the reader's triples are the library's");
+		check(ctx, ssv_regions_set(ctx, reinterpret_cast<const ssv_region *>(region_list.regions.data()), (int64_t)region_list.regions.size(), ssvh_bam_n_targets(src.bam), o.regions_exclude ? 1 : 0));
+		if (pt.on) ssv_prof_enable(ctx, 1);
+	}
+	auto region_changes = [&](const ssv_region_info &info, vector<pair<int64_t, int32_t>> &changes) {
+		changes.clear();
+		for (uint32_t k = 0; k < info.n_changes; ++k) changes.emplace_back((int64_t)info.change_index[k], info.change_tid[k]);
+		region_last_tid = info.last_tid; region_in += info.n_in; region_kept += info.n_kept;
+	};
+	// a decoder's batch retained with the list applied (in the place of ssv_batch_retain), and a batch that is retained already restricted where it lies
+	auto region_retain = [&](const ssv_batch_t &decoded, ssv_batch_t &b, vector<pair<int64_t, int32_t>> &changes) {
+		ssv_region_info info;
+		const int rc = ssv_region_retain(ctx, &decoded, region_last_tid, &b, &info);
+		if (rc == SSV_E_NOMEM) die(probe_only ? "seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead" : kRegionNoMemory);
+		check(ctx, rc);
+		region_changes(info, changes);
+	};
+	auto region_select = [&](ssv_batch_t &b, vector<pair<int64_t, int32_t>> &changes) {
+		ssv_region_info info;
+		ssv_batch_t kept;
+		const int rc = ssv_batch_select(ctx, &b, region_last_tid, &kept, &info);
+		if (rc == SSV_E_NOMEM) die(kRegionNoMemory);
+		check(ctx, rc);
+		b = kept;
+		region_changes(info, changes);
+	};
 	// the records of a retained (or decoded) batch through the clip scan, the pass ending in front of every contig that comes back
 	auto scan_batch = [&](const ssv_batch_t &b, const vector<pair<int64_t, int32_t>> &changes) {
 		int64_t lo = 0;
@@ -1274,6 +1327,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		for (const auto &ch : changes) { const int64_t at = dup_held + ch.first; (at < b.n ? now : later).emplace_back(at < b.n ? at : at - b.n, ch.second); }
 		dup_pending.swap(later);
 		dup_held += (decoded ? decoded->n : 0) - b.n;
+		if (restrict) region_select(b, now); // (the flags are final: they came from the whole input)
 		if (b.n == 0) { check(ctx, ssv_batch_release(ctx, &b)); return; } // (a batch that is one run entirely: its records come with a later one)
 		run->batches.push_back(b);
 		scan_batch(b, now);
@@ -1315,6 +1369,13 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		}
 		if (sort_input) { // -u: the batch is only kept; every pass waits for the sort
 			ssv_batch_t b;
+			if (restrict) { // (the sort sees the kept records only)
+				vector<pair<int64_t, int32_t>> unused;
+				region_retain(decoded, b, unused);
+				if (b.n == 0) check(ctx, ssv_batch_release(ctx, &b)); else unsorted.push_back(b);
+				pt.lap("gpu_retain+regions(wait h2d+kernels)");
+				return;
+			}
 			const int rc = ssv_batch_retain(ctx, &decoded, &b);
 			if (rc == SSV_E_NOMEM) die(kSortNoMemory);
 			check(ctx, rc);
@@ -1329,6 +1390,14 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			return;
 		}
 		ssv_batch_t b = decoded;
+		if (restrict) { // -L / -X: only the kept records stay, and the scan gets their contig changes
+			region_retain(decoded, b, changes_of.front());
+			if (b.n == 0) check(ctx, ssv_batch_release(ctx, &b));
+			else { run->batches.push_back(b); scan_batch(b, changes_of.front()); }
+			changes_of.pop_front();
+			pt.lap("gpu_regions+scan(wait h2d+kernels)");
+			return;
+		}
 		if (run && run->collect) { // `seeksv run`: the batch stays in HBM for the getsv passes
 			const int rc = ssv_batch_retain(ctx, &decoded, &b);
 			if (rc == SSV_E_NOMEM && probe_only)
@@ -1375,11 +1444,22 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 				cerr << ' ' << groups[k] << ' ' << ms << " ms in " << launches << " launches" << (k == 2 ? ";" : ",");
 			}
 			cerr << " resident at the peak beside the records: " << 24 * ps.records << " bytes of rows, " << 8 * ps.records + 32 * ps.taking_part + 32 * ps.pairs << " bytes of keys and indices)" << endl;
-			ssv_prof_enable(ctx, 0);
+			ssv_prof_enable(ctx, restrict ? 1 : 0); // (-L / -X: the selects below are timed too)
+		}
+		if (restrict && sort_input) { // (the marked batches, restricted in front of the sort)
+			vector<ssv_batch_t> still;
+			vector<pair<int64_t, int32_t>> unused;
+			for (ssv_batch_t &b : unsorted) {
+				region_select(b, unused);
+				if (b.n == 0) check(ctx, ssv_batch_release(ctx, &b)); else still.push_back(b);
+			}
+			unsorted.swap(still);
+			pt.lap("gpu_regions");
 		}
 		if (!sort_input) {
 			for (size_t k = 0; k < pd_batches.size(); ++k) {
 				ssv_batch_t b = pd_batches[k];
+				if (restrict) region_select(b, pd_changes[k]);
 				if (b.n == 0) { check(ctx, ssv_batch_release(ctx, &b)); continue; }
 				run->batches.push_back(b);
 				scan_batch(b, pd_changes[k]);
@@ -1389,7 +1469,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		}
 	}
 	if (sort_input) { // -u: one sort of everything that was kept; then the passes see the batches as they would have come from a sorted file
-		if (pt.on) { ssv_prof_enable(ctx, 1); ssv_prof_reset(ctx); }
+		if (pt.on) { ssv_prof_enable(ctx, 1); if (!restrict) ssv_prof_reset(ctx); } // (-L / -X: the region groups' time so far stays; the sort's groups are its own)
 		const size_t n_unsorted = unsorted.size();
 		auto resident = [](const ssv_batch_t *b, int64_t n) { // hot columns, cigar_ends, lines, operations, bases + qualities
 			int64_t bytes = 0;
@@ -1426,6 +1506,20 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 			scan_batch(b, changes);
 			pt.lap("gpu_scan(wait kernels)");
 		}
+	}
+	if (restrict) {
+		cerr << "[seeksv] " << restrict_opt << ": kept " << region_kept << " of " << region_in << " records (" << region_list.regions.size() << " regions on " << region_list.contigs << " contigs)" << endl;
+		if (pt.on) {
+			cerr << "[timing] (" << restrict_opt << " kernel time:";
+			const char *const groups[2] = {"region_select", "region_gather"};
+			for (int k = 0; k < 2; ++k) {
+				double ms = 0; int64_t launches = 0;
+				ssv_prof_get(ctx, groups[k], &ms, &launches, nullptr);
+				cerr << ' ' << groups[k] << ' ' << ms << " ms in " << launches << " launches" << (k == 1 ? ")" : ",");
+			}
+			cerr << endl;
+		}
+		check(ctx, ssv_regions_clear(ctx)); // (the stage's memory goes back in front of the passes that follow)
 	}
 	pass_flushes.push_back(scan_last_tid);
 	emit_pass(true);
@@ -2222,6 +2316,7 @@ struct SomaticOptions {
 	string normal_bam_file, clipped_file, tumor_file, somatic_file;
 	bool mark_dups = false; // -M (with -K): duplicate read pairs of the normal are marked where its records are retained
 	bool pair_dups = false; // -D (with -K): ... by the unclipped 5' ends of both reads, once all its records are retained
+	string include_file, exclude_file; // -L / -X (with -K): the normal's retained records are restricted to a BED file's regions
 	bool from_bam = false; // -K: no clip.gz - the normal's clusters come from its BAM, and the look-ups run on the GPU where the clusters lie
 	GetclipOptions clip;   // -K: the clip pass's options (-c: getclip's -t / -q / -s; the defaults are getclip's)
 };
@@ -2233,7 +2328,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	optind = 0;
 	string clip_opts;
 	bool clip_opts_given = false;
-	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:MD")) >= 0) {
+	while ((c = getopt(argc, argv, "t:q:l:m:n:G:J:ZCN:Kc:MDL:X:")) >= 0) {
 		switch (c) {
 		case 't': o.min_map_rate = atof(optarg); break;
 		case 'q': o.min_mapQ = atoi(optarg); break;
@@ -2248,6 +2343,8 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 		case 'K': o.from_bam = true; break;
 		case 'M': o.mark_dups = true; break;
 		case 'D': o.pair_dups = true; break;
+		case 'L': o.include_file = optarg; break;
+		case 'X': o.exclude_file = optarg; break;
 		case 'c': clip_opts = optarg; clip_opts_given = true; break;
 		}
 	}
@@ -2255,6 +2352,9 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	if (o.mark_dups && !o.from_bam) die("seeksv somatic: -M marks duplicates where the clip pass of -K retains the normal's records; without -K there is no such pass");
 	if (o.pair_dups && !o.from_bam) die("seeksv somatic: -D marks duplicate pairs once the clip pass of -K has retained the normal's records; without -K there is no such pass");
 	if (o.pair_dups && o.mark_dups) die("seeksv somatic: -D and -M are two rules for the one duplicate flag; -M is not supported with -D");
+	if ((!o.include_file.empty() || !o.exclude_file.empty()) && !o.from_bam)
+		die("seeksv somatic: -L and -X restrict the records that the clip pass of -K retains; without -K there is no such pass");
+	if (!o.include_file.empty() && !o.exclude_file.empty()) die("seeksv somatic: -L keeps the records inside its regions and -X those outside; -X is not supported with -L");
 	if (clip_opts_given && !o.from_bam) die("seeksv somatic: -c hands getclip's options to the clip pass of -K; without -K there is no such pass");
 	if (argc != optind + (o.from_bam ? 3 : 4)) { cerr << argc << '\t' << optind << endl; usage_somatic(); }
 	else if (o.offset >= 90 || o.offset < 0) { cerr << "Error: value of -l must in range [0, 90) " << endl; usage_somatic(); }
@@ -2270,6 +2370,7 @@ static SomaticOptions parse_somatic(int argc, char **argv)
 	o.clip.bamfile = o.normal_bam_file; o.clip.device = o.device; o.clip.devices = vector<int>(1, o.device); o.clip.n_ranks = 1;
 	o.clip.device_inflate = true; // (as `seeksv run`: decoded on the GPU, where the records stay)
 	o.clip.mark_dups = o.mark_dups; o.clip.pair_dups = o.pair_dups;
+	o.clip.regions_file = o.include_file.empty() ? o.exclude_file : o.include_file; o.clip.regions_exclude = o.include_file.empty() && !o.exclude_file.empty();
 	if (o.verify_crc) o.clip.verify_crc = true;
 	return o;
 }
@@ -3153,6 +3254,16 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               sorter was matched).  Every file and stdout are what `seeksv run` writes for the same records in that order, except\n"
 	     << "                               prefix.unmapped_[12].fq.gz, which hold the same pairs in input order.  The sample is resident twice while it is sorted\n"
 	     << "                               (2 x 80 bytes a record).  Not with -N above 1, -P or -M, and not inside -c or -v\n"
+	     << "         -L <file>             keep only the records that overlap a region of this BED file (chrom, start, end, tab separated, 0-based half-open; plain text, or\n"
+	     << "                               gzip when the name ends in .gz; further columns, empty lines and lines starting with #, track or browser are ignored; a contig\n"
+	     << "                               that the input's header does not have is ignored and counted on stderr).  A record's interval is [pos, pos + max(reference\n"
+	     << "                               span, 1)): a record without CIGAR and an unmapped read placed at its mate's position cover one base; no flag takes part;\n"
+	     << "                               unplaced records overlap nothing.  The restriction runs on the GPU where the records are retained - behind -M / -D, whose flags\n"
+	     << "                               come from the WHOLE input, in front of -u's sort and of every pass: every file and stdout are those of `seeksv run` on a file\n"
+	     << "                               that holds the kept records with those flags - except prefix.unmapped_[12].fq.gz, which are not restricted.  After\n"
+	     << "                               `samtools view -L` in outline; this program's own rule, no external tool was matched.  Not with -X or -N above 1, not inside -c\n"
+	     << "         -X <file>             the same with the rule turned round: keep only the records that overlap NO region of the file (an exclude list: centromeres,\n"
+	     << "                               decoys, blacklists); unplaced records stay.  Not with -L or -N above 1, not inside -c or -v\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
 	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
 	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
@@ -3166,12 +3277,15 @@ static int cmd_run(int argc, char **argv)
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
 	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuD")) >= 0) {
+	string include_file, exclude_file;
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuDL:X:")) >= 0) {
 		switch (c) {
 		case 'P': split = true; break;
 		case 'M': mark_dups = true; break;
 		case 'u': unsorted = true; break;
 		case 'D': pair_dups = true; break;
+		case 'L': include_file = optarg; break;
+		case 'X': exclude_file = optarg; break;
 		case 'c': clip_opts = optarg; break;
 		case 'v': sv_opts = optarg; break;
 		case 'a': aln_opts = optarg; break;
@@ -3190,7 +3304,12 @@ static int cmd_run(int argc, char **argv)
 	// -u is run's own: refused inside -c / -v with its reason, not with the steps' usage texts
 	for (const string *words : {&clip_opts, &sv_opts}) {
 		std::istringstream in(*words);
-		for (string w; in >> w;) if (w == "-u") die("seeksv run: -u sorts the records that this run keeps, once, for all its steps; -u inside -c or -v is not supported");
+		for (string w; in >> w;) {
+			if (w == "-u") die("seeksv run: -u sorts the records that this run keeps, once, for all its steps; -u inside -c or -v is not supported");
+			// -L / -X are run's own too (inside -v, -L is getsv's flank length as before)
+			if (w == "-X" || (w == "-L" && words == &clip_opts))
+				die("seeksv run: -L and -X restrict the records that this run keeps, once, for all its steps; " + w + " inside -c or -v is not supported");
+		}
 	}
 	const RealignOptions aln = parse_words("realign", aln_opts, parse_realign);
 	if (aln.gpu_given) die("seeksv run: the GPU is chosen by run's own -G, not inside -a");
@@ -3213,6 +3332,10 @@ static int cmd_run(int argc, char **argv)
 	if (pair_dups && mark_dups) die("seeksv run: -D and -M are two rules for the one duplicate flag; -M is not supported with -D");
 	if (pair_dups && ranked) die("seeksv run: -D joins mates by name among the records that one GPU keeps; -N above 1 is not supported with it");
 	if (pair_dups && split) die("seeksv run: -D defers every pass behind the whole decode, -P's pass among them; -P is not supported with it");
+	// -L / -X: one list, applied where one GPU retains the records
+	if (!include_file.empty() && !exclude_file.empty()) die("seeksv run: -L keeps the records inside its regions and -X those outside; -X is not supported with -L");
+	if ((!include_file.empty() || !exclude_file.empty()) && ranked)
+		die(string("seeksv run: ") + (include_file.empty() ? "-X" : "-L") + " restricts the records that one GPU keeps; -N above 1 is not supported with it");
 	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
 	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
 		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
@@ -3221,6 +3344,7 @@ static int cmd_run(int argc, char **argv)
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
 	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted; clip.pair_dups = pair_dups;
+	clip.regions_file = include_file.empty() ? exclude_file : include_file; clip.regions_exclude = include_file.empty() && !exclude_file.empty();
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
 
