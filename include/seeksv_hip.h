@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_regions_set / ssv_regions_clear / ssv_region_retain / ssv_batch_select / ssv_region_lds_capacity, ssv_region, ssv_region_info (`seeksv run -L`, `-X`: the retained records restricted to BED regions).
+#define SSV_ABI_VERSION 9 /* v9 (additive, same version): ssv_rt_begin_original / ssv_rt_original_stats, ssv_rt_original_counts (`seeksv run -A`: junctions from the input's own supplementary alignments).
+                             v9 (additive, same version): ssv_regions_set / ssv_regions_clear / ssv_region_retain / ssv_batch_select / ssv_region_lds_capacity, ssv_region, ssv_region_info (`seeksv run -L`, `-X`: the retained records restricted to BED regions).
                              v9 (additive, same version): ssv_pairdup_retain / ssv_pairdup_rows / ssv_pairdup_mark, ssv_pairdup_stats (`seeksv run -D`: duplicate pairs by unclipped 5' ends, any record order).
                              v9 (additive, same version): ssv_batch_sort, ssv_sorted, ssv_samdec_any_order (`seeksv run -u`: an original in any order, coordinate sorted while it is retained).
                              v9 (additive, same version): ssv_dup_begin / ssv_dup_retain / ssv_dup_finish, ssv_dup_stats (`seeksv run -M`: duplicate read pairs marked while the sample is retained).
@@ -805,6 +806,59 @@ typedef struct {
 int ssv_rt_begin(ssv_ctx *ctx, const ssv_rt_params *p);
 int ssv_rt_scan(ssv_ctx *ctx, const ssv_batch_t *b, const ssv_names_t *names);
 int ssv_rt_finish(ssv_ctx *ctx, ssv_rt_result *out);
+
+/* ---- run -A: junctions from the supplementary alignments of the original itself (v9, additive) --------------------------------------------
+ * ssv_rt_begin_original opens the session of ssv_rt_begin in another mode: ssv_rt_scan, ssv_rt_finish, ssv_rt_pair and ssv_rt_result are the same calls
+ * with the same rows, and a session opened with ssv_rt_begin behaves byte for byte as before.  The batches are the ORIGINAL's (an aligner's output: a read
+ * that spans a breakpoint is a primary record plus a supplementary record, flag 2048, each clipped on one side) in input order, decoded in the decoders'
+ * default form (keep_all_seq == 0 ships the bases of every record with S at an end, which is every record that carries the read).  The rule is this
+ * project's own: FindJunction's geometry, kept byte for byte, with a selection and a key of its own.
+ *
+ * A record takes part when all of these hold:
+ *   - it has a CIGAR;
+ *   - tid is a contig of the header;
+ *   - mapq >= min_mapq;
+ *   - none of 0x4, 0x100, 0x400 is set, as the input has them;
+ *   - exactly one of its two ends is clipped.  An end is clipped when its outermost operation is S or H.
+ * S..S, H..S, H..H and records with no clipped end are not taken, 10I90M and 100= included (FindJunction sends those last two through its 3' branch).
+ *
+ * Lengths come from the CIGAR alone:
+ *   - R is the sum of M I S = X H;
+ *   - the clip length of the clipped end is the sum of the run of S / H operations at that end (5H10S85M: 15);
+ *   - a 5' clipped record (first operation a clip): side '5', left = clip, right = R - left, pos = pos0 + 1;
+ *   - otherwise: side '3', right = clip, left = R - right, pos = pos0 + ref_len, with GenerateCigar's ref_len (M D = N, not X).
+ *
+ * A record carries the read when it has no H, its bases are present (seq_off != SSV_NO_SEQ) and l_qseq == R.
+ *
+ * The key is (read name, flag & 0xC0) in the place of the read name alone: mates never meet; single-end reads have 0 there.
+ *
+ * Hold / pair / drop runs in input order per key, as for ssv_rt_begin.  A held A and a new B pair when all of these hold, looked at in this order:
+ *   - same strand and different sides, or opposite strands and the same side;
+ *   - R_A == R_B (else B counts as dropped_length);
+ *   - at least one of the two carries the read (else B counts as dropped_no_carrier).
+ * Otherwise B is dropped and A stays held.
+ *
+ * Junction, microhomology, kind, clipped lengths, CIGAR sources and edits are ssv_rt_begin's case analysis unchanged.  The two seqs are the slices
+ * (source record, begin, len, rc) that case analysis names; when the source carries the read they are read as for ssv_rt_begin, when it does not the
+ * same bases are read from its partner: (begin, len, rc) on the same strand, (R - begin - len, len, !rc) on opposite strands.  Complementing swaps
+ * A C G T only.  A record whose R is above 2^30 never pairs.
+ *
+ * What the pass does not see: marks made later (-M / -D), a restriction (-L / -X), a sort (-u: it runs in input order, which matters only for
+ * opposite-strand pairs at equal (contig, position), where the completing record is up, and for keys with more than two candidates).  A read of three
+ * or more pieces gives what hold / pair / drop gives: no chaining.
+ * Errors as ssv_rt_begin's; calls out of sequence: SSV_E_STATE.  ssv_rt_original_stats: the counts of the last finished session of this mode
+ * (SSV_E_STATE before one has finished, after a session of the other mode, or after the next begin). */
+typedef struct {
+	int64_t candidates;          /* records that took part */
+	int64_t hard_clipped;        /* ... of which with an H */
+	int64_t pairs;
+	int64_t pairs_borrowed;      /* pairs of which a seq was read from the partner of its source */
+	int64_t dropped_no_carrier;  /* records dropped at the pairing because neither record carried the read */
+	int64_t dropped_length;      /* records dropped at the pairing because R_A != R_B */
+	int64_t store_bytes;         /* device memory the candidates took at the finish: lines, hashes, names, bases and operations */
+} ssv_rt_original_counts; /* (a typedef and a function cannot share a name in C) */
+int ssv_rt_begin_original(ssv_ctx *ctx, const ssv_rt_params *p);
+int ssv_rt_original_stats(ssv_ctx *ctx, ssv_rt_original_counts *out);
 
 /* ---- duplicate read pairs marked while the sample is retained (v9, additive; `seeksv run -M`, `seeksv somatic -K -M`) ----------------------
  * Every pass honours the duplicate flag 0x400; this stage sets it, in the retained copy only, before any pass reads a flag.  The rule is this library's own (it

@@ -191,6 +191,10 @@ class RtResult(C.Structure):
     _fields_ = [("n_pairs", C.c_int64), ("n_candidates", C.c_int64), ("pairs", C.POINTER(RtPair)), ("seqs", C.c_void_p), ("cigars", C.POINTER(C.c_uint32))]
 
 
+class RtOriginalCounts(C.Structure):  # ssv_rt_original_counts
+    _fields_ = [(k, C.c_int64) for k in ("candidates", "hard_clipped", "pairs", "pairs_borrowed", "dropped_no_carrier", "dropped_length", "store_bytes")]
+
+
 def make_batch(arrays, mem=MEM_HOST, n=None):
     """Build an ssv_batch_t over numpy arrays (host) or raw device pointers (ints). Returns (Batch, keepalive)."""
     b = Batch()
@@ -435,6 +439,8 @@ def hip_lib():
         lib.ssv_rt_begin.argtypes = [V, C.POINTER(RtParams)]
         lib.ssv_rt_scan.argtypes = [V, C.POINTER(Batch), C.POINTER(Names)]
         lib.ssv_rt_finish.argtypes = [V, C.POINTER(RtResult)]
+        lib.ssv_rt_begin_original.argtypes = [V, C.POINTER(RtParams)]
+        lib.ssv_rt_original_stats.argtypes = [V, C.POINTER(RtOriginalCounts)]
         lib.ssv_samdec_begin.argtypes = [V, C.POINTER(SamdecParams)]
         lib.ssv_samdec_prefetch.argtypes = [V, V, C.c_size_t]
         lib.ssv_samdec_decode.argtypes = [V, V, C.c_size_t, C.c_int, C.c_int, C.POINTER(Batch)]

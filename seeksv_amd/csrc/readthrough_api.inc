@@ -1,4 +1,5 @@
-// readthrough_api.inc - C ABI of `getsv -F` (FindJunction, process_bwasw.cpp:5-227); included by seeksv_hip.hip, kernels in readthrough_kernels.h
+// readthrough_api.inc - C ABI of `getsv -F` (FindJunction, process_bwasw.cpp:5-227) and of `run -A` (the same session over the original's own split reads:
+// ssv_rt_begin_original); included by seeksv_hip.hip, kernels in readthrough_kernels.h and splitread_kernels.h
 
 static_assert(sizeof(ssv::RtPairOut) == sizeof(ssv_rt_pair), "RtPairOut is the ABI line");
 
@@ -7,6 +8,10 @@ struct ssv_rt_state {
 	int32_t min_mapq = 1, n_targets = 0;
 	uint64_t hash_mask = ~0ull;
 	int hash_bits = 64;
+	bool original = false;                 // ssv_rt_begin_original: the split-read rule (splitread_kernels.h) in the place of FindJunction's selection and key
+	bool stats_valid = false;              // a session of that mode has finished
+	ssv_rt_original_counts stats{};
+	DBuf ostats;                           // that mode's device counters (SR_N_*), zeroed at begin
 	uint64_t rec_base = 0;                 // records scanned so far (file order)
 	int64_t n_cand = 0;                    // candidates gathered so far
 	uint64_t name_used = 0, seq_used = 0, cig_used = 0;
@@ -16,14 +21,19 @@ struct ssv_rt_state {
 	HBuf h_small, h_pairs, h_seqs, h_cigs;
 };
 
-int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p)
+static int rt_begin(ssv_ctx *c, const ssv_rt_params *p, bool original)
 {
 	if (!c) return SSV_E_ARG;
-	if (!p || p->n_targets < 0 || (p->n_targets > 0 && !p->name_rank)) { c->err = "ssv_rt_begin: bad parameters"; return SSV_E_ARG; }
+	if (!p || p->n_targets < 0 || (p->n_targets > 0 && !p->name_rank)) { c->err = original ? "ssv_rt_begin_original: bad parameters" : "ssv_rt_begin: bad parameters"; return SSV_E_ARG; }
 	HIPCHECK(c, hipSetDevice(c->device));
 	if (!c->rt) c->rt.reset(new ssv_rt_state());
 	ssv_rt_state &R = *c->rt;
 	R.phase = ssv_rt_state::IDLE;
+	R.original = original; R.stats_valid = false;
+	if (original) {
+		CHECK(ensure(c, R.ostats, SR_N_STATS * 8));
+		HIPCHECK(c, hipMemsetAsync(R.ostats.p, 0, SR_N_STATS * 8, c->st));
+	}
 	R.min_mapq = p->min_mapq; R.n_targets = p->n_targets;
 	// SSV_RT_HASH_BITS (tests): the name hash cut to its low bits, so that names collide and the exact path runs
 	R.hash_mask = env_low_bits_mask("SSV_RT_HASH_BITS", &R.hash_bits);
@@ -33,6 +43,18 @@ int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p)
 	CHECK(ensure(c, R.small, 256)); CHECK(ensure_host(c, R.h_small, 256));
 	HIPCHECK(c, hipStreamSynchronize(c->st));
 	R.phase = ssv_rt_state::SCANNING;
+	return SSV_OK;
+}
+
+int ssv_rt_begin(ssv_ctx *c, const ssv_rt_params *p) { return rt_begin(c, p, false); }
+int ssv_rt_begin_original(ssv_ctx *c, const ssv_rt_params *p) { return rt_begin(c, p, true); }
+
+int ssv_rt_original_stats(ssv_ctx *c, ssv_rt_original_counts *out)
+{
+	if (!c) return SSV_E_ARG;
+	if (!c->rt || !c->rt->stats_valid || c->rt->phase != ssv_rt_state::FINISHED) { c->err = "ssv_rt_original_stats without a finished ssv_rt_begin_original session"; return SSV_E_STATE; }
+	if (!out) { c->err = "ssv_rt_original_stats: no result"; return SSV_E_ARG; }
+	*out = c->rt->stats;
 	return SSV_OK;
 }
 
@@ -48,7 +70,7 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 	CHECK(stage_batch(c, b, d));
 	const int64_t n = d.n;
 	if (n == 0) return SSV_OK;
-	ProfScope ps(c, P_RT_SCAN, n);
+	ProfScope ps(c, R.original ? P_SPLITREAD_SCAN : P_RT_SCAN, n);
 	CHECK(staged_ends(c, d));
 	DevNames names;
 	CHECK(stage_names(c, nm, n, R.hnames, R.hoff, names));
@@ -57,7 +79,8 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 	CHECK(ensure(c, c->scan_scratch, scan_scratch_elems(n) * 4)); CHECK(ensure(c, c->scan_scratch64, scan_scratch_elems(n) * 8));
 	uint32_t *sm = P<uint32_t>(R.small);
 	HIPCHECK(c, hipMemsetAsync(R.small.p, 0, 256, c->st));
-	k_rt_select<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, R.min_mapq, R.n_targets, P<uint32_t>(R.keep));
+	if (R.original) k_sr_select<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, R.min_mapq, R.n_targets, P<uint32_t>(R.keep));
+	else k_rt_select<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(d, R.min_mapq, R.n_targets, P<uint32_t>(R.keep));
 	exclusive_scan<uint32_t, uint32_t>(c->st, P<uint32_t>(R.keep), P<uint32_t>(R.at), n, 0u, P<uint32_t>(c->scan_scratch), sm);
 	k_rt_place<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.keep), P<uint32_t>(R.at), n, P<uint32_t>(R.cand));
 	HIPCHECK(c, hipGetLastError());
@@ -71,8 +94,10 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 		CHECK(ensure(c, R.nbytes, M1 * 8)); CHECK(ensure(c, R.sbytes, M1 * 8)); CHECK(ensure(c, R.cops, M1 * 8));
 		CHECK(ensure(c, R.hash, (size_t)(R.n_cand + m) * 8 + 16, true, (size_t)R.n_cand * 8));
 		CHECK(ensure(c, R.cands, (size_t)(R.n_cand + m) * sizeof(RtCand) + 64, true, (size_t)R.n_cand * sizeof(RtCand)));
-		k_rt_measure<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.hash_mask, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
-		                                                      P<uint64_t>(R.hash) + R.n_cand, sm + 8);
+		if (R.original) k_sr_measure<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.hash_mask, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                                      P<uint64_t>(R.hash) + R.n_cand); // (a record without its bases does not carry the read: sm[8] stays 0)
+		else k_rt_measure<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.hash_mask, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                           P<uint64_t>(R.hash) + R.n_cand, sm + 8);
 		HIPCHECK(c, hipGetLastError());
 		exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.nbytes), P<uint64_t>(R.nbytes), m, (uint64_t)R.name_used, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.nbytes) + m);
 		exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.sbytes), P<uint64_t>(R.sbytes), m, (uint64_t)R.seq_used, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.sbytes) + m);
@@ -87,8 +112,11 @@ int ssv_rt_scan(ssv_ctx *c, const ssv_batch_t *b, const ssv_names_t *nm)
 		CHECK(ensure(c, R.names, name_end + 16, true, R.name_used));
 		CHECK(ensure(c, R.seqs, seq_end + 16, true, R.seq_used));
 		CHECK(ensure(c, R.cigs, cig_end * 4 + 16, true, R.cig_used * 4));
-		k_rt_gather<<<grid_for(m, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.rec_base, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
-		                                                               P<RtCand>(R.cands) + R.n_cand, P<char>(R.names), P<uint8_t>(R.seqs), P<uint32_t>(R.cigs));
+		if (R.original) k_sr_gather<<<grid_for(m, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.rec_base, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                                               P<RtCand>(R.cands) + R.n_cand, P<char>(R.names), P<uint8_t>(R.seqs), P<uint32_t>(R.cigs),
+		                                                                               P<unsigned long long>(R.ostats));
+		else k_rt_gather<<<grid_for(m, WAVES_PER_BLOCK), BLOCK, 0, c->st>>>(d, names, P<uint32_t>(R.cand), m, R.rec_base, P<uint64_t>(R.nbytes), P<uint64_t>(R.sbytes), P<uint64_t>(R.cops),
+		                                                                    P<RtCand>(R.cands) + R.n_cand, P<char>(R.names), P<uint8_t>(R.seqs), P<uint32_t>(R.cigs));
 		HIPCHECK(c, hipGetLastError());
 		R.n_cand += m; R.name_used = name_end; R.seq_used = seq_end; R.cig_used = cig_end;
 	}
@@ -113,8 +141,21 @@ static int rt_finish(ssv_ctx *c, ssv_rt_result *out);
 
 int ssv_rt_finish(ssv_ctx *c, ssv_rt_result *out)
 {
-	const int rc = rt_finish(c, out);
-	if (c && c->rt && c->rt->phase == ssv_rt_state::FINISHED) rt_release_store(c);
+	int rc = rt_finish(c, out);
+	if (c && c->rt && c->rt->phase == ssv_rt_state::FINISHED) {
+		ssv_rt_state &R = *c->rt;
+		if (R.original && rc == SSV_OK) { // the session's counts (ssv_rt_original_stats)
+			unsigned long long h[SR_N_STATS];
+			if (hipMemcpyAsync(h, R.ostats.p, sizeof(h), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) { c->err = "ssv_rt_finish: the counts did not come back"; rc = SSV_E_HIP; }
+			else {
+				R.stats.candidates = out->n_candidates; R.stats.hard_clipped = (int64_t)h[SR_N_HARD]; R.stats.pairs = out->n_pairs; R.stats.pairs_borrowed = (int64_t)h[SR_N_BORROWED];
+				R.stats.dropped_no_carrier = (int64_t)h[SR_N_NO_CARRIER]; R.stats.dropped_length = (int64_t)h[SR_N_LENGTH];
+				R.stats.store_bytes = (int64_t)(R.n_cand * (int64_t)(sizeof(RtCand) + 8) + (int64_t)R.name_used + (int64_t)R.seq_used + (int64_t)R.cig_used * 4);
+				R.stats_valid = true;
+			}
+		}
+		rt_release_store(c);
+	}
 	return rc;
 }
 
@@ -130,7 +171,7 @@ static int rt_finish(ssv_ctx *c, ssv_rt_result *out)
 	out->n_candidates = n;
 	R.phase = ssv_rt_state::FINISHED;
 	if (n == 0) return SSV_OK;
-	ProfScope ps(c, P_RT_FINISH, n);
+	ProfScope ps(c, R.original ? P_SPLITREAD_FINISH : P_RT_FINISH, n);
 	// ---- pair: stable sort of (hash, candidate) - candidates are in file order - then one lane per run of equal hashes ----
 	const size_t N = (size_t)n;
 	CHECK(ensure(c, R.keys[0], N * 8 + 16)); CHECK(ensure(c, R.keys[1], N * 8 + 16)); CHECK(ensure(c, R.vals[0], N * 4 + 16)); CHECK(ensure(c, R.vals[1], N * 4 + 16));
@@ -143,7 +184,8 @@ static int rt_finish(ssv_ctx *c, ssv_rt_result *out)
 	const int cur = radix_sort_pairs(c->st, kp, vp, n, (R.hash_bits + 7) / 8 * 8, P<uint32_t>(c->ghist), P<uint32_t>(c->scan_scratch));
 	CHECK(ensure(c, R.held, N * 4 + 16)); CHECK(ensure(c, R.partner, N * 4 + 16));
 	HIPCHECK(c, hipMemsetAsync(R.partner.p, 0xff, N * 4, c->st));
-	k_rt_pair<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(kp[cur], vp[cur], n, P<RtCand>(R.cands), P<char>(R.names), P<int32_t>(R.held), P<int32_t>(R.partner));
+	if (R.original) k_sr_pair<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(kp[cur], vp[cur], n, P<RtCand>(R.cands), P<char>(R.names), P<int32_t>(R.held), P<int32_t>(R.partner), P<unsigned long long>(R.ostats));
+	else k_rt_pair<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(kp[cur], vp[cur], n, P<RtCand>(R.cands), P<char>(R.names), P<int32_t>(R.held), P<int32_t>(R.partner));
 	HIPCHECK(c, hipGetLastError());
 	// ---- pair events in the order of their completing record ----
 	CHECK(ensure(c, R.ev_flag, N * 4 + 16)); CHECK(ensure(c, R.ev_at, N * 4 + 16)); CHECK(ensure(c, R.ev_b, N * 4 + 16));
@@ -165,6 +207,7 @@ static int rt_finish(ssv_ctx *c, ssv_rt_result *out)
 	CHECK(ensure(c, R.pseq, M1 * 8)); CHECK(ensure(c, R.pcig, M1 * 8));
 	k_rt_keys<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.ev_b), P<int32_t>(R.partner), m, P<RtCand>(R.cands), P<int32_t>(R.rank), P<RtPairOut>(R.pairs),
 	                                                   P<RtSlice>(R.slices), P<uint32_t>(R.cig_src), P<uint64_t>(R.pseq), P<uint64_t>(R.pcig));
+	if (R.original) k_sr_borrow<<<grid_for(m, BLOCK), BLOCK, 0, c->st>>>(P<uint32_t>(R.ev_b), P<int32_t>(R.partner), m, P<RtCand>(R.cands), P<RtSlice>(R.slices), P<unsigned long long>(R.ostats));
 	HIPCHECK(c, hipGetLastError());
 	exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.pseq), P<uint64_t>(R.pseq), m, 0ull, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.pseq) + m);
 	exclusive_scan<uint64_t, uint64_t>(c->st, P<uint64_t>(R.pcig), P<uint64_t>(R.pcig), m, 0ull, P<uint64_t>(c->scan_scratch64), P<uint64_t>(R.pcig) + m);

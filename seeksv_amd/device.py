@@ -89,7 +89,27 @@ class Context:
         out = self.rt_decode(r, target_names)
         return (out, r.n_candidates) if raw else out
 
-    def rt_begin(self, min_mapq=1, target_names=()):
+    def readthrough_original(self, batches, names, min_mapq=1, target_names=(), raw=False):
+        """readthrough() under the split-read rule of `run -A` (ssv_rt_begin_original, include/seeksv_hip.h): the batches are an aligner's output in
+        input order - primary + supplementary records, hard clips allowed, pairs keyed by (name, flag & 0xC0).  Same rows as readthrough();
+        raw: (rows, rt_original_stats())."""
+        self.rt_begin_original(min_mapq, target_names)
+        for b, nm in zip(batches, names):
+            self.rt_scan(b, nm)
+        out = self.rt_decode(self.rt_finish(), target_names)
+        return (out, self.rt_original_stats()) if raw else out
+
+    def rt_begin_original(self, min_mapq=1, target_names=()):
+        """ssv_rt_begin_original: rt_begin() for a session under the split-read rule; rt_scan / rt_finish / rt_decode as they are"""
+        self.rt_begin(min_mapq, target_names, _call="ssv_rt_begin_original")
+
+    def rt_original_stats(self):
+        """ssv_rt_original_stats: the counts of the last finished rt_begin_original session, a dict of the struct's fields"""
+        s = _abi.RtOriginalCounts()
+        self._check(self._lib.ssv_rt_original_stats(self._h, C.byref(s)), "ssv_rt_original_stats")
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def rt_begin(self, min_mapq=1, target_names=(), _call="ssv_rt_begin"):
         """ssv_rt_begin: a new -F file; target_names give the contigs' byte-wise name order (and the number of contigs a tid may name)"""
         nt = len(target_names)
         order = sorted(range(nt), key=lambda t: target_names[t].encode())
@@ -97,7 +117,7 @@ class Context:
         for k, t in enumerate(order):
             rank[t] = k
         p = _abi.RtParams(int(min_mapq), nt, rank.ctypes.data_as(C.POINTER(C.c_int32)))
-        self._check(self._lib.ssv_rt_begin(self._h, C.byref(p)), "ssv_rt_begin")
+        self._check(getattr(self._lib, _call)(self._h, C.byref(p)), _call)
 
     def rt_scan(self, batch, names):
         """ssv_rt_scan: the next batch in file order.  names: the batch's read names (list of str), or an _abi.Names that says where they lie -

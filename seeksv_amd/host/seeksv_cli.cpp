@@ -359,6 +359,11 @@ struct RunSession {
 	bool keep_unmapped = false;
 	std::deque<string> unmapped[2];
 	std::function<void(ssv_ctx *, int, JunctionMap &)> split_leg; // ... and the -F pass without a file over them (run_split_leg), called where getsv runs its -F pass
+	// `seeksv run -A`: getclip's pump sent every decoded chunk through the split-read session of `ctx` (ssv_rt_begin_original); getsv finishes it where it
+	// runs its -F pass.  The contigs' names, and with SSV_TIMING what the scans took (the groups are reset by later stages)
+	bool splitread_open = false;
+	vector<string> splitread_names;
+	double splitread_scan_ms = 0; int64_t splitread_scan_launches = 0; double splitread_scan_wall = 0;
 	// `seeksv run -N n`: the ranks of getclip keep their own runs; rank 0's context is `ctx`.  Nothing above is collected until a file whose contigs come
 	// back sends the run down the one-GPU path.
 	RunRanks ranks;
@@ -1059,6 +1064,8 @@ struct GetclipOptions {
 	bool sort_input = false; // `run -u` (no option of getclip's own): the input is in any order; its retained records are coordinate sorted on the GPU before any pass
 	string regions_file;     // `run -L FILE` / `-X FILE`, `somatic -K -L` / `-X` (no option of getclip's own): the records that stay resident are restricted to a BED file's regions
 	bool regions_exclude = false; // -X: a record stays iff it overlaps none of them
+	bool splitread = false;  // `run -A` (no option of getclip's own): every decoded chunk also goes through the split-read scan, in front of retention, marks and restriction
+	int splitread_mapq = 1;  // ... with getsv's -w as its MAPQ floor
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1108,6 +1115,8 @@ static ssv_clip_params clip_params(const GetclipOptions &o)
 	p.match_rate = o.threshold; p.min_mapq = o.min_mapQ; p.save_low_quality = o.save_low_quality ? 1 : 0;
 	return p;
 }
+
+static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original); // (with the -F pass, below)
 
 static int getclip_single(const GetclipOptions &o, RunSession *run)
 {
@@ -1339,6 +1348,28 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	static const char *const kPairNoMemory = "seeksv run: -D keeps the decoded sample in GPU memory with 24 bytes a record of rows, and sorts 32 bytes a record that takes part: out of memory; "
 	                                         "mark the duplicates beforehand and run without -D";
 	static const char *const kProbeNoMemory = "seeksv somatic -K: the normal's records do not fit this GPU's memory (80 bytes a record stay resident): out of memory; run `seeksv getclip` on the normal and `seeksv somatic` with its clip.gz instead";
+	// -A: the session is opened on this context and stays open behind the pass; every decoded chunk goes through its select (and what passes, through the gather)
+	// before the chunk's batch is retained, marked, restricted or overwritten - ssv_rt_scan returns with the stream synchronised.  The decoders' default form
+	// holds the bases of every record with S at an end, which is every record that carries the read: nothing more is decoded for it.
+	const bool splitread = o.splitread && run && run->collect && !probe_only;
+	if (splitread) {
+		run->splitread_names.clear();
+		for (int32_t t = 0, nt = ssvh_bam_n_targets(bam); t < nt; ++t) { const char *nm = ssvh_bam_target_name(bam, t); run->splitread_names.emplace_back(nm ? nm : ""); }
+		rt_begin_for(run->splitread_names, o.splitread_mapq, ctx, true);
+		run->splitread_open = true;
+		if (pt.on) ssv_prof_enable(ctx, 1);
+	}
+	auto splitread_scan = [&](const ssv_batch_t &decoded) {
+		const auto t0 = std::chrono::steady_clock::now();
+		ssv_names_t names;
+		memset(&names, 0, sizeof(names));
+		names.mem = SSV_MEM_DEVICE;
+		if (text_input) names = src.text->names;
+		else check(ctx, ssv_bamdec_names(ctx, &names));
+		check(ctx, ssv_rt_scan(ctx, &decoded, &names));
+		run->splitread_scan_wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		pt.lap("gpu_splitread_scan(wait kernels)");
+	};
 	src.pump(mark_dups || pair_dups ? 1 : 0, [&](const ssv_batch_t &b) {
 		pt.lap(text_input ? "sam_read(wait)+gpu_decode" : o.device_inflate ? "bam_read(wait)+gpu_inflate+decode" : "bam_read(wait)");
 		if (!probe_only) { const uint8_t *raw = nullptr; size_t raw_bytes = 0; src.unmapped_raw(&raw, &raw_bytes); unmapped.submit(raw, raw_bytes); }
@@ -1353,6 +1384,7 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		src.contig_changes(b, last_tid, [&](int64_t i, int32_t tid) { changes_of.back().emplace_back(i, tid); });
 		pt.lap("host_side_channel");
 	}, [&](const ssv_batch_t &decoded) {
+		if (splitread) splitread_scan(decoded);
 		if (pair_dups) { // -D: the batch is only kept, with its rows; every pass waits for the mark
 			ssv_names_t names;
 			memset(&names, 0, sizeof(names));
@@ -1409,6 +1441,10 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		changes_of.pop_front();
 		pt.lap("gpu_scan(wait h2d+kernels)");
 	});
+	if (splitread && pt.on) { // (the later stages reset and switch the groups: the scans' time is read here)
+		ssv_prof_get(ctx, "splitread_scan", &run->splitread_scan_ms, &run->splitread_scan_launches, nullptr);
+		if (!(mark_dups || pair_dups || restrict)) ssv_prof_enable(ctx, 0);
+	}
 	if (mark_dups) { // the end of the file flushes the hold-back
 		dup_step(nullptr, vector<pair<int64_t, int32_t>>());
 		ssv_dup_stats ds;
@@ -1781,7 +1817,7 @@ static void resident_alignments(const RunSession &run, seeksv::AlnRecords &R); /
 // says.  Selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
 static const char *kRtOpenError = "[main_samview] fail to open file for reading.";
 
-static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx)
+static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original)
 {
 	const int32_t nt = (int32_t)names.size();
 	// contigs in byte-wise name order: the device compares (rank, pos) where the reference compares make_pair(chr, pos)
@@ -1792,7 +1828,7 @@ static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx
 	ssv_rt_params rp;
 	memset(&rp, 0, sizeof(rp));
 	rp.min_mapq = min_mapq; rp.n_targets = nt; rp.name_rank = rank.data();
-	check(ctx, ssv_rt_begin(ctx, &rp));
+	check(ctx, original ? ssv_rt_begin_original(ctx, &rp) : ssv_rt_begin(ctx, &rp));
 }
 
 static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &names, const std::function<void()> &begin,
@@ -1811,7 +1847,7 @@ static void sam_text_pass(const string &path, ssv_ctx *ctx, vector<string> &name
 // the -F file as SAM text
 static void readthrough_pass_sam(const string &path, int min_mapq, ssv_ctx *ctx, vector<string> &names)
 {
-	sam_text_pass(path, ctx, names, [&] { rt_begin_for(names, min_mapq, ctx); },
+	sam_text_pass(path, ctx, names, [&] { rt_begin_for(names, min_mapq, ctx, false); },
 	              [&](const ssv_batch_t &b, const ssv_names_t &nm) { check(ctx, ssv_rt_scan(ctx, &b, &nm)); });
 }
 
@@ -1863,7 +1899,7 @@ static void readthrough_pass(const string &path, int min_mapq, ssv_ctx *ctx, boo
 		names.resize((size_t)nt);
 		for (int32_t t = 0; t < nt; ++t) { const char *z = ssvh_bam_target_name(hdr, t); names[(size_t)t] = z ? z : ""; }
 		ssvh_bam_close(hdr);
-		rt_begin_for(names, min_mapq, ctx);
+		rt_begin_for(names, min_mapq, ctx, false);
 		BatchSource src;
 		src.any_order = true; // (a bwasw file is in read order, not coordinate order)
 		src.open(path, ctx, device_inflate, kRtOpenError);
@@ -2120,6 +2156,25 @@ static int getsv_main(const GetsvOptions &opt, RunSession *run)
 		run->split_leg(rt_ctx, opt.min_mapQ2, junction2other);
 		cerr << "'FindJunction' finished" << endl;
 		pt.lap("readthrough (run -P: split alignments of the unmapped pairs, device rows)");
+	} else if (run && run->splitread_open) { // `seeksv run -A`: at the same place; the session has seen every chunk of the original
+		rt_ctx = acquire_ctx(opt.device, run);
+		if (pt.on) { ssv_prof_enable(rt_ctx, 1); ssv_prof_reset(rt_ctx); }
+		ssv_rt_result res;
+		check(rt_ctx, ssv_rt_finish(rt_ctx, &res));
+		run->splitread_open = false;
+		seeksv::apply_readthrough(res, run->splitread_names, junction2other);
+		ssv_rt_original_counts st;
+		check(rt_ctx, ssv_rt_original_stats(rt_ctx, &st));
+		cerr << "[seeksv] -A: " << st.pairs << " pairs (" << st.pairs_borrowed << " with a borrowed seq) of " << st.candidates << " one-side-clipped records (" << st.hard_clipped
+		     << " hard-clipped); dropped at the pairing: " << st.dropped_no_carrier << " without a record that carries the read, " << st.dropped_length << " for unequal read lengths" << endl;
+		pt.lap("splitread (run -A: the original's own supplementary alignments)");
+		if (pt.on) {
+			double ms = 0; int64_t launches = 0;
+			ssv_prof_get(rt_ctx, "splitread_finish", &ms, &launches, nullptr);
+			cerr << "[timing] (-A kernel time: splitread_scan " << run->splitread_scan_ms << " ms in " << run->splitread_scan_launches << " launches, splitread_finish " << ms << " ms in " << launches
+			     << " launches; the scans held the pump for " << run->splitread_scan_wall << " s; candidate store " << st.store_bytes << " bytes)" << endl;
+			ssv_prof_enable(rt_ctx, 0);
+		}
 	}
 	{ // InputSoftInfoStoreBreakpoint + GetJunction (getsv.h:423, getsv.cpp:1705): clip clusters x re-alignments of their clipped sequences
 		string err;
@@ -3125,7 +3180,7 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 {
 	ssv_ctx *actx = aligner.kept_ctx;
 	if (!actx) die("[seeksv] run -P: the aligner's index is gone");
-	rt_begin_for(aligner.R.names, min_mapq, rt_ctx);
+	rt_begin_for(aligner.R.names, min_mapq, rt_ctx, false);
 	static const int64_t piece = [] { const char *e = getenv("SSV_REALIGN_SPLIT_PIECE"); const long long v = e ? atoll(e) : 0; return v > 0 ? (int64_t)v : (int64_t)1 << 22; }();
 	seeksv::FastqReads reads;
 	vector<ssv_realign_hit> hits, mates;
@@ -3264,6 +3319,17 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               `samtools view -L` in outline; this program's own rule, no external tool was matched.  Not with -X or -N above 1, not inside -c\n"
 	     << "         -X <file>             the same with the rule turned round: keep only the records that overlap NO region of the file (an exclude list: centromeres,\n"
 	     << "                               decoys, blacklists); unplaced records stay.  Not with -L or -N above 1, not inside -c or -v\n"
+	     << "         -A                    also seed junctions from the input's own supplementary alignments, as `getsv -F` does from a bwasw file: a read that spans a\n"
+	     << "                               breakpoint comes from `bwa mem` / minimap2 as a primary record plus a supplementary record (flag 2048), each clipped on one side.\n"
+	     << "                               Every decoded chunk goes through a split-read scan on the GPU while it is retained; the pairs fold into the junction map where\n"
+	     << "                               -F's do (behind the -B rows, in front of the clip join; -w of -v is the MAPQ floor).  This program's own rule, FindJunction's\n"
+	     << "                               geometry with another selection and key: a record takes part when exactly one end is S or H (hard clips count: lengths come\n"
+	     << "                               from the CIGAR), it is mapped to a contig and neither secondary nor duplicate; records pair by (read name, first / second of\n"
+	     << "                               pair), so mates never meet; the two records must give one read length, and one of them must hold all bases of the read - a\n"
+	     << "                               hard-clipped record's seqs are read from its partner.  The pass reads the input's flags, not the marks -M / -D make in this\n"
+	     << "                               run; it is not restricted by -L / -X; with -u it runs in input order; a read of three or more pieces gives what hold / pair /\n"
+	     << "                               drop gives, no chaining.  Takes a BAM or SAM text, with -u, -M, -D, -L, -X.  Not with -P, -F in -v or -N above 1, not inside\n"
+	     << "                               -c, -v or -a\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
 	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
 	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
@@ -3276,10 +3342,11 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
-	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false;
+	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false, splitread = false;
 	string include_file, exclude_file;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuDL:X:")) >= 0) {
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuDL:X:A")) >= 0) {
 		switch (c) {
+		case 'A': splitread = true; break;
 		case 'P': split = true; break;
 		case 'M': mark_dups = true; break;
 		case 'u': unsorted = true; break;
@@ -3302,6 +3369,11 @@ static int cmd_run(int argc, char **argv)
 	// The three steps' options, each through the step's own parser: a usage error or a value out of range ends the run here with the step's usage text, before
 	// the GPU context is asked for and before any file exists.  The GPU of realign is run's own -G.
 	// -u is run's own: refused inside -c / -v with its reason, not with the steps' usage texts
+	for (const string *words : {&clip_opts, &sv_opts, &aln_opts}) { // -A is run's own as well
+		std::istringstream in(*words);
+		for (string w; in >> w;)
+			if (w == "-A") die("seeksv run: -A scans the records that this run decodes, once, on their way into GPU memory; -A inside -c, -v or -a is not supported");
+	}
 	for (const string *words : {&clip_opts, &sv_opts}) {
 		std::istringstream in(*words);
 		for (string w; in >> w;) {
@@ -3336,6 +3408,10 @@ static int cmd_run(int argc, char **argv)
 	if (!include_file.empty() && !exclude_file.empty()) die("seeksv run: -L keeps the records inside its regions and -X those outside; -X is not supported with -L");
 	if ((!include_file.empty() || !exclude_file.empty()) && ranked)
 		die(string("seeksv run: ") + (include_file.empty() ? "-X" : "-L") + " restricts the records that one GPU keeps; -N above 1 is not supported with it");
+	// -A: one session, fed by the one pump of one GPU
+	if (splitread && split) die("seeksv run: -A and -P both feed the one split-alignment session of this run, which has one source; -P is not supported with -A");
+	if (splitread && !sv.connect_bam.empty()) die("seeksv run: -A is the -F pass of this run; -F inside -v names another source for it");
+	if (splitread && ranked) die("seeksv run: -A pairs the records of a read by name among the records that one GPU decodes; -N above 1 is not supported with it");
 	// -N: the run cuts the file once for both steps and maps its ranks to GPUs itself
 	if (ranked && (clip.ranks_given || clip.devices_given || sv.ranks_given || sv.devices_given))
 		die("seeksv run: with -N the ranks and their GPUs are run's own -N and -G; -N or -G inside -c or -v is not supported with it");
@@ -3344,6 +3420,7 @@ static int cmd_run(int argc, char **argv)
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
 	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted; clip.pair_dups = pair_dups;
+	clip.splitread = splitread; clip.splitread_mapq = sv.min_mapQ2;
 	clip.regions_file = include_file.empty() ? exclude_file : include_file; clip.regions_exclude = include_file.empty() && !exclude_file.empty();
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
