@@ -71,6 +71,7 @@ asan: $(LIBDIR)/libseeksv_hip.so
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Iseeksv_amd/csrc tests/native/inflate_check.cpp -lz -o $(ASAN_DIR)/inflate_check && $(ASAN_DIR)/inflate_check
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/fastq_reads_check.cpp -o $(ASAN_DIR)/fastq_reads_check && $(ASAN_DIR)/fastq_reads_check
 	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra -Iseeksv_amd/host tests/native/regions_check.cpp -lz -o $(ASAN_DIR)/regions_check && $(ASAN_DIR)/regions_check
+	$(CXX) $(ASAN_FLAGS) -std=c++17 -Wall -Wextra tests/native/sa_parse_check.cpp -o $(ASAN_DIR)/sa_parse_check && $(ASAN_DIR)/sa_parse_check
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so):$$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0 SSV_CLEAN_EXIT=1 \
 		SSV_TEST_CXXFLAGS="$(ASAN_FLAGS)" SSV_LIBDIR=$(abspath $(ASAN_DIR)) SSV_ORACLE_SO=$(abspath $(ASAN_DIR))/liboracle.so SSV_CLI=$(abspath $(ASAN_DIR))/seeksv \
 		python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider

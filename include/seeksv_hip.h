@@ -860,6 +860,82 @@ typedef struct {
 int ssv_rt_begin_original(ssv_ctx *ctx, const ssv_rt_params *p);
 int ssv_rt_original_stats(ssv_ctx *ctx, ssv_rt_original_counts *out);
 
+/* ---- run -A -S: junctions from SA tags whose supplementary record is absent (v9, additive) ----------------------------------------------------
+ * ssv_rt_begin_original_sa opens the session of ssv_rt_begin_original in one more mode: a record that carries the read and has an SA value of exactly one
+ * entry also contributes a VIRTUAL CANDIDATE built from that entry, which is used only when its source record found no real partner.  Batches go through
+ * ssv_rt_scan_aux (ssv_rt_scan with a descriptor of where the records' optional fields lie: ssv_aux_t, from ssv_bamdec_aux / ssv_samdec_aux or the
+ * caller's own); ssv_rt_finish, ssv_rt_pair, ssv_rt_result and ssv_rt_original_stats are the same calls with the same rows.  A session opened with
+ * ssv_rt_begin or ssv_rt_begin_original behaves byte for byte as before and launches nothing of this mode.
+ *
+ * 1. Who gets a virtual candidate.  A SOURCE is a record that takes part under ssv_rt_begin_original's rule and carries the read (no H, bases present,
+ *    l_qseq == R).  Only a source has its optional fields looked at.  A hard-clipped record never gets a virtual candidate: a virtual candidate never
+ *    carries the read, so the pair would have no bases.
+ * 2. Finding the value.
+ *    BAM: the typed fields are walked as libbam does: A c C s S i I f d Z H B; an unknown type ends the walk.  The first field with tag SA and type Z is
+ *    taken; SA with another type is passed over.  Nothing is read beyond the record's block_size: a Z or H value with no NUL before the record's end, or a
+ *    B array that runs over it, ends the walk with no value.
+ *    SAM text: optional fields start at field 12.  A field matches only when it begins with "SA:Z:" directly behind a tab ("XA:Z:...SA:Z:..." inside
+ *    another value is no match).  The value ends at the tab, at a '\r' before the newline, at the newline, or at the end of the last line.
+ * 3. The value's grammar: rname,pos,strand,CIGAR,mapQ,NM; - one entry, parsed as written:
+ *      - rname runs up to the first ','; it may hold ';', ':' and '*';
+ *      - pos is decimal, 1 to 2^31-1, stored minus 1;
+ *      - strand is '+' or '-';
+ *      - CIGAR is one or more operations of MIDNSHP=X, each with a length below 2^28, at most 65535 of them;
+ *      - mapQ is decimal, 0 to 255;
+ *      - NM is a run of digits (at least one) and is ignored;
+ *      - the entry ends with ';'; a missing final ';' at the value's end is accepted.
+ *    Anything else is sa_refused: no virtual candidate and no error.  Bytes behind the first entry's ';' make it sa_multi: no virtual candidate (a read of
+ *    three or more pieces stays unchained).  rname must be a contig of the header, by exact name: else sa_refused.
+ * 4. The virtual candidate is what a record with that tid, pos0, strand and CIGAR would give under ssv_rt_begin_original's rule.  S in an SA CIGAR stands
+ *    for the record's H; both are clips.
+ *      - exactly one end must be clipped, and mapQ >= min_mapq: failing either is sa_refused;
+ *      - R, the clip run, ref_len, side, left, right and pos come from the same formulas;
+ *      - it shares its source's name, key, mate bits and record index;
+ *      - it has no bases and never carries the read; it holds its non-clip operations; it is marked, and knows its source.
+ * 5. Pairing.  Under one key, pairing has two phases.
+ *    Phase 1: hold / pair / drop over the real candidates alone, in input order: every outcome and every count is exactly ssv_rt_begin_original's with the
+ *    virtual candidates absent.
+ *    Phase 2: every real candidate that left phase 1 with no partner and is nobody's partner (held, or dropped), if it owns a virtual candidate, pairs with
+ *    it when the strand / side test passes and R_source == R_virtual (unequal: sa_dropped_length).  The source is A, the held record; the virtual candidate
+ *    is B, the completing record, and its row stands where a record right behind the source would have completed it.  A virtual candidate whose source
+ *    found a real partner is sa_redundant.
+ *    The result does not depend on where the input is cut into batches: that is why virtual candidates stay out of phase 1.
+ * 6. Everything behind the pairing is unchanged: junction, microhomology, kind and CIGAR sources by ssv_rt_begin's case analysis; a seq that names the
+ *    virtual side is read from the source by ssv_rt_begin_original's slice rule (it counts among pairs_borrowed).
+ *
+ * Contig names: target_names[n_targets], host, NUL-terminated, read during the call.  Errors as ssv_rt_begin_original's; out of sequence: SSV_E_STATE -
+ * ssv_rt_scan_aux outside a session of this mode, ssv_rt_scan inside one, ssv_rt_original_sa_stats before such a session has finished or after the next
+ * begin; a descriptor that does not belong to the batch (n != batch n, bad mem or encoding, a host span outside bytes): SSV_E_ARG. */
+enum { SSV_AUX_BAM = 0, SSV_AUX_SAM = 1 };
+/* Where the optional fields of a batch's records lie, beside ssv_batch_t and ssv_names_t: record i's are the len[i] bytes at base + off[i], BAM's typed
+ * fields (up to the record's block_size) or SAM text (from field 12 to the line's end).  mem as in ssv_names_t (SSV_MEM_HOST: base[bytes], off[n] and len[n]
+ * are copied to the GPU; SSV_MEM_DEVICE: used in place, bytes unused). */
+typedef struct {
+	int32_t mem;
+	int32_t encoding;       /* SSV_AUX_BAM / SSV_AUX_SAM */
+	int64_t n;              /* records described: the batch's n */
+	const uint8_t *base;
+	const uint64_t *off;
+	const uint32_t *len;
+	int64_t bytes;
+} ssv_aux_t;
+/* The optional fields of the last chunk ssv_bamdec_decode / ssv_samdec_decode handed out, in HBM (valid as long as that batch).  Computed by a kernel of
+ * its own on the context's stream when the call is made; a run that never asks launches nothing. */
+int ssv_bamdec_aux(ssv_ctx *ctx, ssv_aux_t *out);
+int ssv_samdec_aux(ssv_ctx *ctx, ssv_aux_t *out);
+typedef struct {
+	int64_t sa_tags;            /* sources with an SA:Z value: sa_multi + sa_refused + virtuals */
+	int64_t sa_multi;           /* ... whose value holds more than one entry */
+	int64_t sa_refused;         /* ... whose entry is not in the grammar, names no contig, fails the ends rule or the MAPQ floor */
+	int64_t virtuals;           /* virtual candidates made */
+	int64_t sa_redundant;       /* ... whose source found a real partner */
+	int64_t pairs_from_sa;      /* ... that completed a pair (counted in ssv_rt_original_counts.pairs too) */
+	int64_t sa_dropped_length;  /* ... dropped because R_source != R_virtual */
+} ssv_rt_original_sa_counts;
+int ssv_rt_begin_original_sa(ssv_ctx *ctx, const ssv_rt_params *p, const char *const *target_names);
+int ssv_rt_scan_aux(ssv_ctx *ctx, const ssv_batch_t *b, const ssv_names_t *names, const ssv_aux_t *aux);
+int ssv_rt_original_sa_stats(ssv_ctx *ctx, ssv_rt_original_sa_counts *out);
+
 /* ---- duplicate read pairs marked while the sample is retained (v9, additive; `seeksv run -M`, `seeksv somatic -K -M`) ----------------------
  * Every pass honours the duplicate flag 0x400; this stage sets it, in the retained copy only, before any pass reads a flag.  The rule is this library's own (it
  * follows `samtools rmdup` where it can; no external duplicate marker was run or matched).  Records come in file order, coordinate sorted; a RUN is a maximal

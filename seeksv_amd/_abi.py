@@ -195,6 +195,18 @@ class RtOriginalCounts(C.Structure):  # ssv_rt_original_counts
     _fields_ = [(k, C.c_int64) for k in ("candidates", "hard_clipped", "pairs", "pairs_borrowed", "dropped_no_carrier", "dropped_length", "store_bytes")]
 
 
+AUX_BAM, AUX_SAM = 0, 1
+
+
+class Aux(C.Structure):
+    """ssv_aux_t: record i's optional fields are the len[i] bytes at base + off[i]"""
+    _fields_ = [("mem", C.c_int32), ("encoding", C.c_int32), ("n", C.c_int64), ("base", C.c_void_p), ("off", C.c_void_p), ("len", C.c_void_p), ("bytes", C.c_int64)]
+
+
+class RtOriginalSaCounts(C.Structure):  # ssv_rt_original_sa_counts
+    _fields_ = [(k, C.c_int64) for k in ("sa_tags", "sa_multi", "sa_refused", "virtuals", "sa_redundant", "pairs_from_sa", "sa_dropped_length")]
+
+
 def make_batch(arrays, mem=MEM_HOST, n=None):
     """Build an ssv_batch_t over numpy arrays (host) or raw device pointers (ints). Returns (Batch, keepalive)."""
     b = Batch()
@@ -441,6 +453,11 @@ def hip_lib():
         lib.ssv_rt_finish.argtypes = [V, C.POINTER(RtResult)]
         lib.ssv_rt_begin_original.argtypes = [V, C.POINTER(RtParams)]
         lib.ssv_rt_original_stats.argtypes = [V, C.POINTER(RtOriginalCounts)]
+        lib.ssv_rt_begin_original_sa.argtypes = [V, C.POINTER(RtParams), C.POINTER(C.c_char_p)]
+        lib.ssv_rt_scan_aux.argtypes = [V, C.POINTER(Batch), C.POINTER(Names), C.POINTER(Aux)]
+        lib.ssv_rt_original_sa_stats.argtypes = [V, C.POINTER(RtOriginalSaCounts)]
+        lib.ssv_bamdec_aux.argtypes = [V, C.POINTER(Aux)]
+        lib.ssv_samdec_aux.argtypes = [V, C.POINTER(Aux)]
         lib.ssv_samdec_begin.argtypes = [V, C.POINTER(SamdecParams)]
         lib.ssv_samdec_prefetch.argtypes = [V, V, C.c_size_t]
         lib.ssv_samdec_decode.argtypes = [V, V, C.c_size_t, C.c_int, C.c_int, C.POINTER(Batch)]

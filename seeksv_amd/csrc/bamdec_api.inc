@@ -18,6 +18,7 @@ struct ssv_bamdec_state {
 	DBuf tlen; bool have_tlen = false; // contig lengths (optional: ssv_bamdec_target_lens)
 	DecodedColumns cols; // the batch handed out
 	DBuf rel, stash, seq_list, raw_bytes, raw_off, raw;
+	DBuf aux_off, aux_len; // ssv_bamdec_aux: where each record's optional fields lie (only when asked for)
 	HBuf h_stage[3], h_small, h_raw[2], h_status; // h_raw: two in turn - a chunk's UNMAP|MUNMAP records stay valid while the next chunk is decoded (a thread beside the decoder pairs them up)
 	int raw_flip = 0;
 	// chunks announced ahead (ssv_bamdec_prefetch): their compressed bytes travel on the upload stream into one of two slots while the chunk before is inflated
@@ -425,6 +426,27 @@ int ssv_bamdec_names(ssv_ctx *c, ssv_names_t *out)
 	memset(out, 0, sizeof(*out));
 	out->mem = SSV_MEM_DEVICE; out->bias = 36;
 	out->base = P<char>(c->bd->stream); out->off = P<uint64_t>(c->bd->rec_off);
+	return SSV_OK;
+}
+
+// where the optional fields of the last decoded chunk's records lie in the inflated stream (k_bam_aux_span: computed when asked for, never by a decode)
+int ssv_bamdec_aux(ssv_ctx *c, ssv_aux_t *out)
+{
+	if (!c || !out) return SSV_E_ARG;
+	if (!c->bd) { c->err = "ssv_bamdec_aux before ssv_bamdec_begin"; return SSV_E_STATE; }
+	ssv_bamdec_state &d = *c->bd;
+	const int64_t n = d.info.n_records;
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_DEVICE; out->encoding = SSV_AUX_BAM; out->n = n;
+	if (n <= 0) { out->n = 0; return SSV_OK; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	CHECK(ensure(c, d.aux_off, (size_t)n * 8 + 16)); CHECK(ensure(c, d.aux_len, (size_t)n * 4 + 16));
+	{
+		ProfScope ps(c, P_SPLITREAD_SA_AUX, n);
+		k_bam_aux_span<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint8_t>(d.stream), P<uint64_t>(d.rec_off), n, P<uint64_t>(d.aux_off), P<uint32_t>(d.aux_len));
+		HIPCHECK(c, hipGetLastError());
+	}
+	out->base = P<uint8_t>(d.stream); out->off = P<uint64_t>(d.aux_off); out->len = P<uint32_t>(d.aux_len);
 	return SSV_OK;
 }
 

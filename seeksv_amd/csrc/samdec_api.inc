@@ -14,6 +14,7 @@ struct ssv_samdec_state {
 	DBuf text, carrybuf, tile_sep, tile_nl, sep, nlidx, small;
 	DecodedColumns cols; // the batch handed out
 	DBuf name_off, rec;
+	DBuf aux_off, aux_len; // ssv_samdec_aux: where each line's optional fields lie (only when asked for)
 	HBuf h_small;
 	// chunks announced ahead (ssv_samdec_prefetch): on the upload stream into one of two slots, moved behind the carried line by the decode call
 	struct Slot { DBuf buf; const void *host = nullptr; size_t bytes = 0; hipEvent_t up = nullptr, done = nullptr; bool read = false; } slot[2];
@@ -333,6 +334,28 @@ int ssv_samdec_names(ssv_ctx *c, ssv_names_t *out)
 	memset(out, 0, sizeof(*out));
 	out->mem = SSV_MEM_DEVICE; out->bias = 0;
 	out->base = P<char>(c->sd->text); out->off = P<uint64_t>(c->sd->name_off); out->bytes = (int64_t)c->sd->text_bytes;
+	return SSV_OK;
+}
+
+// where the optional fields of the last decoded batch's lines lie in the context's copy of the text: field 12 to the line's end (k_sam_aux_span over the
+// separators the decode left; computed when asked for, never by a decode)
+int ssv_samdec_aux(ssv_ctx *c, ssv_aux_t *out)
+{
+	if (!c || !out) return SSV_E_ARG;
+	if (!c->sd || !c->sd->have_batch) { c->err = "ssv_samdec_aux before a successful ssv_samdec_decode"; return SSV_E_STATE; }
+	ssv_samdec_state &d = *c->sd;
+	const int64_t n = d.info.n_records;
+	memset(out, 0, sizeof(*out));
+	out->mem = SSV_MEM_DEVICE; out->encoding = SSV_AUX_SAM; out->n = n;
+	if (n <= 0) { out->n = 0; return SSV_OK; }
+	HIPCHECK(c, hipSetDevice(c->device));
+	CHECK(ensure(c, d.aux_off, (size_t)n * 8 + 16)); CHECK(ensure(c, d.aux_len, (size_t)n * 4 + 16));
+	{
+		ProfScope ps(c, P_SPLITREAD_SA_AUX, n);
+		k_sam_aux_span<<<grid_for(n, BLOCK), BLOCK, 0, c->st>>>(P<uint8_t>(d.text), P<uint32_t>(d.sep), P<uint32_t>(d.nlidx), n, P<uint64_t>(d.aux_off), P<uint32_t>(d.aux_len));
+		HIPCHECK(c, hipGetLastError());
+	}
+	out->base = P<uint8_t>(d.text); out->off = P<uint64_t>(d.aux_off); out->len = P<uint32_t>(d.aux_len);
 	return SSV_OK;
 }
 

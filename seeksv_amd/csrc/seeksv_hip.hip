@@ -45,6 +45,7 @@
 #include "readthrough_kernels.h"
 #include "splitread_kernels.h"
 #include "samdec_kernels.h"
+#include "splitread_sa_kernels.h"
 #include "alnpack_kernels.h"
 #include "probe_kernels.h"
 #include "dup_kernels.h"
@@ -60,9 +61,9 @@ namespace {
 thread_local std::string g_create_error; // (per thread: ssv_last_error(NULL) is asked by the thread whose call failed; rank and reader threads run side by side)
 
 // timed kernel groups (ssv_prof_*)
-enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_RT_SCAN, P_RT_FINISH, P_REALIGN_GAP, P_REALIGN_ALTS, P_REALIGN_ROWS, P_SOMATIC_PROBE, P_DUP_SELECT, P_DUP_MARK, P_DUP_RETAIN, P_SORT_KEYS, P_SORT_RADIX, P_SORT_GATHER, P_PAIRDUP_ENDS, P_PAIRDUP_JOIN, P_PAIRDUP_MARK, P_REGION_SELECT, P_REGION_GATHER, P_SPLITREAD_SCAN, P_SPLITREAD_FINISH, P_COUNT };
-const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve", "rt_scan", "rt_finish", "realign_gap", "realign_alts", "realign_rows", "somatic_probe", "dup_select", "dup_mark", "dup_retain", "sort_keys", "sort_radix", "sort_gather", "pairdup_ends", "pairdup_join", "pairdup_mark", "region_select", "region_gather", "splitread_scan", "splitread_finish"};
-const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve\nrt_scan\nrt_finish\nrealign_gap\nrealign_alts\nrealign_rows\nsomatic_probe\ndup_select\ndup_mark\ndup_retain\nsort_keys\nsort_radix\nsort_gather\npairdup_ends\npairdup_join\npairdup_mark\nregion_select\nregion_gather\nsplitread_scan\nsplitread_finish";
+enum ProfId { P_H2D, P_CLIP_SCAN, P_CLIP_PLACE, P_CLIP_GATHER, P_SORT, P_CLUSTER_BINS, P_CLUSTER_PACK, P_TABLE_D2H, P_ISIZE, P_GETSV_SCAN, P_GETSV_CAND, P_DEPTH_FINISH, P_BAM_INFLATE, P_BAM_RECORDS, P_BAM_DECODE, P_REALIGN_INDEX, P_REALIGN_QUERY, P_BAM_UPLOAD, P_BAM_RESOLVE, P_RT_SCAN, P_RT_FINISH, P_REALIGN_GAP, P_REALIGN_ALTS, P_REALIGN_ROWS, P_SOMATIC_PROBE, P_DUP_SELECT, P_DUP_MARK, P_DUP_RETAIN, P_SORT_KEYS, P_SORT_RADIX, P_SORT_GATHER, P_PAIRDUP_ENDS, P_PAIRDUP_JOIN, P_PAIRDUP_MARK, P_REGION_SELECT, P_REGION_GATHER, P_SPLITREAD_SA_AUX, P_SPLITREAD_SA_SCAN, P_SPLITREAD_SA_FINISH, P_SPLITREAD_SCAN, P_SPLITREAD_FINISH, P_COUNT };
+const char *const kProfNames[P_COUNT] = {"h2d", "clip_scan", "clip_place", "clip_gather", "event_sort", "cluster_bins", "cluster_pack", "table_d2h", "isize_stats", "getsv_scan", "getsv_cand", "depth_finish", "bam_inflate", "bam_records", "bam_decode", "realign_index", "realign_query", "bam_upload", "bam_resolve", "rt_scan", "rt_finish", "realign_gap", "realign_alts", "realign_rows", "somatic_probe", "dup_select", "dup_mark", "dup_retain", "sort_keys", "sort_radix", "sort_gather", "pairdup_ends", "pairdup_join", "pairdup_mark", "region_select", "region_gather", "splitread_sa_aux", "splitread_sa_scan", "splitread_sa_finish", "splitread_scan", "splitread_finish"};
+const char kProfNameList[] = "h2d\nclip_scan\nclip_place\nclip_gather\nevent_sort\ncluster_bins\ncluster_pack\ntable_d2h\nisize_stats\ngetsv_scan\ngetsv_cand\ndepth_finish\nbam_inflate\nbam_records\nbam_decode\nrealign_index\nrealign_query\nbam_upload\nbam_resolve\nrt_scan\nrt_finish\nrealign_gap\nrealign_alts\nrealign_rows\nsomatic_probe\ndup_select\ndup_mark\ndup_retain\nsort_keys\nsort_radix\nsort_gather\npairdup_ends\npairdup_join\npairdup_mark\nregion_select\nregion_gather\nsplitread_sa_aux\nsplitread_sa_scan\nsplitread_sa_finish\nsplitread_scan\nsplitread_finish";
 
 hipError_t pinned_delete(void *p);
 

@@ -109,6 +109,67 @@ class Context:
         self._check(self._lib.ssv_rt_original_stats(self._h, C.byref(s)), "ssv_rt_original_stats")
         return {k: int(getattr(s, k)) for k, _ in s._fields_}
 
+    # ---- run -A -S: virtual candidates from SA tags (ssv_rt_begin_original_sa) ----
+    def readthrough_original_sa(self, batches, names, auxes, min_mapq=1, target_names=(), raw=False):
+        """readthrough_original() with virtual candidates from the SA tag of a source whose partner is absent (ssv_rt_begin_original_sa,
+        include/seeksv_hip.h).  auxes[k]: batch k's optional fields - an _abi.Aux, or (encoding, [bytes per record]).  Same rows;
+        raw: (rows, rt_original_stats(), rt_original_sa_stats())."""
+        self.rt_begin_original_sa(min_mapq, target_names)
+        for b, nm, ax in zip(batches, names, auxes):
+            self.rt_scan_aux(b, nm, ax)
+        out = self.rt_decode(self.rt_finish(), target_names)
+        return (out, self.rt_original_stats(), self.rt_original_sa_stats()) if raw else out
+
+    def rt_begin_original_sa(self, min_mapq=1, target_names=()):
+        """ssv_rt_begin_original_sa: rt_begin_original() plus the contig names the SA entries are looked up in; batches go through rt_scan_aux"""
+        nt = len(target_names)
+        raw = [x.encode() if isinstance(x, str) else bytes(x) for x in target_names]
+        order = sorted(range(nt), key=lambda t: raw[t])
+        rank = np.zeros(max(nt, 1), dtype=np.int32)
+        rank[order] = np.arange(nt, dtype=np.int32)
+        arr = (C.c_char_p * max(1, nt))(*raw)
+        p = _abi.RtParams(int(min_mapq), nt, rank.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(self._lib.ssv_rt_begin_original_sa(self._h, C.byref(p), arr), "ssv_rt_begin_original_sa")
+
+    @staticmethod
+    def _as_aux(aux):
+        """an _abi.Aux as it is, or one over host memory for (encoding, [the optional-field bytes of every record]); -> (Aux, keepalive)"""
+        if isinstance(aux, _abi.Aux):
+            return aux, None
+        enc, areas = aux
+        blob = b"".join(areas)
+        lens = np.array([len(a) for a in areas], dtype=np.uint32)
+        off = np.zeros(len(areas) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(lens, dtype=np.uint64)
+        buf = C.create_string_buffer(blob, max(1, len(blob)))
+        return _abi.Aux(_abi.MEM_HOST, int(enc), len(areas), C.cast(buf, C.c_void_p), off.ctypes.data, lens.ctypes.data, len(blob)), (buf, off, lens)
+
+    def rt_scan_aux(self, batch, names, aux):
+        """ssv_rt_scan_aux: rt_scan() in a session of rt_begin_original_sa.  aux: bamdec_aux() / samdec_aux() for a batch of a device decoder, or
+        (encoding, [bytes per record])"""
+        bb, keep = self._as_batch(batch)
+        n, keep_names = self._as_names(names)
+        a, keep_aux = self._as_aux(aux)
+        self._check(self._lib.ssv_rt_scan_aux(self._h, C.byref(bb), C.byref(n), C.byref(a)), "ssv_rt_scan_aux")
+
+    def rt_original_sa_stats(self):
+        """ssv_rt_original_sa_stats: the seven SA counts of the last finished rt_begin_original_sa session, a dict of the struct's fields"""
+        s = _abi.RtOriginalSaCounts()
+        self._check(self._lib.ssv_rt_original_sa_stats(self._h, C.byref(s)), "ssv_rt_original_sa_stats")
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+    def bamdec_aux(self):
+        """ssv_bamdec_aux: where the optional fields of the batch bam_batches handed out last lie in HBM (valid as long as that batch)"""
+        a = _abi.Aux()
+        self._check(self._lib.ssv_bamdec_aux(self._h, C.byref(a)), "ssv_bamdec_aux")
+        return a
+
+    def samdec_aux(self):
+        """ssv_samdec_aux: where the optional fields of the batch decoded last lie in HBM (valid as long as that batch)"""
+        a = _abi.Aux()
+        self._check(self._lib.ssv_samdec_aux(self._h, C.byref(a)), "ssv_samdec_aux")
+        return a
+
     def rt_begin(self, min_mapq=1, target_names=(), _call="ssv_rt_begin"):
         """ssv_rt_begin: a new -F file; target_names give the contigs' byte-wise name order (and the number of contigs a tid may name)"""
         nt = len(target_names)

@@ -361,7 +361,8 @@ struct RunSession {
 	std::function<void(ssv_ctx *, int, JunctionMap &)> split_leg; // ... and the -F pass without a file over them (run_split_leg), called where getsv runs its -F pass
 	// `seeksv run -A`: getclip's pump sent every decoded chunk through the split-read session of `ctx` (ssv_rt_begin_original); getsv finishes it where it
 	// runs its -F pass.  The contigs' names, and with SSV_TIMING what the scans took (the groups are reset by later stages)
-	bool splitread_open = false;
+	bool splitread_open = false, splitread_sa = false;
+	double splitread_aux_ms = 0; int64_t splitread_aux_launches = 0;
 	vector<string> splitread_names;
 	double splitread_scan_ms = 0; int64_t splitread_scan_launches = 0; double splitread_scan_wall = 0;
 	// `seeksv run -N n`: the ranks of getclip keep their own runs; rank 0's context is `ctx`.  Nothing above is collected until a file whose contigs come
@@ -1066,6 +1067,7 @@ struct GetclipOptions {
 	bool regions_exclude = false; // -X: a record stays iff it overlaps none of them
 	bool splitread = false;  // `run -A` (no option of getclip's own): every decoded chunk also goes through the split-read scan, in front of retention, marks and restriction
 	int splitread_mapq = 1;  // ... with getsv's -w as its MAPQ floor
+	bool splitread_sa = false; // `run -A -S`: ... and a record that carries the read also gives a virtual candidate from its SA tag (ssv_rt_begin_original_sa)
 	vector<int> devices;
 	string prefix = "output", bamfile;
 	void set_devices(const char *list) { devices = parse_devices(list); device = devices.empty() ? 0 : devices[0]; }
@@ -1116,7 +1118,7 @@ static ssv_clip_params clip_params(const GetclipOptions &o)
 	return p;
 }
 
-static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original); // (with the -F pass, below)
+static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original, bool sa = false); // (with the -F pass, below)
 
 static int getclip_single(const GetclipOptions &o, RunSession *run)
 {
@@ -1355,8 +1357,8 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 	if (splitread) {
 		run->splitread_names.clear();
 		for (int32_t t = 0, nt = ssvh_bam_n_targets(bam); t < nt; ++t) { const char *nm = ssvh_bam_target_name(bam, t); run->splitread_names.emplace_back(nm ? nm : ""); }
-		rt_begin_for(run->splitread_names, o.splitread_mapq, ctx, true);
-		run->splitread_open = true;
+		rt_begin_for(run->splitread_names, o.splitread_mapq, ctx, true, o.splitread_sa);
+		run->splitread_open = true; run->splitread_sa = o.splitread_sa;
 		if (pt.on) ssv_prof_enable(ctx, 1);
 	}
 	auto splitread_scan = [&](const ssv_batch_t &decoded) {
@@ -1366,7 +1368,11 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		names.mem = SSV_MEM_DEVICE;
 		if (text_input) names = src.text->names;
 		else check(ctx, ssv_bamdec_names(ctx, &names));
-		check(ctx, ssv_rt_scan(ctx, &decoded, &names));
+		if (o.splitread_sa) { // -S: where the chunk's optional fields lie, asked of the decoder that made the chunk
+			ssv_aux_t aux;
+			check(ctx, text_input ? ssv_samdec_aux(ctx, &aux) : ssv_bamdec_aux(ctx, &aux));
+			check(ctx, ssv_rt_scan_aux(ctx, &decoded, &names, &aux));
+		} else check(ctx, ssv_rt_scan(ctx, &decoded, &names));
 		run->splitread_scan_wall += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 		pt.lap("gpu_splitread_scan(wait kernels)");
 	};
@@ -1442,7 +1448,8 @@ static int getclip_single(const GetclipOptions &o, RunSession *run)
 		pt.lap("gpu_scan(wait h2d+kernels)");
 	});
 	if (splitread && pt.on) { // (the later stages reset and switch the groups: the scans' time is read here)
-		ssv_prof_get(ctx, "splitread_scan", &run->splitread_scan_ms, &run->splitread_scan_launches, nullptr);
+		ssv_prof_get(ctx, o.splitread_sa ? "splitread_sa_scan" : "splitread_scan", &run->splitread_scan_ms, &run->splitread_scan_launches, nullptr);
+		if (o.splitread_sa) ssv_prof_get(ctx, "splitread_sa_aux", &run->splitread_aux_ms, &run->splitread_aux_launches, nullptr);
 		if (!(mark_dups || pair_dups || restrict)) ssv_prof_enable(ctx, 0);
 	}
 	if (mark_dups) { // the end of the file flushes the hold-back
@@ -1817,7 +1824,7 @@ static void resident_alignments(const RunSession &run, seeksv::AlnRecords &R); /
 // says.  Selection, pairing by read name and the junction of every pair run on the GPU (ssv_rt_*), the pairs are applied to the map here in their order.
 static const char *kRtOpenError = "[main_samview] fail to open file for reading.";
 
-static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original)
+static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx, bool original, bool sa)
 {
 	const int32_t nt = (int32_t)names.size();
 	// contigs in byte-wise name order: the device compares (rank, pos) where the reference compares make_pair(chr, pos)
@@ -1828,6 +1835,12 @@ static void rt_begin_for(const vector<string> &names, int min_mapq, ssv_ctx *ctx
 	ssv_rt_params rp;
 	memset(&rp, 0, sizeof(rp));
 	rp.min_mapq = min_mapq; rp.n_targets = nt; rp.name_rank = rank.data();
+	if (sa) { // -S: the SA entries name contigs, which the session looks up
+		vector<const char *> ptrs((size_t)nt + 1, nullptr);
+		for (int32_t t = 0; t < nt; ++t) ptrs[(size_t)t] = names[(size_t)t].c_str();
+		check(ctx, ssv_rt_begin_original_sa(ctx, &rp, ptrs.data()));
+		return;
+	}
 	check(ctx, original ? ssv_rt_begin_original(ctx, &rp) : ssv_rt_begin(ctx, &rp));
 }
 
@@ -2167,8 +2180,21 @@ static int getsv_main(const GetsvOptions &opt, RunSession *run)
 		check(rt_ctx, ssv_rt_original_stats(rt_ctx, &st));
 		cerr << "[seeksv] -A: " << st.pairs << " pairs (" << st.pairs_borrowed << " with a borrowed seq) of " << st.candidates << " one-side-clipped records (" << st.hard_clipped
 		     << " hard-clipped); dropped at the pairing: " << st.dropped_no_carrier << " without a record that carries the read, " << st.dropped_length << " for unequal read lengths" << endl;
+		if (run->splitread_sa) {
+			ssv_rt_original_sa_counts sa;
+			check(rt_ctx, ssv_rt_original_sa_stats(rt_ctx, &sa));
+			cerr << "[seeksv] -S: sa_tags " << sa.sa_tags << ", sa_multi " << sa.sa_multi << ", sa_refused " << sa.sa_refused << ", virtuals " << sa.virtuals << ", sa_redundant " << sa.sa_redundant
+			     << ", pairs_from_sa " << sa.pairs_from_sa << ", sa_dropped_length " << sa.sa_dropped_length << endl;
+		}
 		pt.lap("splitread (run -A: the original's own supplementary alignments)");
-		if (pt.on) {
+		if (pt.on && run->splitread_sa) {
+			double ms = 0; int64_t launches = 0;
+			ssv_prof_get(rt_ctx, "splitread_sa_finish", &ms, &launches, nullptr);
+			cerr << "[timing] (-A -S kernel time: splitread_sa_aux " << run->splitread_aux_ms << " ms in " << run->splitread_aux_launches << " launches, splitread_sa_scan " << run->splitread_scan_ms << " ms in "
+			     << run->splitread_scan_launches << " launches, splitread_sa_finish " << ms << " ms in " << launches << " launches; the scans held the pump for " << run->splitread_scan_wall
+			     << " s; candidate store " << st.store_bytes << " bytes)" << endl;
+			ssv_prof_enable(rt_ctx, 0);
+		} else if (pt.on) {
 			double ms = 0; int64_t launches = 0;
 			ssv_prof_get(rt_ctx, "splitread_finish", &ms, &launches, nullptr);
 			cerr << "[timing] (-A kernel time: splitread_scan " << run->splitread_scan_ms << " ms in " << run->splitread_scan_launches << " launches, splitread_finish " << ms << " ms in " << launches
@@ -3330,6 +3356,13 @@ static void run_split_leg(RunAligner &aligner, RunSession *run, ssv_ctx *rt_ctx,
 	     << "                               run; it is not restricted by -L / -X; with -u it runs in input order; a read of three or more pieces gives what hold / pair /\n"
 	     << "                               drop gives, no chaining.  Takes a BAM or SAM text, with -u, -M, -D, -L, -X.  Not with -P, -F in -v or -N above 1, not inside\n"
 	     << "                               -c, -v or -a\n"
+	     << "         -S                    with -A: a record that holds all bases of its read and names ONE other alignment in its SA tag (SA:Z:rname,pos,strand,CIGAR,\n"
+	     << "                               mapQ,NM; as `bwa mem` and minimap2 write it) also stands for that alignment when its record is not in the input - a region\n"
+	     << "                               slice, a file written with `samtools view -F 0x800`, a supplementary record that is a duplicate or below the MAPQ floor.  The\n"
+	     << "                               entry is used only when the record found no real partner, so a complete input gives what -A gives.  The contig must be in\n"
+	     << "                               the header, the CIGAR must have exactly one clipped end (S stands for the record's H) and mapQ must reach -w of -v; a value\n"
+	     << "                               with two or more entries is counted and left alone (no chaining).  stderr reports sa_tags, sa_multi, sa_refused, virtuals,\n"
+	     << "                               sa_redundant, pairs_from_sa and sa_dropped_length.  Only with -A; not inside -c, -v or -a\n"
 	     << "         -N <int>              cut the BAM into N runs of records, one per GPU (ranks share GPUs when there are fewer): every rank decodes its run once and\n"
 	     << "                               keeps it in its own GPU's memory, the getsv pass scans the runs where they lie and the ranks' tallies and depths meet in one\n"
 	     << "                               RCCL all-gather; the aligner step runs on the first GPU.  Same files and stdout as without it.  Not with -P; -c and -v\n"
@@ -3342,11 +3375,12 @@ static int cmd_run(int argc, char **argv)
 {
 	int c, device = 0, n_ranks = 1;
 	string clip_opts, sv_opts, aln_opts, device_list;
-	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false, splitread = false;
+	bool split = false, ranks_given = false, mark_dups = false, unsorted = false, pair_dups = false, splitread = false, splitread_sa = false;
 	string include_file, exclude_file;
-	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuDL:X:A")) >= 0) {
+	while ((c = getopt(argc, argv, "c:v:a:G:PN:MuDL:X:AS")) >= 0) {
 		switch (c) {
 		case 'A': splitread = true; break;
+		case 'S': splitread_sa = true; break;
 		case 'P': split = true; break;
 		case 'M': mark_dups = true; break;
 		case 'u': unsorted = true; break;
@@ -3373,6 +3407,14 @@ static int cmd_run(int argc, char **argv)
 		std::istringstream in(*words);
 		for (string w; in >> w;)
 			if (w == "-A") die("seeksv run: -A scans the records that this run decodes, once, on their way into GPU memory; -A inside -c, -v or -a is not supported");
+	}
+	if (splitread_sa) { // -S is run's own, and a mode of -A (inside -a, -S stays realign's own option when -S is not given to run)
+		for (const string *words : {&clip_opts, &sv_opts, &aln_opts}) {
+			std::istringstream in(*words);
+			for (string w; in >> w;)
+				if (w == "-S") die("seeksv run: -S reads the SA tags of the records that this run decodes, as a mode of run's own -A; -S inside -c, -v or -a is not supported with it");
+		}
+		if (!splitread) die("seeksv run: -S adds the SA tags' alignments to the split-read pass of -A; -S without -A is not supported");
 	}
 	for (const string *words : {&clip_opts, &sv_opts}) {
 		std::istringstream in(*words);
@@ -3420,7 +3462,7 @@ static int cmd_run(int argc, char **argv)
 	// what run decides itself
 	clip.device_inflate = true; clip.n_ranks = n_ranks; clip.device = device; clip.devices = ranked ? devices : vector<int>(1, device); // (ranks without -G take the machine's GPUs in order)
 	clip.prefix = prefix; clip.bamfile = bam; clip.mark_dups = mark_dups; clip.sort_input = unsorted; clip.pair_dups = pair_dups;
-	clip.splitread = splitread; clip.splitread_mapq = sv.min_mapQ2;
+	clip.splitread = splitread; clip.splitread_mapq = sv.min_mapQ2; clip.splitread_sa = splitread_sa;
 	clip.regions_file = include_file.empty() ? exclude_file : include_file; clip.regions_exclude = include_file.empty() && !exclude_file.empty();
 	sv.device = device; sv.devices = vector<int>(1, device);
 	sv.clip_bam = prefix + ".clip.bam"; sv.original_bam = bam; sv.clipfile = prefix + ".clip.gz"; sv.breakpoint_file = prefix + ".sv.txt"; sv.clip_unmap_fq_file = prefix + ".unmapped.clip.fq";
